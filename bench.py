@@ -16,6 +16,12 @@ advances every session by one token; value = generated tokens/s over the whole n
     python bench.py                       # N=1 (defaults finish in ~1-2 minutes)
     python bench.py --gpus N              # spawns the N ranks itself (no launcher needed)
     torchrun --nproc-per-node N bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --full       # + the second timed phase on another stage-hop data plane
+    python bench.py --dump-outputs DIR    # + DIR/tokens.npy, DIR/logits.npy of the last timed step
+
+A plain run does what the headline figure needs and no more: set-up, warm-up, the --steps timed
+steps, the result line.  Inputs (weights, prompts, sampling seeds) depend on the arguments only,
+so two builds run with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -177,6 +183,27 @@ def run_failover_drill(a, cfg, eng, ex, rank, world, S, R, M, B, device, load_s)
     os._exit(code)
 
 
+DUMP_ARRAY_BYTES = 32 << 20  # per array; the two arrays of a run stay under 64 MB together
+
+
+def dump_array(out_dir: str, name: str, arr) -> str:
+    """``--dump-outputs``: write ``arr`` (float32 / float64) as ``out_dir/name.npy``.  An array above
+    DUMP_ARRAY_BYTES is cut to a fixed sample of its flattened elements (seeded, sorted indices, the
+    same for every run of the same shape)."""
+    import numpy as np
+
+    arr = np.ascontiguousarray(arr)
+    assert arr.dtype in (np.float32, np.float64), arr.dtype
+    keep = DUMP_ARRAY_BYTES // arr.itemsize
+    if arr.size > keep:
+        idx = np.sort(np.random.default_rng(0).choice(arr.size, size=keep, replace=False))
+        arr = arr.reshape(-1)[idx]
+    os.makedirs(out_dir, exist_ok=True)
+    path = os.path.join(out_dir, name + ".npy")
+    np.save(path, arr)
+    return path
+
+
 def _free_port() -> int:
     import socket
 
@@ -293,10 +320,19 @@ def main(argv=None):
                     help="stage-hop data plane: ProcessGroupNCCL (nccl, the GPU default), the framework's own "
                          "RCCL communicators (rccl; + MPAMD_GRAPH_HOP=1 records the hop inside the decode graph), "
                          "or host-staged gloo")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the second timed phase on another "
+                         "stage-hop data plane (--phase2).  A plain run sets up, warms up, times --steps steps, "
+                         "writes --dump-outputs and prints the result line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned to its callers as "
+                         "DIR/<name>.npy: tokens.npy (float64, one sampled token id per session, in session order) "
+                         "and logits.npy (float32, the logits rows of the step's last micro-batch, one per session "
+                         "in it)")
     ap.add_argument("--phase2", default="auto", choices=["auto", "off", "rccl", "nccl", "gloo"],
-                    help="after the headline phase, a second timed phase of the same pipelines on another stage-hop "
-                         "data plane, in the same processes: auto = the framework's RCCL communicators with the hop "
-                         "recorded in the decode graphs (rccl + graph hop) whenever the headline ran on "
+                    help="with --full: after the headline phase, a second timed phase of the same pipelines on another "
+                         "stage-hop data plane, in the same processes: auto = the framework's RCCL communicators with "
+                         "the hop recorded in the decode graphs (rccl + graph hop) whenever the headline ran on "
                          "ProcessGroupNCCL with >= 2 stages; reported under 'phase2' (ok or the failure reason), "
                          "never replacing the headline value")
     ap.add_argument("--phase2-timeout", type=float, default=180.0,
@@ -311,6 +347,8 @@ def main(argv=None):
                     help="test hook: make the second phase fail on the last stage rank at communicator set-up "
                          "(init) or in the middle of its timed steps (run)")
     a = ap.parse_args(argv)
+    if a.phase2 not in ("auto", "off") and not a.full:
+        ap.error(f"--phase2 {a.phase2} needs --full (a plain run times the headline phase only)")
 
     from src import ops
     from src.models.config import resolve_model
@@ -465,6 +503,15 @@ def main(argv=None):
         if phase == "start":
             gc_runs[info["generation"]] += 1
 
+    last_out = []  # --dump-outputs: what the executor returned in the newest step (replaced every step)
+    if a.dump_outputs:
+        compute = eng._compute
+
+        def _keep_last(seq_recs, x, m):
+            last_out[:] = [compute(seq_recs, x, m)]
+            return last_out[0]
+
+        eng._compute = _keep_last
     gc.callbacks.append(_gc_cb)
     t1 = time.perf_counter()
     eng.timing = True
@@ -475,6 +522,9 @@ def main(argv=None):
     dt_local = time.perf_counter() - t1
     gc.callbacks.remove(_gc_cb)
     eng.timing = False
+    if a.dump_outputs and last_out and stage == S - 1 and lane == 0:
+        # the tail's last timed step: its logits rows, before anything else runs on the executor
+        dump_array(a.dump_outputs, "logits", last_out[0].detach().float().cpu().numpy())
     if ch is not None:
         ch.timing = False
     stage_ms = eng.stage_ms() or 0.0
@@ -487,6 +537,11 @@ def main(argv=None):
         n_tokens = eng.tokens_generated
         if any(r.done for r in eng.finished):
             raise SystemExit("a benchmark session finished early: the timed rounds would be short of work")
+        if a.dump_outputs and lane == 0 and a.steps > 0:
+            # what the engine's caller received from the last timed step: one token per session
+            import numpy as np
+
+            dump_array(a.dump_outputs, "tokens", np.asarray([r.generated[-1] for r in reqs1], dtype=np.float64))
         eng.stop()
     else:
         eng.serve()  # until the head's STOP
@@ -582,8 +637,8 @@ def main(argv=None):
 
 
 def phase2_backend(a, S, R, TP, device, data_plane):
-    """The second phase's data plane, or None: only pure pipelines (no replicas / TP)."""
-    if a.phase2 == "off" or S < 2 or R != 1 or TP != 1:
+    """The second phase's data plane, or None: only with --full, only pure pipelines (no replicas / TP)."""
+    if not a.full or a.phase2 == "off" or S < 2 or R != 1 or TP != 1:
         return None
     if a.phase2 == "auto":
         return "rccl" if (device.type == "cuda" and data_plane == "pgnccl") else None

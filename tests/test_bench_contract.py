@@ -85,7 +85,7 @@ def _spawn2(extra, timeout=240):
 def test_bench_second_phase_same_tokens():
     """The second timed phase runs the same sessions on a second channel in the same processes and
     draws exactly the headline phase's tokens."""
-    rec = _spawn2(["--phase2", "gloo"])
+    rec = _spawn2(["--full", "--phase2", "gloo"])
     p2 = rec["phase2"]
     assert p2["ok"] is True and p2["data_plane"].startswith("gloo"), p2
     assert p2["tokens_match_headline"] is True and p2["sessions_compared"] == 6
@@ -101,8 +101,48 @@ def test_bench_second_phase_failure_keeps_headline(extra, stage):
     """A second phase that cannot set up its communicators (the RCCL data plane on a CPU run; an
     injected set-up error on one rank) or loses a rank mid-run is reported as ``phase2.ok = false``
     with its reason; the command still exits 0 with the headline numbers."""
-    rec = _spawn2(extra)
+    rec = _spawn2(["--full", *extra])
     p2 = rec["phase2"]
     assert p2["ok"] is False and p2["reason"], p2
     if stage:
         assert p2["stage"] == stage
+
+
+def _plain1(extra):
+    cmd = [sys.executable, "bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1", "--model", "tiny-llama",
+           "--device", "cpu", "--batch", "2", "--prompt-len", "8", *extra]
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
+    env["OMP_NUM_THREADS"] = "1"
+    return subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=240, env=env)
+
+
+def test_bench_dump_outputs_repeatable(tmp_path):
+    """``--dump-outputs DIR`` writes the last timed step's tokens (one per session) and logits rows as
+    float64 / float32 ``.npy``; two runs with the same arguments write identical arrays, and the
+    result line keeps its keys (``ms_per_step`` over exactly ``--steps`` timed steps)."""
+    import numpy as np
+
+    got = []
+    for name in ("a", "b"):
+        r = _plain1(["--dump-outputs", str(tmp_path / name)])
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout
+        rec = json.loads(lines[0])
+        assert KEYS <= set(rec) and rec["steps"] == 3 and rec["ms_per_step"] > 0 and "phase2" not in rec
+        assert rec["value"] == pytest.approx(3 * 2 / (3 * rec["ms_per_step"] / 1000), rel=1e-2)
+        assert sorted(os.listdir(tmp_path / name)) == ["logits.npy", "tokens.npy"]
+        got.append((np.load(tmp_path / name / "tokens.npy"), np.load(tmp_path / name / "logits.npy")))
+    (tok_a, log_a), (tok_b, log_b) = got
+    assert tok_a.dtype == np.float64 and tok_a.shape == (2,)
+    assert log_a.dtype == np.float32 and log_a.shape == (2, 512) and np.isfinite(log_a).all()
+    assert ((tok_a >= 0) & (tok_a < 512) & (tok_a == np.floor(tok_a))).all()
+    assert np.array_equal(tok_a, tok_b) and np.array_equal(log_a, log_b)
+
+
+def test_bench_second_phase_needs_full():
+    """The second phase belongs to ``--full``: asking for one on a plain run is an error, not a
+    silently longer (or silently shorter) run."""
+    r = _plain1(["--phase2", "gloo"])
+    assert r.returncode != 0 and "--full" in r.stderr
+    assert not [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
