@@ -6,8 +6,10 @@ for memory/disk with quantization-aware bytes per parameter) and petals/server/s
 per block)), ``attn_cache_tokens`` default 16384 for GQA models, 4096 otherwise).
 
 MI355X specifics: weights and KV are both resident in HBM (288 GB per GPU), there is no
-autograd reserve in an inference-only server, and the quantized weight format is OCP fp8
-(e4m3, 1 byte per parameter + per-channel scales) rather than bitsandbytes INT8/NF4.
+autograd reserve in an inference-only server, and the quantized weight formats are OCP fp8
+(e4m3, 1 byte per parameter + per-channel scales) and OCP MXFP4 (e2m1 + one e8m0 scale per 32
+weights: 4.25 bits per parameter, the figure upstream budgets for NF4) rather than bitsandbytes
+INT8/NF4.
 """
 from __future__ import annotations
 
@@ -18,7 +20,8 @@ import torch
 from .models.config import ModelConfig
 
 # bytes per parameter of the stored weight format
-_QUANT_BYTES = {None: None, "none": None, "fp8": 1.0, "int8": 1.0, "nf4": 4.25 / 8}
+_QUANT_BYTES = {None: None, "none": None, "fp8": 1.0, "int8": 1.0, "nf4": 4.25 / 8, "mxfp4": 4.25 / 8}
+_CHANNEL_SCALES = ("fp8", "int8")  # formats with per-output-channel fp32 scales beside the weights
 _DTYPE_BYTES = {torch.float32: 4, torch.float16: 2, torch.bfloat16: 2}
 
 
@@ -39,7 +42,8 @@ def get_block_size(cfg: ModelConfig, location: str = "memory", dtype=torch.bfloa
     """Bytes of one decoder block's parameters (``location`` = "memory" or "disk").
 
     On disk the checkpoint dtype counts; in memory the quantized format does (fp8: 1 B per
-    parameter for the projection matrices, norms stay 16-bit).
+    parameter for the projection matrices + per-channel fp32 scales; mxfp4: 4.25 bits per
+    parameter, block scales included; norms stay 16-bit).
     """
     if location not in ("memory", "disk"):
         raise ValueError(f"location must be 'memory' or 'disk', got {location!r}")
@@ -51,7 +55,7 @@ def get_block_size(cfg: ModelConfig, location: str = "memory", dtype=torch.bfloa
     norms = 2 * H * elt
     matrices = cfg.layer_param_bytes(1.0) - 2 * H  # parameter count of the projection matrices
     scales = (cfg.q_dim + 2 * cfg.kv_dim + H + 2 * cfg.intermediate_size + H) * 4  # per-channel fp32
-    return int(matrices * q + norms + scales)
+    return int(matrices * q + norms + (scales if quant_type in _CHANNEL_SCALES else 0))
 
 
 def default_attn_cache_tokens(cfg: ModelConfig) -> int:

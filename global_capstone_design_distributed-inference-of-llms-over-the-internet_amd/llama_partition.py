@@ -74,11 +74,36 @@ def resolve_dtype(dtype, device) -> torch.dtype:
     return dt
 
 
+QUANT_CHOICES = ("none", "fp8", "mxfp4", "nf4", "int8")
+# upstream's bitsandbytes formats map to the native format of the same width
+_QUANT_ALIASES = {"nf4": "mxfp4", "int8": "fp8"}
+
+
+def resolve_quant_type(quant_type) -> str:
+    """``--quant_type`` -> "none", "fp8" or "mxfp4".  Upstream's names map to the gfx950-native
+    format of the same size, with one log line saying so (as ``resolve_dtype`` does for fp16)."""
+    q = "none" if quant_type is None else str(quant_type).lower()
+    if q not in QUANT_CHOICES:
+        raise ValueError(f"quant_type must be one of {QUANT_CHOICES}, got {quant_type!r}")
+    if q == "nf4":
+        logger.info("nf4 requested on MI355X: the 4-bit HIP kernels take OCP MXFP4 (e2m1 + e8m0 block scales, the "
+                    "same 4.25 bits per weight; hardware convert, no NF4 table); using mxfp4")
+    elif q == "int8":
+        logger.info("int8 requested on MI355X: the 8-bit HIP kernels take OCP fp8 (e4m3, per-channel scales, the "
+                    "same 1 byte per weight); using fp8")
+    return _QUANT_ALIASES.get(q, q)
+
+
 def load_stage_model(model_name: str, device, role: str, *, start: int = 0, end: Optional[int] = None,
                      dtype=torch.bfloat16, use_cpu_offload: bool = False, seed: int = 0,
-                     **executor_kwargs) -> LoadedStage:
-    """Load ONLY the role's blocks (+ embeddings for stage0, norm/head for last)."""
+                     quant_type: Optional[str] = None, **executor_kwargs) -> LoadedStage:
+    """Load ONLY the role's blocks (+ embeddings for stage0, norm/head for last).  ``quant_type``
+    ("fp8" / "mxfp4", or upstream's "int8" / "nf4"): the blocks are quantized one by one as they
+    are built."""
     cfg = resolve_model(model_name)
+    quant = resolve_quant_type(quant_type)
+    if quant != "none" and use_cpu_offload:
+        raise ValueError(f"CPU offload is not supported with {quant} weights")
     L = cfg.num_hidden_layers
     if role == "stage0":
         s, e = 0, end
@@ -98,8 +123,9 @@ def load_stage_model(model_name: str, device, role: str, *, start: int = 0, end:
     dt = resolve_dtype(dtype, device)
     load_dev = torch.device("cpu") if use_cpu_offload else device
     w = build_stage_weights(cfg, model_name, s, e, has_embed=role in ("stage0", "full"),
-                            has_head=role in ("last", "full"), device=load_dev, dtype=dt, seed=seed)
-    logger.info(f"load_stage_model: role={role}, layers={e - s}, start={s}, end={e}")
+                            has_head=role in ("last", "full"), device=load_dev, dtype=dt, seed=seed,
+                            quant_type=quant)
+    logger.info(f"load_stage_model: role={role}, layers={e - s}, start={s}, end={e}, quant_type={quant}")
     return LoadedStage(cfg, w, role, s, e, device, dt, model_name, executor_kwargs, bool(use_cpu_offload))
 
 

@@ -42,7 +42,7 @@ from .comm.registry import DHT, get_dht_time
 from .comm.rpc import RpcServer, get_loop
 from .dht_utils import (DEFAULT_TTL, get_module_entries, get_remote_module_infos, get_stage_key, register_blocks_on_dht,
                         register_model_on_dht, register_server_on_dht, register_stage_on_dht)
-from .llama_partition import load_stage_model, resolve_dtype
+from .llama_partition import QUANT_CHOICES, load_stage_model, resolve_dtype, resolve_quant_type
 from .load_balancing import ServerState, choose_best_blocks, should_choose_other_blocks
 from .models.config import resolve_model
 from .models.tokenizer import load_tokenizer
@@ -78,6 +78,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--temperature", type=float, default=1.0)
     p.add_argument("--top_p", type=float, default=0.92)
     p.add_argument("--top_k", type=int, default=50)
+    p.add_argument("--quant_type", default="none", choices=list(QUANT_CHOICES),
+                   help="stage servers: stored weight format of the blocks (mxfp4 = OCP MXFP4, 4.25 bits per "
+                        "weight; fp8 = OCP e4m3; upstream's nf4 / int8 map to mxfp4 / fp8)")
     p.add_argument("--use_cpu_offload", action="store_true")
     p.add_argument("--keep_layers_on_gpu", type=int, default=0)
     p.add_argument("--use_load_balancing", action="store_true")
@@ -488,6 +491,14 @@ def _log_stage_stats(replica: int, rows, route) -> None:
 
 
 # ================================================================================ servers
+def _quant(args) -> str:
+    """``--quant_type`` resolved once per process (the nf4 / int8 mapping logs one line)."""
+    q = getattr(args, "_quant_resolved", None)
+    if q is None:
+        q = args._quant_resolved = resolve_quant_type(getattr(args, "quant_type", "none"))
+    return q
+
+
 class _Server:
     """RPC server + handler + heartbeat for one loaded span."""
 
@@ -521,7 +532,7 @@ class _Server:
         a, ex = self.args, self.ex
         exp = get_dht_time() + a.ttl
         extra = dict(start_block=ex.start, end_block=ex.end, final_stage=self.final,
-                     cache_tokens_left=int(ex.sessions.cache_tokens_left()))
+                     cache_tokens_left=int(ex.sessions.cache_tokens_left()), quant_type=ex.quant_type)
         if self.next_pings:
             extra["next_pings"] = dict(self.next_pings)
         if self.lb:
@@ -629,7 +640,7 @@ def run_stage_server_fixed(args, device, cuts: List[int], stop: Optional[threadi
     role = "last" if final else "segment"
     dtype = resolve_dtype(args.dtype, device)
     full = load_stage_model(args.model, device, role, start=s, end=e, dtype=dtype, seed=args.seed,
-                            use_cpu_offload=args.use_cpu_offload, **_executor_kwargs(args))
+                            use_cpu_offload=args.use_cpu_offload, quant_type=_quant(args), **_executor_kwargs(args))
     off = bool(args.use_cpu_offload) and device.type == "cuda"
     ex = StageExecutor(cfg, full.weights if off or not args.use_cpu_offload else _onto(full, device), device,
                        dtype=dtype, offload=off, keep_layers_on_gpu=args.keep_layers_on_gpu, **full.executor_kwargs)
@@ -656,10 +667,12 @@ def run_stage_server_with_load_balancing(args, device, cuts: List[int], stop: Op
     total = args.total_blocks or cfg.num_hidden_layers
     min_block = cuts[0] if cuts else 0
     dtype = resolve_dtype(args.dtype, device)
+    quant = _quant(args)
     if args.num_blocks is None and getattr(args, "auto_num_blocks", False) and device.type == "cuda":
         from .block_utils import auto_num_blocks
 
-        num_blocks = auto_num_blocks(cfg, dtype=dtype, device=device, total_blocks=total - min_block)
+        num_blocks = auto_num_blocks(cfg, dtype=dtype, quant_type=quant, device=device,
+                                     total_blocks=total - min_block)
         logger.info(f"auto num_blocks = {num_blocks}")
     else:
         num_blocks = args.num_blocks or 4
@@ -696,7 +709,7 @@ def run_stage_server_with_load_balancing(args, device, cuts: List[int], stop: Op
         final = e >= total
         logger.info(f"Selected blocks [{s}, {e}) (final={final})")
         full = load_stage_model(args.model, device, "last" if final else "segment", start=s, end=e, dtype=dtype,
-                                seed=args.seed, **_executor_kwargs(args))
+                                seed=args.seed, quant_type=quant, **_executor_kwargs(args))
         ex = StageExecutor(cfg, full.weights, device, dtype=dtype, **full.executor_kwargs)
         tb = max(1, int(getattr(args, "throughput_batch", 16)))
         srv = _Server(args, dht, ex, final, args.stage, throughput=FALLBACK_THROUGHPUT, lb=True, announce=False)

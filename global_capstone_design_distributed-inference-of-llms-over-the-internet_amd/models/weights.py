@@ -76,6 +76,16 @@ class LlamaLayer:
     gate_up_ws: Optional[torch.Tensor] = None
     down_w8: Optional[torch.Tensor] = None
     down_ws: Optional[torch.Tensor] = None
+    # OCP MXFP4 W4A16 copies (ops.pack_weight_w4: e2m1 codes + one e8m0 scale per 32 weights
+    # along K), qkv / gate_up quantized with the norm weights folded in (``folded``)
+    qkv_w4: Optional[torch.Tensor] = None
+    qkv_s4: Optional[torch.Tensor] = None
+    o_w4: Optional[torch.Tensor] = None
+    o_s4: Optional[torch.Tensor] = None
+    gate_up_w4: Optional[torch.Tensor] = None
+    gate_up_s4: Optional[torch.Tensor] = None
+    down_w4: Optional[torch.Tensor] = None
+    down_s4: Optional[torch.Tensor] = None
     # Mixtral sparse-MoE block (HF MixtralSparseMoeBlock): ``router`` [E, H]; gate_up / down
     # (and their packed copies) are then stacked per expert: [E, 2F, H] / [E, H, F]
     router: Optional[torch.Tensor] = None
@@ -96,14 +106,21 @@ class LlamaLayer:
     def w8(self) -> bool:
         return self.qkv_w8 is not None
 
+    @property
+    def w4(self) -> bool:
+        return self.qkv_w4 is not None
+
     def dense(self, name: str, dtype=torch.bfloat16) -> torch.Tensor:
-        """Row-major weight ``name`` (dequantized on the fly when only an fp8 copy is kept; a
-        W8A16 layer's qkv / gate_up then carry the folded norm weights, see ``folded``)."""
+        """Row-major weight ``name`` (dequantized on the fly when only an fp8 or MXFP4 copy is
+        kept; a W8A16 / W4A16 layer's qkv / gate_up then carry the folded norm weights, see
+        ``folded``)."""
+        from .. import ops
+
+        if getattr(self, name + "_w4") is not None:  # (also when a 16-bit copy was kept: it is unfolded)
+            return ops.unpack_weight_w4(getattr(self, name + "_w4"), getattr(self, name + "_s4"), dtype)
         w = getattr(self, name)
         if w is not None:
             return w
-        from .. import ops
-
         if getattr(self, name + "_w8") is not None:
             return ops.unpack_weight_w8(getattr(self, name + "_w8"), getattr(self, name + "_ws"), dtype)
         return ops.unpack_weight_fp8(getattr(self, name + "_q"), getattr(self, name + "_s"), dtype)
@@ -245,9 +262,49 @@ class StageWeights:
                 setattr(lay, name + "_s", None)
             lay.folded = bool(fold_norms)
 
+    def quantize_mxfp4(self, drop_dense: bool = True) -> None:
+        """OCP MXFP4 weights (4.25 bits per weight) for every projection: the W4A16 decode path.
+
+        The input / post-attention RMSNorm weights are folded into qkv / gate_up along K BEFORE
+        the one quantization (W' = W diag(g), computed in fp32), and ``folded`` is set: every path
+        over these weights normalises with a unit RMSNorm weight.  ``drop_dense`` frees the 16-bit
+        copies (prefill and > 64-row steps then dequantize one projection at a time).  Embeddings,
+        norms and lm_head stay 16-bit."""
+        from .. import ops
+
+        if self.cfg.is_moe:
+            raise ValueError("MXFP4 weights are not supported for MoE (Mixtral) models")
+        for lay in self.layers:
+            if not isinstance(lay, LlamaLayer):
+                raise ValueError("MXFP4 weights are built for Llama-family stages only")
+            if lay.w4:
+                continue
+            if lay.fp8 or lay.folded:
+                raise ValueError("quantize_mxfp4 needs the unquantized, unfolded 16-bit weights")
+            for name in LlamaLayer.PROJ:
+                N, K = getattr(lay, name).shape
+                if N % 16 or K % 128 or (name == "gate_up" and N % 32):
+                    raise ValueError(f"MXFP4 weights need N % 16 == 0 and K % 128 == 0: {name} is [{N}, {K}]")
+            for name, g in (("qkv", lay.input_norm), ("o", None), ("gate_up", lay.post_norm), ("down", None)):
+                w = getattr(lay, name).float()
+                if g is not None:
+                    w = w * g.float()[None, :]
+                w4, s4 = ops.pack_weight_w4(w)
+                del w
+                setattr(lay, name + "_w4", w4)
+                setattr(lay, name + "_s4", s4)
+                if drop_dense:
+                    setattr(lay, name, None)
+                    setattr(lay, name + "_p", None)
+            lay.folded = True
+
     @property
     def fp8(self) -> bool:
         return bool(self.layers) and all(isinstance(L, LlamaLayer) and L.fp8 for L in self.layers)
+
+    @property
+    def w4(self) -> bool:
+        return bool(self.layers) and all(isinstance(L, LlamaLayer) and L.w4 for L in self.layers)
 
     @property
     def w8(self) -> bool:
@@ -258,13 +315,39 @@ class StageWeights:
         for lay in self.layers:
             for f in dataclasses.fields(lay):
                 t = getattr(lay, f.name)
-                if t is not None and id(t) not in seen:
+                if isinstance(t, torch.Tensor) and id(t) not in seen:  # (``folded`` is a flag, not a tensor)
                     seen.add(id(t))
                     yield t
         for t in (self.embed, self.pos_embed, self.final_norm, self.final_norm_b, self.lm_head, self.lm_head_p):
             if t is not None and id(t) not in seen:
                 seen.add(id(t))
                 yield t
+
+
+QUANT_TYPES = (None, "none", "fp8", "mxfp4")
+
+
+def resolve_quant(quant_type: Optional[str], fp8: bool = False) -> Optional[str]:
+    """The weight builders' ``quant_type`` / ``fp8`` arguments -> None, "fp8" or "mxfp4"."""
+    if quant_type not in QUANT_TYPES:
+        raise ValueError(f"quant_type must be one of {QUANT_TYPES}, got {quant_type!r}")
+    quant = None if quant_type in (None, "none") else quant_type
+    if fp8:
+        if quant not in (None, "fp8"):
+            raise ValueError(f"fp8=True contradicts quant_type={quant_type!r}")
+        quant = "fp8"
+    return quant
+
+
+def _quantize_block(cfg: ModelConfig, idx: int, lay, quant: str) -> None:
+    """Quantize one freshly built block in place (its 16-bit copies are dropped)."""
+    if quant == "fp8" and not isinstance(lay, LlamaLayer):
+        return
+    one = StageWeights(cfg, idx, idx + 1, [lay])
+    if quant == "mxfp4":
+        one.quantize_mxfp4(drop_dense=True)
+    else:
+        one.quantize_fp8(drop_dense=True)
 
 
 def _gen(device, seed: int):
@@ -310,17 +393,19 @@ def _random_gpt2_layer(cfg: ModelConfig, idx: int, device, dtype, seed: int) -> 
 
 
 def random_stage_weights(cfg: ModelConfig, start: int, end: int, *, has_embed: bool, has_head: bool, device,
-                         dtype=torch.bfloat16, seed: int = 0, fp8: bool = False) -> StageWeights:
-    """``fp8``: quantize each block as soon as it is generated (bf16 copies dropped), so a
-    70B stage never holds its full bf16 weights."""
+                         dtype=torch.bfloat16, seed: int = 0, fp8: bool = False,
+                         quant_type: Optional[str] = None) -> StageWeights:
+    """``quant_type`` ("fp8" / "mxfp4"; ``fp8=True`` is the older spelling of "fp8"): quantize each
+    block as soon as it is generated (16-bit copies dropped), so a 70B stage never holds its full
+    bf16 weights."""
     device = torch.device(device)
+    quant = resolve_quant(quant_type, fp8)
     mk = _random_gpt2_layer if cfg.model_type == "gpt2" else _random_llama_layer
     layers = []
     for i in range(start, end):
         lay = mk(cfg, i, device, dtype, seed)
-        if fp8 and isinstance(lay, LlamaLayer):
-            one = StageWeights(cfg, i, i + 1, [lay])
-            one.quantize_fp8(drop_dense=True)
+        if quant is not None:
+            _quantize_block(cfg, i, lay, quant)
         layers.append(lay)
     sw = StageWeights(cfg, start, end, layers)
     H, V = cfg.hidden_size, cfg.vocab_size
@@ -415,7 +500,11 @@ class _Checkpoint:
 
 
 def load_stage_weights(cfg: ModelConfig, path: str, start: int, end: int, *, has_embed: bool, has_head: bool,
-                       device, dtype=torch.bfloat16) -> StageWeights:
+                       device, dtype=torch.bfloat16, quant_type: Optional[str] = None) -> StageWeights:
+    """``quant_type`` ("fp8" / "mxfp4"): each block is quantized as soon as it is read."""
+    quant = resolve_quant(quant_type)
+    if quant is not None and (cfg.model_type == "gpt2" or cfg.is_moe):
+        raise ValueError(f"quant_type={quant} is built for dense Llama-family models only")
     ck = _Checkpoint(path)
     dev = torch.device(device)
 
@@ -456,6 +545,8 @@ def load_stage_weights(cfg: ModelConfig, path: str, start: int, end: int, *, has
         gu = interleave_gate_up(t(p + "mlp.gate_proj.weight"), t(p + "mlp.up_proj.weight")).contiguous()
         layers.append(LlamaLayer(t(p + "input_layernorm.weight"), qkv, t(p + "self_attn.o_proj.weight"),
                                  t(p + "post_attention_layernorm.weight"), gu, t(p + "mlp.down_proj.weight")))
+        if quant is not None:
+            _quantize_block(cfg, i, layers[-1], quant)
     sw = StageWeights(cfg, start, end, layers)
     if has_embed:
         sw.embed = t("model.embed_tokens.weight")
@@ -469,7 +560,8 @@ def load_stage_weights(cfg: ModelConfig, path: str, start: int, end: int, *, has
 
 
 def build_stage_weights(cfg: ModelConfig, model: str, start: int, end: int, *, has_embed: bool, has_head: bool,
-                        device, dtype=torch.bfloat16, seed: int = 0) -> StageWeights:
+                        device, dtype=torch.bfloat16, seed: int = 0,
+                        quant_type: Optional[str] = None) -> StageWeights:
     """Checkpoint weights when ``model`` is a local HF directory, synthetic weights for presets.
 
     A directory without loadable weights is an error: silently serving a real config with
@@ -479,6 +571,6 @@ def build_stage_weights(cfg: ModelConfig, model: str, start: int, end: int, *, h
             raise FileNotFoundError(f"--model {model!r} is a directory without *.safetensors or pytorch_model*.bin "
                                     f"weights (pass a preset name such as llama2-7b for synthetic weights)")
         return load_stage_weights(cfg, model, start, end, has_embed=has_embed, has_head=has_head, device=device,
-                                  dtype=dtype)
+                                  dtype=dtype, quant_type=quant_type)
     return random_stage_weights(cfg, start, end, has_embed=has_embed, has_head=has_head, device=device, dtype=dtype,
-                                seed=seed)
+                                seed=seed, quant_type=quant_type)

@@ -1339,6 +1339,63 @@ def linear_w8(x, w8, w_scale, a_rows: int, out=None, epilogue: int = 0, residual
 
 
 # ---------------------------------------------------------------------------------------
+# W4A16 decode GEMM (csrc/gemm_w4.hip mp_gemm_w4): OCP MXFP4 weights - e2m1 codes, one e8m0 scale
+# per 32 weights along K, 4.25 bits per weight - dequantized in registers into the bf16 MFMA
+# (v_cvt_scalef32_pk_bf16_fp4), bf16 activations.  Weight layout, in the bf16 fragment order:
+#   w4 uint8 [N/16, K/128, 64, 16]: lane = 16 q + c; byte 4 s + b = the codes of
+#       W[16 nt + c][128 kb + 32 s + 8 q + 2 b] (low nibble) and the next k (high nibble): one
+#       16-byte lane load is the lane's 8 weights of each of four consecutive 32-deep k-slices s;
+#   s4 uint8 [N/16, K/128, 16, 4]: column c, one scale byte per k-slice (its four q groups share it).
+def pack_weight_w4(w: torch.Tensor):
+    """W [N, K] (N % 16 == 0, K % 128 == 0) -> (w4, s4), quantized by the OCP MX rule
+    (``reference.quant_mxfp4``); runs on CPU and GPU tensors."""
+    return ref.pack_weight_w4(w)
+
+
+def unpack_weight_w4(w4: torch.Tensor, s4: torch.Tensor, dtype=torch.bfloat16) -> torch.Tensor:
+    """MXFP4 -> row-major W [N, K] (exact: code x 2^(e - 127) is a bf16 value).  GPU tensors go
+    through the HIP dequantizer (one launch) when the kernel library is loaded."""
+    if w4.is_cuda and native_available():
+        w = torch.ops.mpamd.dequant_w4(w4, s4)
+        return w if dtype == torch.bfloat16 else w.to(dtype)
+    return ref.unpack_weight_w4(w4, s4, dtype)
+
+
+_W4_OK = {}
+
+
+def w4_gemm_ok(M: int, N: int, K: int, epilogue: int = 0) -> bool:
+    """Whether the W4A16 ring kernel covers the shape (M <= 64; epilogue 0, 1 = packed SwiGLU, 3)."""
+    key = (int(M), int(N), int(K), int(epilogue))
+    if key not in _W4_OK:
+        _W4_OK[key] = bool(native_available() and torch.ops.mpamd.gemm_w4_ok(*key))
+    return _W4_OK[key]
+
+
+def linear_w4(x, w4, s4, a_rows: int, out=None, epilogue: int = 0, residual=None, out_packed: bool = False,
+              ss_in=None, eps: float = 0.0, ap_out=None, ss_out=None, ss_zero=None):
+    """``linear`` with an MXFP4 weight (``pack_weight_w4``) and a PACKED bf16 activation of
+    ``a_rows`` rows (M <= 64): the one-launch ring kernel with the fused-norm path's epilogues (0
+    with optional ``ss_in`` row scale, packed SwiGLU, 3 = residual-stream producer).  A shape the
+    kernel does not cover raises.  Out of scope for 4-bit weights: the split-K ring,
+    ``linear_partials`` / the qkv fold, a start-up autotuner, W4A8 / W4A4 on the block-scaled
+    MFMA, and MoE / tensor-parallel / offloaded stages."""
+    M = int(a_rows)
+    N, K = 16 * w4.shape[0], 128 * w4.shape[1]
+    if not _native(x):
+        return linear(x, None, out=out, epilogue=epilogue, residual=residual, wp=pack_weight(
+            unpack_weight_w4(w4, s4, x.dtype)), a_rows=M, out_packed=out_packed, ss_in=ss_in, eps=eps,
+            ap_out=ap_out, ss_out=ss_out, ss_zero=ss_zero)
+    ncols = N // 2 if epilogue == 1 else N
+    if out is None:
+        out = (torch.empty(packed_numel(M, ncols), dtype=x.dtype, device=x.device) if out_packed
+               else torch.empty(M, ncols, dtype=x.dtype, device=x.device))
+    torch.ops.mpamd.gemm_w4(x, w4, s4, out, residual, int(epilogue), M, 1 | (2 if out_packed else 0), ap_out, ss_out,
+                            ss_zero, ss_in, 1.0 / K, float(eps))
+    return out
+
+
+# ---------------------------------------------------------------------------------------
 # W8A8-MX decode GEMM (csrc/gemm_mx.hip): the W8A16 fp8 weights x MX e4m3 activations (e8m0 scale
 # per 32-element block) on gfx950's block-scaled MFMA, split-K ring form + reduce launch.
 def mx_buffers(M: int, K: int, device):

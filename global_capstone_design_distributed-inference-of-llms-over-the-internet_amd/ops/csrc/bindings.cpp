@@ -62,6 +62,11 @@ int mp_gemm_ss_elems();
 int mp_gemm_w8(const void* x, const void* wq, const float* wsc, void* y, int64_t y_stride, const void* res,
                int64_t res_stride, int M, int N, int K, int epilogue, int flags, void* ws, void* ap, void* ss_out,
                void* ss_zero, const void* ss_in, float inv_k, float eps, hipStream_t stream);
+int mp_gemm_w4(const void* x, const void* w4, const void* s4, void* y, int64_t y_stride, const void* res,
+               int64_t res_stride, int M, int N, int K, int epilogue, int flags, void* ap, void* ss_out, void* ss_zero,
+               const void* ss_in, float inv_k, float eps, hipStream_t stream);
+int mp_gemm_w4_ok(int M, int N, int K, int epilogue);
+int mp_dequant_w4(const void* w4, const void* s4, void* w, int N, int K, hipStream_t stream);
 int mp_pack_act(const void* x, int64_t xs, void* ap, int M, int K, hipStream_t stream);
 int mp_quant_mx(const void* ap, void* ax, void* as, int M, int K, hipStream_t stream);
 int mp_gemm_mx(const void* ax, const void* as, const void* wq, const float* wsc, void* y, int64_t y_stride,
@@ -650,6 +655,78 @@ void gemm_w8(const at::Tensor& x, const at::Tensor& wq, const at::Tensor& wsc, a
   check_launch(rc, "gemm_w8");
 }
 
+// MXFP4 weight operands (gemm_w4.hip): codes uint8 [N/16, K/128, 64, 16] + e8m0 scales uint8 [N/16, K/128, 16, 4]
+static void check_w4(const at::Tensor& w4, const at::Tensor& s4) {
+  MP_CHECK(w4.is_cuda() && w4.scalar_type() == at::kByte && w4.dim() == 4 && w4.size(2) == 64 && w4.size(3) == 16 &&
+               w4.is_contiguous(),
+           "w4 must be an MXFP4 weight uint8 [N/16, K/128, 64, 16] (ops.pack_weight_w4)");
+  MP_CHECK(s4.is_cuda() && s4.scalar_type() == at::kByte && s4.dim() == 4 && s4.size(0) == w4.size(0) &&
+               s4.size(1) == w4.size(1) && s4.size(2) == 16 && s4.size(3) == 4 && s4.is_contiguous() &&
+               s4.device() == w4.device(),
+           "s4 must be the e8m0 block scales uint8 [N/16, K/128, 16, 4] (ops.pack_weight_w4)");
+}
+
+// W4A16 decode GEMM (gemm_w4.hip mp_gemm_w4): packed bf16 x (M rows), MXFP4 weight; flags bit 1 =
+// packed SwiGLU output
+void gemm_w4(const at::Tensor& x, const at::Tensor& w4, const at::Tensor& s4, at::Tensor& y,
+             const c10::optional<at::Tensor>& residual, int64_t epilogue, int64_t M_, int64_t flags,
+             const c10::optional<at::Tensor>& ap, const c10::optional<at::Tensor>& ss_out,
+             const c10::optional<at::Tensor>& ss_zero, const c10::optional<at::Tensor>& ss_in, double inv_k,
+             double eps) {
+  check_bf16_cuda(x, "x");
+  check_bf16_cuda(y, "y");
+  check_w4(w4, s4);
+  const int N = 16 * w4.size(0), K = 128 * w4.size(1);
+  const int M = (int)M_;
+  const bool opk = flags & 2;
+  MP_CHECK(M >= 0 && M <= 64, "gemm_w4: 0 <= M <= 64");
+  MP_CHECK(x.is_contiguous() && x.numel() >= packed_numel(M, K), "packed x too small");
+  MP_CHECK(epilogue == 0 || epilogue == 3 || (epilogue == 1 && opk), "gemm_w4: epilogue 0, 3 or packed SwiGLU");
+  MP_CHECK(epilogue != 1 || N % 32 == 0, "gemm_w4: SwiGLU needs N % 32 == 0");
+  const int ncols = epilogue == 1 ? N / 2 : N;
+  if (opk) {
+    MP_CHECK(epilogue == 1 && y.is_contiguous() && y.numel() >= packed_numel(M, ncols), "packed y");
+  } else {
+    check_rows(y, "y");
+    MP_CHECK(y.size(0) == M && y.size(1) == ncols, "y shape");
+  }
+  const void* rp = nullptr;
+  int64_t rs = 0;
+  if (residual.has_value()) {
+    check_bf16_cuda(*residual, "residual");
+    check_rows(*residual, "residual");
+    MP_CHECK(residual->size(0) == M && residual->size(1) == N, "residual shape");
+    rp = residual->data_ptr();
+    rs = residual->stride(0);
+  }
+  void* app = nullptr;
+  if (ap.has_value()) {
+    check_bf16_cuda(*ap, "ap");
+    MP_CHECK(ap->is_contiguous() && ap->numel() >= packed_numel(M, N), "ap: packed [ceil(M/16)*16*N]");
+    app = ap->data_ptr();
+  }
+  MP_CHECK(epilogue != 3 || (app != nullptr && rp != nullptr), "epilogue 3 needs residual and ap");
+  const int rc = mp_gemm_w4(x.data_ptr(), w4.data_ptr(), s4.data_ptr(), y.data_ptr(), opk ? 0 : y.stride(0), rp, rs, M,
+                            N, K, (int)epilogue, (int)flags, app, opt_ss(ss_out, "ss_out"), opt_ss(ss_zero, "ss_zero"),
+                            opt_ss(ss_in, "ss_in"), (float)inv_k, (float)eps, cur_stream());
+  TORCH_CHECK(rc != 1, "mpamd: gemm_w4: no MXFP4-weight kernel covers M=", M, " N=", N, " K=", K, " epilogue=",
+              epilogue);
+  check_launch(rc, "gemm_w4");
+}
+
+bool gemm_w4_ok(int64_t M, int64_t N, int64_t K, int64_t epilogue) {
+  return mp_gemm_w4_ok((int)M, (int)N, (int)K, (int)epilogue) != 0;
+}
+
+// MXFP4 weight -> row-major bf16 [N, K]
+at::Tensor dequant_w4(const at::Tensor& w4, const at::Tensor& s4) {
+  check_w4(w4, s4);
+  const int N = 16 * w4.size(0), K = 128 * w4.size(1);
+  auto w = at::empty({N, K}, w4.options().dtype(at::kBFloat16));
+  check_launch(mp_dequant_w4(w4.data_ptr(), s4.data_ptr(), w.data_ptr(), N, K, cur_stream()), "dequant_w4");
+  return w;
+}
+
 int64_t gemm_workspace_bytes() { return mp_gemm_workspace_bytes(); }
 int64_t gemm_slab_offset() { return mp_gemm_slab_offset(); }
 int64_t gemm_rwk_split(int64_t M, int64_t N, int64_t K, int64_t f8) {
@@ -857,6 +934,12 @@ TORCH_LIBRARY(mpamd, m) {
       "gemm_w8(Tensor x, Tensor wq, Tensor wsc, Tensor(a!) y, Tensor? residual, int epilogue, int M, int flags, "
       "Tensor(b!)? workspace=None, Tensor(c!)? ap=None, Tensor(d!)? ss_out=None, Tensor(e!)? ss_zero=None, "
       "Tensor? ss_in=None, float inv_k=0., float eps=0.) -> ()");
+  m.def(
+      "gemm_w4(Tensor x, Tensor w4, Tensor s4, Tensor(a!) y, Tensor? residual, int epilogue, int M, int flags, "
+      "Tensor(c!)? ap=None, Tensor(d!)? ss_out=None, Tensor(e!)? ss_zero=None, Tensor? ss_in=None, float inv_k=0., "
+      "float eps=0.) -> ()");
+  m.def("gemm_w4_ok(int M, int N, int K, int epilogue) -> bool", &gemm_w4_ok);
+  m.def("dequant_w4(Tensor w4, Tensor s4) -> Tensor");
   m.def("pack_act(Tensor x, Tensor(a!) ap) -> ()");
   m.def("pack_weight(Tensor w) -> Tensor");
   m.def("quant_act_fp8(Tensor ap, Tensor(a!) a8, Tensor(b!) scale, int M, int K) -> ()");
@@ -887,6 +970,8 @@ TORCH_LIBRARY_IMPL(mpamd, CUDA, m) {
   m.impl("sample", &sample);
   m.impl("gemm", &gemm);
   m.impl("gemm_w8", &gemm_w8);
+  m.impl("gemm_w4", &gemm_w4);
+  m.impl("dequant_w4", &dequant_w4);
   m.impl("pack_weight", &pack_weight);
   m.impl("pack_act", &pack_act);
   m.impl("quant_act_fp8", &quant_act_fp8);

@@ -353,3 +353,80 @@ def linear_fp8(a8, a_scale, wq, w_scale, M, epilogue=0, residual=None, dtype=tor
     if epilogue == 2:
         return (y.to(dtype).float() + residual.float()).to(dtype)
     return y.to(dtype)
+
+
+# ------------------------------------------------------------------ OCP MXFP4 weights (W4A16)
+# e2m1 codes (sign bit 3, bits 2..0 index E2M1_VALUES) with one e8m0 scale byte per 32 weights
+# along K: 4 + 8 / 32 = 4.25 bits per weight.  Packed layout (csrc/gemm_w4.hip):
+#   w4 uint8 [N/16, K/128, 64, 16]: lane = 16 q + c, byte 4 s + b holds the codes of
+#       W[16 nt + c][128 kb + 32 s + 8 q + 2 b] (low nibble) and of the next k (high nibble) - a
+#       lane's 16 bytes are its 8 weights of each of four consecutive 32-deep k-slices s;
+#   s4 uint8 [N/16, K/128, 16, 4]: column c, one scale byte per k-slice s.
+E2M1_VALUES = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
+MX_BLOCK = 32
+
+
+def quant_mxfp4(w):
+    """W [N, K] -> (codes uint8 [N, K], scale bytes uint8 [N, K/32]) by the OCP MX rule: e =
+    clamp(floor(log2(amax)) - 2 + 127, 1, 254) per 32-block (1 for an all-zero block), codes =
+    x / 2^(e - 127) rounded to nearest e2m1 with ties to the even code, saturating at +-6; the
+    code 0b1000 (negative zero) is never emitted."""
+    N, K = w.shape
+    if K % MX_BLOCK:
+        raise ValueError(f"MXFP4 needs K % {MX_BLOCK} == 0 (K={K})")
+    x = w.detach().float().reshape(N, K // MX_BLOCK, MX_BLOCK)
+    amax = x.abs().amax(-1)
+    _, ex = torch.frexp(amax)  # amax = m 2^ex, m in [0.5, 1): floor(log2(amax)) = ex - 1
+    e = torch.where(amax > 0, (ex.to(torch.int32) - 1 - 2 + 127).clamp(1, 254), torch.ones_like(ex, dtype=torch.int32))
+    scale = (e << 23).view(torch.float32)  # 2^(e - 127), exact
+    a = (x / scale[..., None]).abs()
+    code = ((a > 0.25).to(torch.uint8) + (a >= 0.75).to(torch.uint8) + (a > 1.25).to(torch.uint8)
+            + (a >= 1.75).to(torch.uint8) + (a > 2.5).to(torch.uint8) + (a >= 3.5).to(torch.uint8)
+            + (a > 5.0).to(torch.uint8))
+    code = code | (((x < 0) & (code > 0)).to(torch.uint8) << 3)
+    return code.reshape(N, K), e.to(torch.uint8)
+
+
+def dequant_mxfp4(code, e, dtype=torch.float32):
+    """codes [N, K], scale bytes [N, K/32] -> W [N, K] = value(code) * 2^(e - 127) (exact in bf16)."""
+    N, K = code.shape
+    tab = torch.tensor(E2M1_VALUES + tuple(-v for v in E2M1_VALUES), dtype=torch.float32, device=code.device)
+    scale = (e.to(torch.int32) << 23).view(torch.float32)
+    v = tab[code.long()].reshape(N, K // MX_BLOCK, MX_BLOCK) * scale[..., None]
+    return v.reshape(N, K).to(dtype)
+
+
+def pack_mxfp4(code, e):
+    """codes [N, K], scale bytes [N, K/32] -> (w4, s4) in the decode GEMM's fragment order (layout above)."""
+    N, K = code.shape
+    if N % 16 or K % 128:
+        raise ValueError(f"MXFP4 weights need N % 16 == 0 and K % 128 == 0 (N={N}, K={K})")
+    by = code[:, 0::2] | (code[:, 1::2] << 4)  # [N, K/2]: lower k in the low nibble
+    # byte index k/2 = 64 kb + 16 s + 4 q + b  ->  [nt, kb, q, c, s, b]
+    w4 = by.view(N // 16, 16, K // 128, 4, 4, 4).permute(0, 2, 4, 1, 3, 5).reshape(N // 16, K // 128, 64, 16)
+    s4 = e.view(N // 16, 16, K // 128, 4).permute(0, 2, 1, 3)
+    return w4.contiguous(), s4.contiguous()
+
+
+def unpack_mxfp4(w4, s4):
+    """Inverse of ``pack_mxfp4``: (codes uint8 [N, K], scale bytes uint8 [N, K/32])."""
+    n16, k128 = w4.shape[0], w4.shape[1]
+    N, K = n16 * 16, k128 * 128
+    by = w4.view(n16, k128, 4, 16, 4, 4).permute(0, 3, 1, 4, 2, 5).reshape(N, K // 2)
+    code = torch.stack((by & 15, by >> 4), -1).reshape(N, K)
+    e = s4.view(n16, k128, 16, 4).permute(0, 2, 1, 3).reshape(N, K // MX_BLOCK)
+    return code, e
+
+
+def pack_weight_w4(w):
+    """W [N, K] (N % 16 == 0, K % 128 == 0) -> (w4 uint8 [N/16, K/128, 64, 16], s4 uint8
+    [N/16, K/128, 16, 4]): MXFP4 quantization (``quant_mxfp4``) + the fragment-order layout."""
+    N, K = w.shape
+    if N % 16 or K % 128:
+        raise ValueError(f"MXFP4 weights need N % 16 == 0 and K % 128 == 0 (N={N}, K={K})")
+    return pack_mxfp4(*quant_mxfp4(w))
+
+
+def unpack_weight_w4(w4, s4, dtype=torch.float32):
+    """Inverse layout of ``pack_weight_w4`` + dequantization -> W [N, K]."""
+    return dequant_mxfp4(*unpack_mxfp4(w4, s4), dtype)

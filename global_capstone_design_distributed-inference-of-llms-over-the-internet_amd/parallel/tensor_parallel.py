@@ -62,6 +62,8 @@ def _shard_gate_up(gu: torch.Tensor, r: int, tp: int) -> torch.Tensor:
 def _shard_layer(L: LlamaLayer, cfg: ModelConfig, r: int, tp: int) -> LlamaLayer:
     if L.fp8 and L.qkv is None:
         raise ValueError("shard bf16 weights before fp8 quantization")
+    if getattr(L, "w4", False):
+        raise ValueError("MXFP4 weights are not supported under tensor parallelism")
     D, nh, nkv = cfg.head_dim, cfg.num_attention_heads, cfg.num_key_value_heads
     qh, kh = nh // tp * D, nkv // tp * D
     q = L.qkv[: nh * D][r * qh:(r + 1) * qh]

@@ -247,6 +247,13 @@ class StageExecutor:
         self._mx = bool(self._w8 and fp8_mode == "mx")
         if self._w8:
             weights.prepare_w8a16(fold_norms=True)
+        # MXFP4 weights (StageWeights.quantize_mxfp4: norm weights folded in before the one
+        # quantization): <= 64-row decode steps run the fused-norm path on ops.linear_w4, everything
+        # else dequantizes one projection at a time (LlamaLayer.dense) and normalises with unit weights
+        self._w4 = bool(self.device.type == "cuda" and weights.w4 and cfg.model_type != "gpt2" and
+                        not cfg.is_moe and self._tp is None)
+        if weights.w4 and self._tp is not None:
+            raise ValueError("MXFP4 weights are not supported under tensor parallelism")
         # fused-norm decode path (ops/csrc/gemm.hip EpiArgs): no RMSNorm kernels between the
         # layers' GEMMs - dense bf16 or W8A16 Llama stages without TP (MoE / W8A8 / TP keep the
         # norm kernels)
@@ -273,7 +280,7 @@ class StageExecutor:
                 ops.load_kernel_table()  # the committed per-shape kernel choices (ops.KERNEL_TABLE)
                 if ops.autotune_mode() != "off":
                     H, F = cfg.hidden_size, cfg.intermediate_size
-                    shapes = [] if (weights.fp8 or not weights.layers) else \
+                    shapes = [] if (weights.fp8 or weights.w4 or not weights.layers) else \
                         [(cfg.q_dim + 2 * cfg.kv_dim, H, 0), (H, cfg.q_dim, 0), (2 * F, H, 1), (H, F, 0)]
                     if self._fused and shapes:
                         shapes += [(H, cfg.q_dim, 3), (H, F, 3)]
@@ -285,7 +292,9 @@ class StageExecutor:
                     if self._w8 and weights.layers:
                         ops.autotune_w8([(cfg.q_dim + 2 * cfg.kv_dim, H, 0), (H, cfg.q_dim, 3), (2 * F, H, 1),
                                          (H, F, 3)], self.device)
-                    if self._fused and weights.layers and self._fuse_rope:
+                    if self._w4:
+                        pass  # no 4-bit autotuner, no qkv fold: one ring form per shape
+                    elif self._fused and weights.layers and self._fuse_rope:
                         # qkv as split-K partials summed in the attention kernel, per row bucket
                         ops.autotune_qkv_fold(cfg.q_dim + 2 * cfg.kv_dim, H, self.device, fp8=bool(self._w8))
                     elif weights.fp8 and weights.layers:
@@ -302,6 +311,11 @@ class StageExecutor:
         logger.info(f"StageExecutor blocks [{self.start},{self.end}) embed={self.is_first} head={self.is_last} "
                     f"kv_pages={num_pages} x {page_size} tokens ({self.cache.nbytes / 2**30:.2f} GiB) "
                     f"graphs={self.use_graphs}")
+
+    @property
+    def quant_type(self) -> str:
+        """Stored weight format of this span's blocks: "none", "fp8" or "mxfp4" (announced by the server)."""
+        return "mxfp4" if self.w.w4 else ("fp8" if self.w.fp8 else "none")
 
     # ================================================================== planning
     def plan(self, seqs: Sequence[Tuple[str, int]], *, reset: Sequence[bool] = (), max_length: Optional[int] = None,
@@ -526,9 +540,9 @@ class StageExecutor:
         """Decode steps of T rows: qkv as split-K partial slabs folded into the attention kernel's
         loads - where ``_confirm_qkv_fold``'s decode-step A/B on this executor found it faster for
         the batch bucket the step replays (an unconfirmed bucket keeps the reduce launch)."""
-        if not (self._fuse_rope and self._fused and self.device.type == "cuda") or \
+        if not (self._fuse_rope and self._fused and self.device.type == "cuda") or self._w4 or \
                 os.environ.get("MPAMD_QKV_FOLD", "1") == "0":
-            return False
+            return False  # (a 4-bit stage has no split-K ring: never folded)
         cfg = self.cfg
         return bool(self.qkv_fold_by_bucket.get(self._bucket(T), False)) and \
             ops.rwk_split(T, cfg.q_dim + 2 * cfg.kv_dim, cfg.hidden_size, bool(self._w8)) > 0
@@ -572,7 +586,8 @@ class StageExecutor:
         e = lambda name, shape, dtype=dt: bufs.get(name) if name in bufs else torch.empty(shape, dtype=dtype, device=dev)  # noqa: E731
         fp8_dec = prompt is None and self._fp8_ok(T)
         fused_dec = (not fp8_dec and prompt is None and self._fused and self.n_layers > 0 and
-                     (T <= 64 and (self._w8 or self._packed_ok(T)) or (not self._w8 and self._fused_wide_ok(T))))
+                     (T <= 64 and (self._w8 or self._w4_ok(T) or self._packed_ok(T)) or
+                      (not self._w8 and not self._w4 and self._fused_wide_ok(T))))
         if self.is_first and not (fused_dec and self._fused_entry and x.dim() == 1 and x.is_contiguous()):
             h = ops.embedding(x, w.embed, out=e("h", (T, H)))
         elif self.is_first:
@@ -633,6 +648,9 @@ class StageExecutor:
             if self._w8:  # fp8 weights (W8A16): same launches, 1 byte per weight streamed
                 def gemm(a, L, name, **kw):
                     return ops.linear_w8(a, getattr(L, name + "_w8"), getattr(L, name + "_ws"), T, **kw)
+            elif self._w4:  # MXFP4 weights (W4A16): same launches, 4.25 bits per weight streamed
+                def gemm(a, L, name, **kw):
+                    return ops.linear_w4(a, getattr(L, name + "_w4"), getattr(L, name + "_s4"), T, **kw)
             else:
                 def gemm(a, L, name, **kw):
                     return ops.linear(a, None, wp=getattr(L, name + "_p"), a_rows=T, **kw)
@@ -705,12 +723,14 @@ class StageExecutor:
             act = e("act", (T, cfg.intermediate_size))
             fold_native = self._folded_native(T)
             for li, L in self._iter_layers(_DENSE_FIELDS):
-                # W8A16 layers' only weights carry the norm weights folded in (prepare_w8a16).
+                # W8A16 / MXFP4 layers' only weights carry the norm weights folded in (prepare_w8a16,
+                # quantize_mxfp4).
                 # bf16 layers packed for the fused path carry them in qkv_p / gate_up_p only: when
                 # the native GEMM would pick those up, normalise with a unit weight; otherwise
                 # keep the real norm weights and hand the GEMM the unfolded row-major weight only
-                folded_bf16 = L.folded and not L.w8
-                unit = (L.folded and L.w8) or (folded_bf16 and fold_native)
+                quant = L.w8 or L.w4
+                folded_bf16 = L.folded and not quant
+                unit = (L.folded and quant) or (folded_bf16 and fold_native)
                 g_in, g_post = (self._unit_norm(), self._unit_norm()) if unit else (L.input_norm, L.post_norm)
                 qkv_p = None if (folded_bf16 and not fold_native) else L.qkv_p
                 gu_p = None if (folded_bf16 and not fold_native) else L.gate_up_p
@@ -853,7 +873,7 @@ class StageExecutor:
         cfg = self.cfg
         N = cfg.q_dim + 2 * cfg.kv_dim
         key = (ops._m_bucket(B), N, cfg.hidden_size, bool(self._w8))
-        if not self.use_graphs or B > self.graph_max_batch or not (self._fuse_rope and self._fused) or \
+        if not self.use_graphs or B > self.graph_max_batch or not (self._fuse_rope and self._fused) or self._w4 or \
                 os.environ.get("MPAMD_QKV_FOLD", "1") == "0":
             return None
         Bb = self._bucket(B)
@@ -1004,6 +1024,8 @@ class StageExecutor:
         w = self.w
         if w.fp8:
             raise ValueError("CPU offload is not supported with fp8 weights")
+        if w.w4:
+            raise ValueError("CPU offload is not supported with MXFP4 weights")
 
         keep = max(0, min(int(keep_layers_on_gpu), self.n_layers))
         n_stream = self.n_layers - keep
@@ -1043,6 +1065,16 @@ class StageExecutor:
         cfg = self.cfg
         return all(d % 256 == 0 for d in (cfg.hidden_size, cfg.q_dim, cfg.intermediate_size)) and \
             (cfg.q_dim + 2 * cfg.kv_dim) % 32 == 0
+
+    def _w4_ok(self, M: int) -> bool:
+        """Fused-norm decode path of an MXFP4 stage: <= 64 rows, every projection's shape covered by
+        the W4A16 ring kernel (otherwise the step takes the dequantizing dense path)."""
+        if not self._w4 or not 0 < M <= 64:
+            return False
+        cfg = self.cfg
+        H, F = cfg.hidden_size, cfg.intermediate_size
+        return all(ops.w4_gemm_ok(M, N, K, epi) for N, K, epi in
+                   ((cfg.q_dim + 2 * cfg.kv_dim, H, 0), (H, cfg.q_dim, 3), (2 * F, H, 1), (H, F, 3)))
 
     def _packed_ok(self, M: int) -> bool:
         """Packed-activation decode path: GPU, native GEMM allowed, all projections packed; 65..256

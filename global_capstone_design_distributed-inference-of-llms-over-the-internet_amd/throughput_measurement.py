@@ -114,7 +114,7 @@ def _measure_forward(executor, sid, x, n_tokens, n_steps, dev) -> float:
 
 
 class ThroughputCache:
-    """JSON file of past measurements keyed by (model, span, dtype, device), guarded by an
+    """JSON file of past measurements keyed by (model, span, dtype, device, batch, quant type), guarded by an
     exclusive ``flock`` (upstream: one system-wide lock + ``throughput_v2.json``)."""
 
     def __init__(self, path: Optional[str] = None):
@@ -142,7 +142,11 @@ class ThroughputCache:
     def key(executor, batch: int = 1) -> str:
         dev = executor.device
         name = torch.cuda.get_device_name(dev) if dev.type == "cuda" else "cpu"
-        return f"{executor.cfg.name}|{executor.start}-{executor.end}|{executor.dtype}|{name}|b{int(batch)}"
+        # a quantized span streams fewer bytes per token: its measurements are its own (upstream
+        # keys the cache by quant type too); unquantized keys keep their form
+        quant = getattr(executor, "quant_type", "none")
+        q = "" if quant in (None, "none") else f"|{quant}"
+        return f"{executor.cfg.name}|{executor.start}-{executor.end}|{executor.dtype}|{name}|b{int(batch)}{q}"
 
     def get(self, key: str) -> Optional[dict]:
         with self._locked():
