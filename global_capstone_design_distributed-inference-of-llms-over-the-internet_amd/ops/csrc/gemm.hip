@@ -31,10 +31,7 @@ extern "C" int mp_gemm_ss_elems() { return mp::SS_NSH * mp::SS_ROWS; }
 
 // byte offset / size of the split-K partial-slab region inside the GEMM workspace (shared with
 // the fp8 split-K kernel, fp8.hip)
-extern "C" int64_t mp_gemm_slab_offset() {
-  using namespace mp;
-  return (int64_t)SK_MAX_GROUPS * sizeof(int) + SK_ZERO_BYTES + (int64_t)SK_MAX_BLOCKS * 2 * SK_MAX_S * 64 * sizeof(float);
-}
+extern "C" int64_t mp_gemm_slab_offset() { return mp::RWK_SLAB_OFFSET; }
 extern "C" int64_t mp_gemm_slab_bytes() { return mp::RWK_SLAB_BYTES; }
 
 // Split count S of the split-K ring form for this shape (0: not covered): with flags bit 14 the
@@ -54,11 +51,7 @@ extern "C" int mp_gemm_rwk_split(int M, int N, int K, int f8) {
   return S;
 }
 
-extern "C" int64_t mp_gemm_workspace_bytes() {
-  using namespace mp;
-  return (int64_t)SK_MAX_GROUPS * sizeof(int) + SK_ZERO_BYTES +
-         (int64_t)SK_MAX_BLOCKS * 2 * SK_MAX_S * 64 * sizeof(float) + RWK_SLAB_BYTES;
-}
+extern "C" int64_t mp_gemm_workspace_bytes() { return mp::RWK_SLAB_OFFSET + mp::RWK_SLAB_BYTES; }
 
 // flags: bit 0 = x is packed (Ap[K/32][ceil(M/16)][64][8]); bit 1 = SwiGLU output packed;
 //        bit 2 = use the stream-K kernel (needs ws: mp_gemm_workspace_bytes(), zero-initialised,
@@ -97,54 +90,40 @@ extern "C" int mp_gemm_bf16(const void* x, int64_t x_stride, const void* w, void
     if (rc == 0) return (int)hipGetLastError();
   }
   if ((flags & 1) && (flags & 256) && !(flags & 2) && gate == nullptr && ws != nullptr) {  // split-K ring
-#define MP_RWK(MT_) \
-  rc = launch_gemm_rwk<MT_>(x, w, y, y_stride, res, res_stride, M, N, K, epilogue, ep, ws, stream, rwk_comb(flags))
-    switch ((M + 15) / 16) {  // the packed layout's row-tile count is part of its strides
-      case 1: MP_RWK(1); break;
-      case 2: MP_RWK(2); break;
-      case 3: MP_RWK(3); break;
-      default: MP_RWK(4); break;
-    }
-#undef MP_RWK
+    rc = with_row_tiles(M, [&](auto mt) {
+      return launch_gemm_rwk<mt()>(x, w, y, y_stride, res, res_stride, M, N, K, epilogue, ep, ws, stream,
+                                   rwk_comb(flags));
+    });
     if (rc < 0) return rc;
     if (rc == 0) return (int)hipGetLastError();
   }
   if (flags & 16384) return -6;  // partials only: nothing else writes them
   if (gate != nullptr) flags &= ~(4 | 16 | 128);  // gated (MoE expert) GEMMs use the one-group kernel
   if ((flags & 1) && (flags & 128) && !(flags & 8)) {  // balanced ring kernel
-    if (M <= 16) rc = launch_gemm_rw<1>(x, w, y, y_stride, res, res_stride, M, N, K, epilogue, flags, ep, stream);
-    else if (M <= 32) rc = launch_gemm_rw<2>(x, w, y, y_stride, res, res_stride, M, N, K, epilogue, flags, ep, stream);
-    else if (M <= 48) rc = launch_gemm_rw<3>(x, w, y, y_stride, res, res_stride, M, N, K, epilogue, flags, ep, stream);
-    else rc = launch_gemm_rw<4>(x, w, y, y_stride, res, res_stride, M, N, K, epilogue, flags, ep, stream);
+    rc = with_row_tiles(M, [&](auto mt) {
+      return launch_gemm_rw<mt()>(x, w, y, y_stride, res, res_stride, M, N, K, epilogue, flags, ep, stream);
+    });
     if (rc < 0) return rc;
     if (rc == 0) return (int)hipGetLastError();
   }
   if ((flags & 1) && (flags & 16) && !(flags & 8)) {  // shared-A kernel
-    if (M <= 16) rc = launch_gemm_lds<1>(x, w, y, y_stride, res, res_stride, M, N, K, epilogue, flags, ep, stream);
-    else if (M <= 32) rc = launch_gemm_lds<2>(x, w, y, y_stride, res, res_stride, M, N, K, epilogue, flags, ep, stream);
-    else if (M <= 48) rc = launch_gemm_lds<3>(x, w, y, y_stride, res, res_stride, M, N, K, epilogue, flags, ep, stream);
-    else rc = launch_gemm_lds<4>(x, w, y, y_stride, res, res_stride, M, N, K, epilogue, flags, ep, stream);
+    rc = with_row_tiles(M, [&](auto mt) {
+      return launch_gemm_lds<mt()>(x, w, y, y_stride, res, res_stride, M, N, K, epilogue, flags, ep, stream);
+    });
     if (rc < 0) return rc;
     if (rc == 0) return (int)hipGetLastError();
   }
   if ((flags & 1) && (flags & 4) && !(flags & 8) && ws != nullptr) {
-    if (M <= 16) rc = launch_gemm_sk<1>(x, y, y_stride, w, res, res_stride, M, N, K, epilogue, flags, ws, ep, stream);
-    else if (M <= 32)
-      rc = launch_gemm_sk<2>(x, y, y_stride, w, res, res_stride, M, N, K, epilogue, flags, ws, ep, stream);
-    else if (M <= 48)
-      rc = launch_gemm_sk<3>(x, y, y_stride, w, res, res_stride, M, N, K, epilogue, flags, ws, ep, stream);
-    else rc = launch_gemm_sk<4>(x, y, y_stride, w, res, res_stride, M, N, K, epilogue, flags, ws, ep, stream);
+    rc = with_row_tiles(M, [&](auto mt) {
+      return launch_gemm_sk<mt()>(x, y, y_stride, w, res, res_stride, M, N, K, epilogue, flags, ws, ep, stream);
+    });
     if (rc < 0) return rc;
     if (rc == 0) return (int)hipGetLastError();
     // rc == 1: shape not covered by the stream-K form -> one-group-per-workgroup kernel
   }
-  if (M <= 16) rc = launch_gemm<1>(x, x_stride, w, y, y_stride, res, res_stride, M, N, K, epilogue, flags, gate, ep,
-                                   stream);
-  else if (M <= 32) rc = launch_gemm<2>(x, x_stride, w, y, y_stride, res, res_stride, M, N, K, epilogue, flags, gate,
-                                        ep, stream);
-  else if (M <= 48) rc = launch_gemm<3>(x, x_stride, w, y, y_stride, res, res_stride, M, N, K, epilogue, flags, gate,
-                                        ep, stream);
-  else rc = launch_gemm<4>(x, x_stride, w, y, y_stride, res, res_stride, M, N, K, epilogue, flags, gate, ep, stream);
+  rc = with_row_tiles(M, [&](auto mt) {
+    return launch_gemm<mt()>(x, x_stride, w, y, y_stride, res, res_stride, M, N, K, epilogue, flags, gate, ep, stream);
+  });
   if (rc) return rc;
   return (int)hipGetLastError();
 }

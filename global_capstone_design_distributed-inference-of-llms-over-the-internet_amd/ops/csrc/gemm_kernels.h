@@ -458,6 +458,9 @@ constexpr int SK_MAX_GROUPS = 1 << 15;
 constexpr int SK_MAX_BLOCKS = 512;
 constexpr int SK_MAX_S = 64;  // MT * NT * 4 accumulator slots per lane
 constexpr int SK_ZERO_BYTES = 4 * 1024;  // zero A fragments (MT <= 4) for masked units
+// workspace: counters, zeros, the stream-K slabs, then the split-K ring's partial slabs (RWK_SLAB_BYTES)
+constexpr int64_t RWK_SLAB_OFFSET =
+    (int64_t)SK_MAX_GROUPS * sizeof(int) + SK_ZERO_BYTES + (int64_t)SK_MAX_BLOCKS * 2 * SK_MAX_S * 64 * sizeof(float);
 
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
@@ -1775,8 +1778,7 @@ static int launch_gemm_rwk(const void* x, const void* w, void* y, int64_t ys, co
   if constexpr (MX) mx_geometry(tiles, nt, S);
   if (nt == 0) return 1;
   if ((int64_t)S * M * N * 4 > RWK_SLAB_BYTES) return 1;
-  float* part = (float*)((char*)ws + (int64_t)SK_MAX_GROUPS * sizeof(int) + SK_ZERO_BYTES +
-                         (int64_t)SK_MAX_BLOCKS * 2 * SK_MAX_S * 64 * sizeof(float));
+  float* part = (float*)((char*)ws + RWK_SLAB_OFFSET);
   const dim3 g1((tiles / nt) * S);
   int* tick = (int*)ws + SK_MAX_GROUPS / 2;  // rwk arrival tickets (the stream-K kernel uses the low half)
   if (inl && MT <= 4 && nt >= 2 && tiles / nt <= SK_MAX_GROUPS / 8 - 1 &&
@@ -1798,26 +1800,37 @@ static int launch_gemm_rwk(const void* x, const void* w, void* y, int64_t ys, co
       return 0;
     }
   }
+#define MP_RWKS(NT_)                                                                                           \
+  if constexpr (NT_ <= nt_max)                                                                                 \
+    hipLaunchKernelGGL((gemm_rwk_kernel<MT, NT_, F8, -1, MX>), g1, dim3(RW_WAVES * 64), 0, stream,             \
+                       (const bf16_t*)x, (const bf16_t*)w, part, M, N, K, S, ep, nullptr, 0, nullptr, 0, nullptr)
   switch (nt) {
-    case 1: hipLaunchKernelGGL((gemm_rwk_kernel<MT, 1, F8, -1, MX>), g1, dim3(RW_WAVES * 64), 0, stream, (const bf16_t*)x, (const bf16_t*)w, part, M, N, K, S, ep, nullptr, 0, nullptr, 0, nullptr); break;
-    case 2: hipLaunchKernelGGL((gemm_rwk_kernel<MT, 2, F8, -1, MX>), g1, dim3(RW_WAVES * 64), 0, stream, (const bf16_t*)x, (const bf16_t*)w, part, M, N, K, S, ep, nullptr, 0, nullptr, 0, nullptr); break;
-    case 4:
-      if constexpr (4 <= nt_max)
-        hipLaunchKernelGGL((gemm_rwk_kernel<MT, 4, F8, -1, MX>), g1, dim3(RW_WAVES * 64), 0, stream, (const bf16_t*)x, (const bf16_t*)w, part, M, N, K, S, ep, nullptr, 0, nullptr, 0, nullptr);
-      break;
-    case 6:
-      if constexpr (6 <= nt_max)
-        hipLaunchKernelGGL((gemm_rwk_kernel<MT, 6, F8, -1, MX>), g1, dim3(RW_WAVES * 64), 0, stream, (const bf16_t*)x, (const bf16_t*)w, part, M, N, K, S, ep, nullptr, 0, nullptr, 0, nullptr);
-      break;
-    default:
-      if constexpr (8 <= nt_max)
-        hipLaunchKernelGGL((gemm_rwk_kernel<MT, 8, F8, -1, MX>), g1, dim3(RW_WAVES * 64), 0, stream, (const bf16_t*)x, (const bf16_t*)w, part, M, N, K, S, ep, nullptr, 0, nullptr, 0, nullptr);
-      break;
+    case 1: MP_RWKS(1); break;
+    case 2: MP_RWKS(2); break;
+    case 4: MP_RWKS(4); break;
+    case 6: MP_RWKS(6); break;
+    default: MP_RWKS(8); break;
   }
+#undef MP_RWKS
   if (comb < 0) return 0;  // partials only: the consumer sums the S slabs itself (rwk_split)
   const dim3 g2(N / (256 * SKR_CPT), M);
   launch_splitk_reduce(S, epi, g2, stream, part, M, N, y, ys, res, rs, ep);
   return 0;
+}
+
+// Row tiles of a decode GEMM of M <= 64 rows as a compile-time constant: fn(integral_constant<MT>),
+// MT = ceil(M / 16) in 1..4 (the packed layout's row-tile count is part of its strides).  The entry
+// points used to spell this as ``switch ((M + 15) / 16)`` with default 4 or as an
+// ``M <= 16 / 32 / 48`` chain: the two agree for 1 <= M <= 64, which is all the callers pass (each
+// entry point returns for M == 0 and rejects or hands on M > 64 first).
+template <class Fn>
+static inline int with_row_tiles(int M, Fn&& fn) {
+  switch ((M + 15) / 16) {
+    case 1: return fn(std::integral_constant<int, 1>{});
+    case 2: return fn(std::integral_constant<int, 2>{});
+    case 3: return fn(std::integral_constant<int, 3>{});
+    default: return fn(std::integral_constant<int, 4>{});
+  }
 }
 
 }  // namespace mp

@@ -121,13 +121,10 @@ extern "C" int mp_gemm_mx(const void* ax, const void* as, const void* wq, const 
   ep.rot = (flags >> 10) & 1;
   ep.xsc = (const uint8_t*)as;
   const int comb = (flags & 16384) ? -1 : 0;
-  int rc;
-  switch ((M + 15) / 16) {
-    case 1: rc = launch_gemm_rwk<1, true, true>(ax, wq, y, y_stride, res, res_stride, M, N, K, epilogue, ep, ws, stream, comb); break;
-    case 2: rc = launch_gemm_rwk<2, true, true>(ax, wq, y, y_stride, res, res_stride, M, N, K, epilogue, ep, ws, stream, comb); break;
-    case 3: rc = launch_gemm_rwk<3, true, true>(ax, wq, y, y_stride, res, res_stride, M, N, K, epilogue, ep, ws, stream, comb); break;
-    default: rc = launch_gemm_rwk<4, true, true>(ax, wq, y, y_stride, res, res_stride, M, N, K, epilogue, ep, ws, stream, comb); break;
-  }
+  const int rc = with_row_tiles(M, [&](auto mt) {
+    return launch_gemm_rwk<mt(), true, true>(ax, wq, y, y_stride, res, res_stride, M, N, K, epilogue, ep, ws, stream,
+                                             comb);
+  });
   if (rc != 0) return rc;
   return (int)hipGetLastError();
 }

@@ -224,10 +224,9 @@ static int launch_gemm_rw4(const void* x, const void* w4, const void* s4, void* 
 static int gemm_w4_dispatch(const void* x, const void* w4, const void* s4, void* y, int64_t ys, const void* res,
                             int64_t rs, int M, int N, int K, int epi, bool opk, const EpiArgs& ep, hipStream_t stream,
                             bool dry) {
-  if (M <= 16) return launch_gemm_rw4<1>(x, w4, s4, y, ys, res, rs, M, N, K, epi, opk, ep, stream, dry);
-  if (M <= 32) return launch_gemm_rw4<2>(x, w4, s4, y, ys, res, rs, M, N, K, epi, opk, ep, stream, dry);
-  if (M <= 48) return launch_gemm_rw4<3>(x, w4, s4, y, ys, res, rs, M, N, K, epi, opk, ep, stream, dry);
-  return launch_gemm_rw4<4>(x, w4, s4, y, ys, res, rs, M, N, K, epi, opk, ep, stream, dry);
+  return with_row_tiles(M, [&](auto mt) {
+    return launch_gemm_rw4<mt()>(x, w4, s4, y, ys, res, rs, M, N, K, epi, opk, ep, stream, dry);
+  });
 }
 
 // One thread per 16-byte lane chunk: 32 weights (8 of each of 4 k-slices) -> 4 x 16 B of row-major bf16

@@ -21,21 +21,17 @@ extern "C" int mp_gemm_w8(const void* x, const void* wq, const float* wsc, void*
   ep.rot = (flags >> 10) & 1;
   int rc = 1;
   if ((flags & 256) && !(flags & 2) && ws != nullptr) {
-    switch ((M + 15) / 16) {
-      case 1: rc = launch_gemm_rwk<1, true>(x, wq, y, y_stride, res, res_stride, M, N, K, epilogue, ep, ws, stream, rwk_comb(flags)); break;
-      case 2: rc = launch_gemm_rwk<2, true>(x, wq, y, y_stride, res, res_stride, M, N, K, epilogue, ep, ws, stream, rwk_comb(flags)); break;
-      case 3: rc = launch_gemm_rwk<3, true>(x, wq, y, y_stride, res, res_stride, M, N, K, epilogue, ep, ws, stream, rwk_comb(flags)); break;
-      default: rc = launch_gemm_rwk<4, true>(x, wq, y, y_stride, res, res_stride, M, N, K, epilogue, ep, ws, stream, rwk_comb(flags)); break;
-    }
+    rc = with_row_tiles(M, [&](auto mt) {
+      return launch_gemm_rwk<mt(), true>(x, wq, y, y_stride, res, res_stride, M, N, K, epilogue, ep, ws, stream,
+                                         rwk_comb(flags));
+    });
     if (rc < 0) return rc;
     if (rc == 0) return (int)hipGetLastError();
   }
   if (flags & 16384) return -6;  // partials only: nothing else writes them
-  const int fl = flags | 1;
-  if (M <= 16) rc = launch_gemm_rw<1, true>(x, wq, y, y_stride, res, res_stride, M, N, K, epilogue, fl, ep, stream);
-  else if (M <= 32) rc = launch_gemm_rw<2, true>(x, wq, y, y_stride, res, res_stride, M, N, K, epilogue, fl, ep, stream);
-  else if (M <= 48) rc = launch_gemm_rw<3, true>(x, wq, y, y_stride, res, res_stride, M, N, K, epilogue, fl, ep, stream);
-  else rc = launch_gemm_rw<4, true>(x, wq, y, y_stride, res, res_stride, M, N, K, epilogue, fl, ep, stream);
+  rc = with_row_tiles(M, [&](auto mt) {
+    return launch_gemm_rw<mt(), true>(x, wq, y, y_stride, res, res_stride, M, N, K, epilogue, flags | 1, ep, stream);
+  });
   if (rc != 0) return rc;
   return (int)hipGetLastError();
 }

@@ -5,6 +5,22 @@
 // form faster (profiles/r5x).
 #include "gemm_t2d.h"
 
+// The instantiation that holds 65..256 rows: MT = 5, 6, 7, 8 row tiles, then 12 (129..192 rows)
+// and 16; fn(integral_constant<MT>) as with_row_tiles.  Callers pass 65 <= M <= 256 only
+// (mp_gemm_bf16 and mp_gemm_rw_ok check it): on that range this switch and the ``M <= 80 / 96 / 112 /
+// 128 / 192`` chains it replaces agree; below 65 rows it would pick 16 where the chains picked 5.
+template <class Fn>
+static inline int with_row_tiles_wide(int M, Fn&& fn) {
+  switch ((M + 15) / 16) {
+    case 5: return fn(std::integral_constant<int, 5>{});
+    case 6: return fn(std::integral_constant<int, 6>{});
+    case 7: return fn(std::integral_constant<int, 7>{});
+    case 8: return fn(std::integral_constant<int, 8>{});
+    case 9: case 10: case 11: case 12: return fn(std::integral_constant<int, 12>{});
+    default: return fn(std::integral_constant<int, 16>{});
+  }
+}
+
 extern "C" int mp_gemm_bf16_wide(const void* x, const void* w, void* y, int64_t y_stride, const void* res,
                                  int64_t res_stride, int M, int N, int K, int epilogue, int flags, void* ws,
                                  const mp::EpiArgs& ep, hipStream_t stream) {
@@ -18,26 +34,16 @@ extern "C" int mp_gemm_bf16_wide(const void* x, const void* w, void* y, int64_t 
     if (rc == 0) return (int)hipGetLastError();
   }
   if ((flags & 256) && !(flags & 2) && ws != nullptr) {  // split-K ring
-#define MP_RWK(MT_) \
-  rc = launch_gemm_rwk<MT_>(x, w, y, y_stride, res, res_stride, M, N, K, epilogue, ep, ws, stream, rwk_comb(flags))
-    switch ((M + 15) / 16) {
-      case 5: MP_RWK(5); break;
-      case 6: MP_RWK(6); break;
-      case 7: MP_RWK(7); break;
-      case 8: MP_RWK(8); break;
-      case 9: case 10: case 11: case 12: MP_RWK(12); break;
-      default: MP_RWK(16); break;
-    }
-#undef MP_RWK
+    rc = with_row_tiles_wide(M, [&](auto mt) {
+      return launch_gemm_rwk<mt()>(x, w, y, y_stride, res, res_stride, M, N, K, epilogue, ep, ws, stream,
+                                   rwk_comb(flags));
+    });
     if (rc < 0) return rc;
     if (rc == 0) return (int)hipGetLastError();
   }
-  if (M <= 80) rc = launch_gemm_rw<5>(x, w, y, y_stride, res, res_stride, M, N, K, epilogue, flags, ep, stream);
-  else if (M <= 96) rc = launch_gemm_rw<6>(x, w, y, y_stride, res, res_stride, M, N, K, epilogue, flags, ep, stream);
-  else if (M <= 112) rc = launch_gemm_rw<7>(x, w, y, y_stride, res, res_stride, M, N, K, epilogue, flags, ep, stream);
-  else if (M <= 128) rc = launch_gemm_rw<8>(x, w, y, y_stride, res, res_stride, M, N, K, epilogue, flags, ep, stream);
-  else if (M <= 192) rc = launch_gemm_rw<12>(x, w, y, y_stride, res, res_stride, M, N, K, epilogue, flags, ep, stream);
-  else rc = launch_gemm_rw<16>(x, w, y, y_stride, res, res_stride, M, N, K, epilogue, flags, ep, stream);
+  rc = with_row_tiles_wide(M, [&](auto mt) {
+    return launch_gemm_rw<mt()>(x, w, y, y_stride, res, res_stride, M, N, K, epilogue, flags, ep, stream);
+  });
   if (rc != 0) return rc < 0 ? rc : -1;
   return (int)hipGetLastError();
 }
@@ -65,13 +71,9 @@ extern "C" int mp_gemm_rw_ok(int M, int N, int K, int epilogue, int out_packed) 
   EpiArgs ep{};
   ep.mt_out = (M + 15) / 16;
   const int flags = 1 | (out_packed ? 2 : 0) | 128;
-  int rc;
-  if (M <= 80) rc = launch_gemm_rw<5>(nullptr, nullptr, nullptr, 0, nullptr, 0, M, N, K, epilogue, flags, ep, 0, true);
-  else if (M <= 96) rc = launch_gemm_rw<6>(nullptr, nullptr, nullptr, 0, nullptr, 0, M, N, K, epilogue, flags, ep, 0, true);
-  else if (M <= 112) rc = launch_gemm_rw<7>(nullptr, nullptr, nullptr, 0, nullptr, 0, M, N, K, epilogue, flags, ep, 0, true);
-  else if (M <= 128) rc = launch_gemm_rw<8>(nullptr, nullptr, nullptr, 0, nullptr, 0, M, N, K, epilogue, flags, ep, 0, true);
-  else if (M <= 192) rc = launch_gemm_rw<12>(nullptr, nullptr, nullptr, 0, nullptr, 0, M, N, K, epilogue, flags, ep, 0, true);
-  else rc = launch_gemm_rw<16>(nullptr, nullptr, nullptr, 0, nullptr, 0, M, N, K, epilogue, flags, ep, 0, true);
+  const int rc = with_row_tiles_wide(M, [&](auto mt) {
+    return launch_gemm_rw<mt()>(nullptr, nullptr, nullptr, 0, nullptr, 0, M, N, K, epilogue, flags, ep, 0, true);
+  });
   return rc == 0;
 }
 

@@ -326,8 +326,7 @@ static int launch_gemm_rg(const void* x, const void* w, void* y, int64_t ys, con
   float* part = nullptr;
   if (g.S > 1) {
     if (ws == nullptr || (int64_t)g.S * M * N * 4 > RWK_SLAB_BYTES) return 1;
-    part = (float*)((char*)ws + (int64_t)SK_MAX_GROUPS * sizeof(int) + SK_ZERO_BYTES +
-                    (int64_t)SK_MAX_BLOCKS * 2 * SK_MAX_S * 64 * sizeof(float));
+    part = (float*)((char*)ws + RWK_SLAB_OFFSET);
   }
   const bool opk = flags & 2;
   int rc = 1;
