@@ -15,6 +15,7 @@ from __future__ import annotations
 import math
 import os
 import threading
+from functools import partial
 from typing import Optional, Tuple
 
 import torch
@@ -159,6 +160,12 @@ def set_gemm_sk(mode: str) -> None:
     _GEMM_SK = mode
 
 
+def _dev_key(device):
+    """Key of the per-device caches: an index-less CUDA device means the current one."""
+    device = torch.device(device)
+    return device.type, device.index if device.index is not None else torch.cuda.current_device()
+
+
 def gemm_workspace(device) -> torch.Tensor:
     """Per-device scratch of the stream-K GEMM: split-group arrival counters, a zero A
     fragment for masked units, and fp32 partial slabs.
@@ -168,8 +175,7 @@ def gemm_workspace(device) -> torch.Tensor:
     uses it at a time (the executors' decode step is single-stream).  Call this before a
     hipGraph capture so the allocation does not happen inside it.
     """
-    device = torch.device(device)
-    key = (device.type, device.index if device.index is not None else torch.cuda.current_device())
+    key = _dev_key(device)
     ws = _GEMM_WS.get(key)
     if ws is None:
         require_native()
@@ -343,6 +349,33 @@ def _todo(table: dict, keys) -> list:
     return out
 
 
+def _todo_rows(table: dict, N: int, K: int, epi: int, ms) -> list:
+    """The row counts an autotuner times for one (N, K, epilogue): the last of ``ms`` in each M bucket
+    whose (bucket, N, K, epilogue) key ``_todo`` says to time."""
+    rows = {_m_bucket(M): M for M in ms}
+    keys = _todo(table, [(b, N, K, int(epi)) for b in rows])
+    return [M for b, M in rows.items() if (b, N, K, int(epi)) in keys]
+
+
+def _time_candidates(cands: dict, iters: int, rounds: int) -> dict:
+    """{name: best ms per call} of the callables ``cands[name](i)``, i = the call's number (which the
+    tuners use to rotate over weight copies).  The candidates are timed in alternating rounds, in
+    mapping order: two warm-up calls, then ``iters`` calls between two events; best round each."""
+    t = {name: float("inf") for name in cands}
+    for _ in range(rounds):
+        for name, fn in cands.items():
+            for i in range(2):
+                fn(i)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for i in range(iters):
+                fn(i)
+            e1.record()
+            e1.synchronize()
+            t[name] = min(t[name], e0.elapsed_time(e1) / iters)
+    return t
+
+
 def qkv_fold_pinned(bucket: int, N: int, K: int, fp8: bool) -> Optional[bool]:
     if autotune_mode() == "force":
         return None
@@ -371,8 +404,7 @@ def autotune_gemm(shapes, device, ms=(4, 16, 32, 48, 64), iters: int = 24, round
     pool = None
     try:
         for (N, K, epi) in shapes:
-            keys = _todo(_SK_CHOICE, list(dict.fromkeys((_m_bucket(M), N, K, int(epi)) for M in ms)))
-            todo = [M for M in dict((_m_bucket(M), M) for M in ms).values() if (_m_bucket(M), N, K, int(epi)) in keys]
+            todo = _todo_rows(_SK_CHOICE, N, K, epi, ms)
             if not todo:
                 continue
             if pool is None:
@@ -386,58 +418,33 @@ def autotune_gemm(shapes, device, ms=(4, 16, 32, 48, 64), iters: int = 24, round
                 wps = [pool[i * n:(i + 1) * n].view(N // 16, K // 32, 64, 8)
                        for i in range(min(16, pool.numel() // n))]
             copies = len(wps)
-            ncols = N // 2 if epi == 1 else N
             for M in todo:
+                key = (_m_bucket(M), N, K, int(epi))
                 cands = [k for k in _KERNEL_FLAGS if _covered(k, M, N, K, epi)]
                 if len(cands) == 1:
-                    _SK_CHOICE[(_m_bucket(M), N, K, int(epi))] = "pk"
+                    _SK_CHOICE[key] = "pk"
                     continue
                 xp = pack_act(torch.randn(M, K, device=device).to(torch.bfloat16))
-                y = torch.empty(packed_numel(M, ncols) if epi == 1 else M * ncols, dtype=torch.bfloat16,
-                                device=device)
                 res = torch.zeros(M, N, dtype=torch.bfloat16, device=device) if epi in (2, 3) else None
-                extra = {}
-                if epi == 3:  # fused-norm producer: packed copy + per-row sum of squares
-                    extra = dict(ap_out=torch.zeros(packed_numel(M, N), dtype=torch.bfloat16, device=device),
-                                 ss_out=norm_stats_buffer(device)[0], ss_zero=norm_stats_buffer(device)[0])
-                out = y if epi == 1 else (res if epi == 3 else y.view(M, ncols))
-                t = {k: float("inf") for k in cands}
-                for _ in range(rounds):
-                    for mode in cands:
-                        _GEMM_SK = mode
-                        for i in range(2):
-                            linear(xp, None, out=out, epilogue=epi, residual=res, wp=wps[i % copies], a_rows=M,
-                                   out_packed=epi == 1, **extra)
-                        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                        e0.record()
-                        for i in range(iters):
-                            linear(xp, None, out=out, epilogue=epi, residual=res, wp=wps[i % copies], a_rows=M,
-                                   out_packed=epi == 1, **extra)
-                        e1.record()
-                        e1.synchronize()
-                        t[mode] = min(t[mode], e0.elapsed_time(e1) / iters)
+                # fused-norm producer: packed copy + per-row sum of squares
+                extra = _epi3_scratch(M, N, device) if epi == 3 else {}
+                out = res if epi == 3 else _gemm_out(M, N // 2 if epi == 1 else N, epi == 1, torch.bfloat16, device)
+
+                def call(mode, i):
+                    global _GEMM_SK
+                    _GEMM_SK = mode
+                    linear(xp, None, out=out, epilogue=epi, residual=res, wp=wps[i % copies], a_rows=M,
+                           out_packed=epi == 1, **extra)
+
+                t = _time_candidates({k: partial(call, k) for k in cands}, iters, rounds)
                 best = min(t, key=t.get)
                 # keep the one-group kernel unless another wins by > 3 % (timing noise guard)
                 best = best if t[best] < 0.97 * t["pk"] else "pk"
                 # then the same kernel with the rotated k walk, kept if it wins by > 1 %
-                tr = {best: float("inf"), best + "+r": float("inf")}
-                for _ in range(rounds):
-                    for mode in tr:
-                        _GEMM_SK = mode
-                        for i in range(2):
-                            linear(xp, None, out=out, epilogue=epi, residual=res, wp=wps[i % copies], a_rows=M,
-                                   out_packed=epi == 1, **extra)
-                        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                        e0.record()
-                        for i in range(iters):
-                            linear(xp, None, out=out, epilogue=epi, residual=res, wp=wps[i % copies], a_rows=M,
-                                   out_packed=epi == 1, **extra)
-                        e1.record()
-                        e1.synchronize()
-                        tr[mode] = min(tr[mode], e0.elapsed_time(e1) / iters)
+                tr = _time_candidates({k: partial(call, k) for k in (best, best + "+r")}, iters, rounds)
                 if tr[best + "+r"] < 0.99 * tr[best]:
                     best = best + "+r"
-                _SK_CHOICE[(_m_bucket(M), N, K, int(epi))] = best
+                _SK_CHOICE[key] = best
     finally:
         _GEMM_SK = saved
         del pool
@@ -473,6 +480,18 @@ def norm_stats_buffer(device, n: int = 1) -> torch.Tensor:
     return torch.zeros(n, ref.SS_SHARDS, ref.SS_ROWS, dtype=torch.int64, device=device)
 
 
+def _gemm_out(M: int, ncols: int, out_packed: bool, dtype, device) -> torch.Tensor:
+    """Output buffer of a decode GEMM or attention step of M rows: flat in the packed activation
+    layout (the next GEMM's input), or row-major [M, ncols]."""
+    return torch.empty(packed_numel(M, ncols) if out_packed else (M, ncols), dtype=dtype, device=device)
+
+
+def _epi3_scratch(M: int, N: int, device) -> dict:
+    """``linear*`` arguments of an autotuner's epilogue-3 call: the packed copy and the row statistics."""
+    return dict(ap_out=torch.zeros(packed_numel(M, N), dtype=torch.bfloat16, device=device),
+                ss_out=norm_stats_buffer(device)[0], ss_zero=norm_stats_buffer(device)[0])
+
+
 def rmsnorm(x, w, eps, out=None, residual=None, mode=0, rows=None, packed=False, ss=None, a8=None, a8_scale=None):
     """mode 0: y = norm(x)*w; 1: residual += x, y = norm(residual)*w; 2: residual = x, y = norm(x)*w;
     3: residual = x, y = x, ``ss`` = fixed-point row sums of squares (``norm_stats_buffer``; entry of
@@ -491,8 +510,7 @@ def rmsnorm(x, w, eps, out=None, residual=None, mode=0, rows=None, packed=False,
         return ref.pack_act(y, out=out) if packed else y
     n = rows.numel() if rows is not None else x.shape[0]
     if out is None:
-        out = (torch.empty(packed_numel(n, x.shape[1]), dtype=x.dtype, device=x.device) if packed
-               else torch.empty(n, x.shape[1], dtype=x.dtype, device=x.device))
+        out = _gemm_out(n, x.shape[1], packed, x.dtype, x.device)
     torch.ops.mpamd.rmsnorm(x, residual if residual is not None else x, w, out, float(eps), int(mode), rows,
                             int(bool(packed)), ss, a8, a8_scale)
     return a8 if a8 is not None else out
@@ -543,14 +561,11 @@ def attention_partition(num_queries: int, nkv: int, max_ctx: int, target_wgs: in
     return ps, np_
 
 
-def query_blocks(ntoks, nrep: int):
-    """MFMA attention query blocks for a ragged step: int32 [2, NB] = (first flat token, count).
-
-    A block holds 16 / min(nrep, 16) consecutive tokens of ONE sequence (x the GQA group's
-    heads = 16 MFMA rows).  ``ntoks``: tokens per sequence in flat order."""
+def _token_blocks(ntoks, tb: int):
+    """int32 [2, NB] = (first flat token, count): runs of <= ``tb`` consecutive tokens of ONE
+    sequence.  ``ntoks``: tokens per sequence in flat order."""
     import numpy as np
 
-    tb = 16 // min(max(int(nrep), 1), 16)
     n = np.asarray(ntoks, dtype=np.int64)
     off = np.concatenate([[0], np.cumsum(n)[:-1]]) if n.size else n
     nb = (n + tb - 1) // tb
@@ -559,6 +574,14 @@ def query_blocks(ntoks, nrep: int):
     tok0 = off[seq_of_block] + k * tb
     cnt = np.minimum(tb, n[seq_of_block] - k * tb)
     return np.stack([tok0, cnt]).astype(np.int32)
+
+
+def query_blocks(ntoks, nrep: int):
+    """MFMA attention query blocks for a ragged step: int32 [2, NB] = (first flat token, count).
+
+    A block holds 16 / min(nrep, 16) consecutive tokens of ONE sequence (x the GQA group's
+    heads = 16 MFMA rows).  ``ntoks``: tokens per sequence in flat order."""
+    return _token_blocks(ntoks, 16 // min(max(int(nrep), 1), 16))
 
 
 def query_superblocks(ntoks, nrep: int, group: int = 8):
@@ -598,10 +621,8 @@ def attention_mfma(q, k_cache, v_cache, block_tables, q_seq, q_ctx, qblocks, nh,
         part_size = 128 * math.ceil(math.ceil(max_ctx / num_parts) / 128)
         num_parts = math.ceil(max(max_ctx, 1) / part_size)
     if out is None:
-        out = (torch.empty(packed_numel(T, nh * D), dtype=q.dtype, device=q.device) if packed
-               else torch.empty(T, nh * D, dtype=q.dtype, device=q.device))
-    if workspace is None or (num_parts > 1 and workspace.numel() < T * nh * num_parts * (D + 2)):
-        workspace = attention_workspace(T, nh, D, num_parts, q.device)
+        out = _gemm_out(T, nh * D, packed, q.dtype, q.device)
+    workspace = _attn_workspace(workspace, T, nh, D, num_parts, q.device)
     torch.ops.mpamd.attention_mfma(q, k_cache, v_cache, block_tables, q_seq, q_ctx, qblocks, out, workspace, nh, nkv,
                                    float(scale), int(part_size), int(num_parts), int(bool(packed)), superblocks)
     return out
@@ -614,18 +635,7 @@ FA_WAVES_FORCE = None  # 4 / 8: every prefill step on that workgroup size (A/B r
 def fa_blocks(ntoks, nrep: int, waves: int = None):
     """Workgroup blocks of the FA2 prefill kernel (csrc/attention_fa.hip): int32 [2, NB] =
     (first flat token, count), each <= 32 x waves / nrep consecutive tokens of ONE sequence."""
-    import numpy as np
-
-    waves = int(waves or FA_WAVES)
-    tb = max(1, (32 * waves) // max(int(nrep), 1))
-    n = np.asarray(ntoks, dtype=np.int64)
-    off = np.concatenate([[0], np.cumsum(n)[:-1]]) if n.size else n
-    nb = (n + tb - 1) // tb
-    seq_of_block = np.repeat(np.arange(n.size), nb)
-    k = np.arange(int(nb.sum())) - np.repeat(np.concatenate([[0], np.cumsum(nb)[:-1]]) if nb.size else nb, nb)
-    tok0 = off[seq_of_block] + k * tb
-    cnt = np.minimum(tb, n[seq_of_block] - k * tb)
-    return np.stack([tok0, cnt]).astype(np.int32)
+    return _token_blocks(ntoks, max(1, (32 * int(waves or FA_WAVES)) // max(int(nrep), 1)))
 
 
 def fa_plan(ntoks, nh: int, nkv: int, n_cu: int = 256):
@@ -681,8 +691,7 @@ def attention_fa(q, k_cache, v_cache, block_tables, q_seq, q_ctx, fablocks, nh, 
     num_parts = math.ceil(max(max_ctx, 1) / part_size)
     if out is None:
         out = torch.empty(T, nh * D, dtype=q.dtype, device=q.device)
-    if workspace is None or (num_parts > 1 and workspace.numel() < T * nh * num_parts * (D + 2)):
-        workspace = attention_workspace(T, nh, D, num_parts, q.device)
+    workspace = _attn_workspace(workspace, T, nh, D, num_parts, q.device)
     if pair is None:
         pair = fa_pair(int(fablocks.shape[1]), nh, nkv, num_parts)
     torch.ops.mpamd.attention_fa(q, k_cache, v_cache, block_tables, q_seq, q_ctx, fablocks, out, workspace, nh, nkv,
@@ -716,10 +725,8 @@ def attention_mfma_rope(qkv, k_cache, v_cache, block_tables, q_seq, q_ctx, qbloc
         part_size = 128 * math.ceil(max(max_ctx, 1) / 128)
         num_parts = 1
     if out is None:
-        out = (torch.empty(packed_numel(T, nh * D), dtype=qkv.dtype, device=qkv.device) if packed
-               else torch.empty(T, nh * D, dtype=qkv.dtype, device=qkv.device))
-    if workspace is None or (num_parts > 1 and workspace.numel() < T * nh * num_parts * (D + 2)):
-        workspace = attention_workspace(T, nh, D, num_parts, qkv.device)
+        out = _gemm_out(T, nh * D, packed, qkv.dtype, qkv.device)
+    workspace = _attn_workspace(workspace, T, nh, D, num_parts, qkv.device)
     torch.ops.mpamd.attention_mfma_rope(qkv, k_cache, v_cache, block_tables, q_seq, q_ctx, qblocks, positions, cos,
                                         sin, slots, out, workspace, nh, nkv, float(scale), int(part_size),
                                         int(num_parts), int(bool(packed)), *_qkv_part_args(qkv_part),
@@ -735,8 +742,7 @@ def attention_counters(device) -> torch.Tensor:
     combine (csrc/attention.hip split_combine): one per (query, head group) of a step; the
     last-arriving slice re-zeroes its counter.  Steps with more (query, group) pairs than this
     holds fall back to the separate reduce launch.  Call before a hipGraph capture."""
-    device = torch.device(device)
-    key = (device.type, device.index if device.index is not None else torch.cuda.current_device())
+    key = _dev_key(device)
     c = _ATTN_CNT.get(key)
     if c is None:
         c = _ATTN_CNT[key] = torch.zeros(1 << 16, dtype=torch.int32, device=device)
@@ -759,6 +765,13 @@ def attention_workspace(num_queries: int, nh: int, head_dim: int, num_parts: int
     return torch.empty(max(1, num_queries * nh * num_parts * (head_dim + 2)), dtype=torch.float32, device=device)
 
 
+def _attn_workspace(workspace, num_queries: int, nh: int, head_dim: int, num_parts: int, device) -> torch.Tensor:
+    """The caller's split-K workspace, or a new one if it has none or one too small for ``num_parts``."""
+    if workspace is None or (num_parts > 1 and workspace.numel() < num_queries * nh * num_parts * (head_dim + 2)):
+        return attention_workspace(num_queries, nh, head_dim, num_parts, device)
+    return workspace
+
+
 def paged_attention(q, k_cache, v_cache, block_tables, q_seq, q_ctx, nh, nkv, scale, out=None, workspace=None,
                     part_size=None, num_parts=None, max_ctx=None, packed=False):
     if not _native(q):
@@ -772,8 +785,7 @@ def paged_attention(q, k_cache, v_cache, block_tables, q_seq, q_ctx, nh, nkv, sc
             max_ctx = int(q_ctx.max().item()) if T else 1
         part_size, num_parts = attention_partition(T, nkv, max_ctx)
     if out is None:
-        out = (torch.empty(packed_numel(T, nh * D), dtype=q.dtype, device=q.device) if packed
-               else torch.empty(T, nh * D, dtype=q.dtype, device=q.device))
+        out = _gemm_out(T, nh * D, packed, q.dtype, q.device)
     if workspace is None:
         workspace = attention_workspace(T, nh, D, num_parts, q.device)
     torch.ops.mpamd.paged_attention(q, k_cache, v_cache, block_tables, q_seq, q_ctx, out, workspace, int(nh), int(nkv),
@@ -827,8 +839,7 @@ def paged_attention_rope(qkv, k_cache, v_cache, block_tables, q_seq, q_ctx, posi
             max_ctx = int(q_ctx.max().item()) if T else 1
         part_size, num_parts = attention_partition(T, nkv, max_ctx)
     if out is None:
-        out = (torch.empty(packed_numel(T, nh * D), dtype=qkv.dtype, device=qkv.device) if packed
-               else torch.empty(T, nh * D, dtype=qkv.dtype, device=qkv.device))
+        out = _gemm_out(T, nh * D, packed, qkv.dtype, qkv.device)
     if workspace is None:
         workspace = attention_workspace(T, nh, D, num_parts, qkv.device)
     torch.ops.mpamd.paged_attention_rope(qkv, k_cache, v_cache, block_tables, q_seq, q_ctx, positions, cos, sin,
@@ -997,8 +1008,7 @@ def linear(x, w, out=None, epilogue=0, residual=None, policy=None, wp=None, a_ro
         if a_rows is None:  # row-major caller: pack x into the fragment layout first
             x = pack_act(x)
         if out is None:
-            out = (torch.empty(packed_numel(M, ncols), dtype=x.dtype, device=x.device) if out_packed
-                   else torch.empty(M, ncols, dtype=x.dtype, device=x.device))
+            out = _gemm_out(M, ncols, out_packed, x.dtype, x.device)
         if gate is not None:
             kern = "pk"
         elif M > 64 and t2d_rows(M) and t2d_ok(M, N, K, epilogue, out_packed):
@@ -1089,7 +1099,6 @@ def autotune_qkv_fold(N: int, K: int, device, fp8: bool = False, ms=(16, 32, 48,
     """Per M bucket: the qkv GEMM as partial slabs (no reduce launch) vs the kernel the GEMM
     autotuner chose for the full projection; the fold is kept where it wins by > 3 %.  Weights
     rotated over ~1 GiB of copies, as in ``autotune_gemm``."""
-    global _W8_MODE
     device = torch.device(device)
     if device.type != "cuda" or os.environ.get("MPAMD_QKV_FOLD", "1") == "0":
         return {}
@@ -1123,18 +1132,7 @@ def autotune_qkv_fold(N: int, K: int, device, fp8: bool = False, ms=(16, 32, 48,
             else:
                 linear_partials(xp, M, wp=ws[i % copies], out=y)
 
-        t = {"full": float("inf"), "part": float("inf")}
-        for _ in range(rounds):
-            for name, fn in (("full", full), ("part", part)):
-                for i in range(2):
-                    fn(i)
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                for i in range(iters):
-                    fn(i)
-                e1.record()
-                e1.synchronize()
-                t[name] = min(t[name], e0.elapsed_time(e1) / iters)
+        t = _time_candidates({"full": full, "part": part}, iters, rounds)
         _QKV_FOLD_CAND[key] = t["part"] < 0.97 * t["full"]
     del ws
     return dict(_QKV_FOLD_CAND)
@@ -1226,8 +1224,7 @@ def autotune_fp8(shapes, device, ms=(32, 48, 64), iters: int = 12, rounds: int =
     saved = _FP8_MODE
     try:
         for (N, K, epi) in shapes:
-            keys = _todo(_FP8_CHOICE, list(dict.fromkeys((_m_bucket(M), N, K, int(epi)) for M in ms)))
-            todo = [M for M in dict((_m_bucket(M), M) for M in ms).values() if (_m_bucket(M), N, K, int(epi)) in keys]
+            todo = _todo_rows(_FP8_CHOICE, N, K, epi, ms)
             if not todo:
                 continue
             copies = max(1, min(8, (1 << 30) // (N * K)))
@@ -1239,19 +1236,13 @@ def autotune_fp8(shapes, device, ms=(32, 48, 64), iters: int = 12, rounds: int =
                 a8 = torch.randint(0, 0x77, (packed_numel(M, K),), dtype=torch.uint8, device=device)
                 asc = torch.ones(((M + 15) // 16) * 16, dtype=torch.float32, device=device)
                 out = torch.empty(M, ncols, dtype=torch.bfloat16, device=device)
-                t = {k: float("inf") for k in _FP8_KERNELS}
-                for _ in range(rounds):
-                    for name in _FP8_KERNELS:
-                        _FP8_MODE = name
-                        for i in range(2):
-                            linear_fp8(a8, asc, wqs[i % copies], wsc, M, out=out, epilogue=epi)
-                        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                        e0.record()
-                        for i in range(iters):
-                            linear_fp8(a8, asc, wqs[i % copies], wsc, M, out=out, epilogue=epi)
-                        e1.record()
-                        e1.synchronize()
-                        t[name] = min(t[name], e0.elapsed_time(e1) / iters)
+
+                def call(name, i):
+                    global _FP8_MODE
+                    _FP8_MODE = name
+                    linear_fp8(a8, asc, wqs[i % copies], wsc, M, out=out, epilogue=epi)
+
+                t = _time_candidates({k: partial(call, k) for k in _FP8_KERNELS}, iters, rounds)
                 _FP8_CHOICE[(_m_bucket(M), N, K, int(epi))] = min(t, key=t.get)
             del wqs
     finally:
@@ -1273,8 +1264,7 @@ def linear_fp8(a8, a_scale, wq, w_scale, M: int, out=None, epilogue: int = 0, re
             return out
         return y
     if out is None:
-        out = (torch.empty(packed_numel(M, ncols), dtype=torch.bfloat16, device=a8.device) if out_packed
-               else torch.empty(M, ncols, dtype=torch.bfloat16, device=a8.device))
+        out = _gemm_out(M, ncols, out_packed, torch.bfloat16, a8.device)
     kind = _fp8_kind(M, N, 64 * wq.shape[1], epilogue)
     torch.ops.mpamd.gemm_fp8(a8, a_scale, wq, w_scale, out, residual, int(epilogue), int(M), int(bool(out_packed)),
                              kind, gemm_workspace(a8.device) if kind == 2 else None)
@@ -1327,8 +1317,7 @@ def linear_w8(x, w8, w_scale, a_rows: int, out=None, epilogue: int = 0, residual
             ap_out=ap_out, ss_out=ss_out, ss_zero=ss_zero)
     ncols = N // 2 if epilogue == 1 else N
     if out is None:
-        out = (torch.empty(packed_numel(M, ncols), dtype=x.dtype, device=x.device) if out_packed
-               else torch.empty(M, ncols, dtype=x.dtype, device=x.device))
+        out = _gemm_out(M, ncols, out_packed, x.dtype, x.device)
     kern = _w8_kernel(M, N, K, epilogue)
     flags = 1 | (2 if out_packed else 0) | _W8_KERNELS[_base(kern)] | (ROT_FLAG if kern.endswith("+r") else 0)
     torch.ops.mpamd.gemm_w8(x, w8, w_scale, out, residual, int(epilogue), M, flags,
@@ -1388,8 +1377,7 @@ def linear_w4(x, w4, s4, a_rows: int, out=None, epilogue: int = 0, residual=None
             ap_out=ap_out, ss_out=ss_out, ss_zero=ss_zero)
     ncols = N // 2 if epilogue == 1 else N
     if out is None:
-        out = (torch.empty(packed_numel(M, ncols), dtype=x.dtype, device=x.device) if out_packed
-               else torch.empty(M, ncols, dtype=x.dtype, device=x.device))
+        out = _gemm_out(M, ncols, out_packed, x.dtype, x.device)
     torch.ops.mpamd.gemm_w4(x, w4, s4, out, residual, int(epilogue), M, 1 | (2 if out_packed else 0), ap_out, ss_out,
                             ss_zero, ss_in, 1.0 / K, float(eps))
     return out
@@ -1457,8 +1445,7 @@ def autotune_w8(shapes, device, ms=(4, 16, 32, 48, 64), iters: int = 12, rounds:
     saved = _W8_MODE
     try:
         for (N, K, epi) in shapes:
-            keys = _todo(_W8_CHOICE, list(dict.fromkeys((_m_bucket(M), N, K, int(epi)) for M in ms)))
-            todo = [M for M in dict((_m_bucket(M), M) for M in ms).values() if (_m_bucket(M), N, K, int(epi)) in keys]
+            todo = _todo_rows(_W8_CHOICE, N, K, epi, ms)
             if not todo:
                 continue
             # the ring form only (SwiGLU / narrow N) or all three, each also with the rotated k walk
@@ -1471,29 +1458,16 @@ def autotune_w8(shapes, device, ms=(4, 16, 32, 48, 64), iters: int = 12, rounds:
             for M in todo:
                 xp = pack_act(torch.randn(M, K, device=device).to(torch.bfloat16))
                 res = torch.zeros(M, N, dtype=torch.bfloat16, device=device) if epi == 3 else None
-                extra = {}
-                if epi == 3:
-                    extra = dict(ap_out=torch.zeros(packed_numel(M, N), dtype=torch.bfloat16, device=device),
-                                 ss_out=norm_stats_buffer(device)[0], ss_zero=norm_stats_buffer(device)[0])
-                ncols = N // 2 if epi == 1 else N
-                out = res if epi == 3 else (
-                    torch.empty(packed_numel(M, ncols), dtype=torch.bfloat16, device=device) if epi == 1
-                    else torch.empty(M, N, dtype=torch.bfloat16, device=device))
-                t = {k: float("inf") for k in names}
-                for _ in range(rounds):
-                    for name in names:
-                        _W8_MODE = name
-                        for i in range(2):
-                            linear_w8(xp, wqs[i % copies], wsc, M, out=out, epilogue=epi, residual=res,
-                                      out_packed=epi == 1, **extra)
-                        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                        e0.record()
-                        for i in range(iters):
-                            linear_w8(xp, wqs[i % copies], wsc, M, out=out, epilogue=epi, residual=res,
-                                      out_packed=epi == 1, **extra)
-                        e1.record()
-                        e1.synchronize()
-                        t[name] = min(t[name], e0.elapsed_time(e1) / iters)
+                extra = _epi3_scratch(M, N, device) if epi == 3 else {}
+                out = res if epi == 3 else _gemm_out(M, N // 2 if epi == 1 else N, epi == 1, torch.bfloat16, device)
+
+                def call(name, i):
+                    global _W8_MODE
+                    _W8_MODE = name
+                    linear_w8(xp, wqs[i % copies], wsc, M, out=out, epilogue=epi, residual=res,
+                              out_packed=epi == 1, **extra)
+
+                t = _time_candidates({k: partial(call, k) for k in names}, iters, rounds)
                 # the best plain form, rotated unless the rotation measures > 1 % slower: isolated
                 # timings under-rank it (Llama-3-70B fp8 64 sessions, all forms rotated: 17.47 ->
                 # 17.23 ms; the isolated choice had kept three of four shapes plain, profiles/r3_70)

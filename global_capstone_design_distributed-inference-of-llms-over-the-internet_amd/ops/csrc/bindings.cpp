@@ -8,6 +8,7 @@
 #include <torch/library.h>
 
 #include <cmath>
+#include <utility>
 
 extern "C" {
 int mp_rmsnorm(const void* x, int64_t x_stride, void* res, int64_t res_stride, const void* w, void* y,
@@ -48,7 +49,6 @@ int mp_quant_act_fp8(const void* ap, void* a8, float* scale, float* part, int M,
 int mp_gemm_fp8(const void* a8, const float* as, const void* wq, const float* ws, void* y, int64_t ys, const void* res,
                 int64_t rs, int M, int N, int K, int epilogue, int out_packed, int kind, float* part,
                 int64_t part_bytes, hipStream_t stream);
-int64_t mp_gemm_slab_offset();
 int64_t mp_gemm_slab_bytes();
 void mp_fp8_set_kernel(int kind);
 int mp_gemm_rw_ok(int M, int N, int K, int epilogue, int out_packed);
@@ -105,6 +105,54 @@ inline void* opt_ss(const c10::optional<at::Tensor>& t, const char* name) {
   MP_CHECK(t->is_cuda() && t->scalar_type() == at::kLong && t->is_contiguous() && t->numel() >= mp_gemm_ss_elems(),
            std::string(name) + ": int64 cuda contiguous [32, 256] (ops.norm_stats_buffer)");
   return t->data_ptr();
+}
+
+// fp8 weight of the W8A16 / W8A8-MX decode GEMMs and its per-column scales -> (N, K)
+inline std::pair<int, int> check_w8_weight(const at::Tensor& wq, const at::Tensor& wsc) {
+  MP_CHECK(wq.is_cuda() && wq.scalar_type() == at::kByte && wq.dim() == 4 && wq.size(2) == 64 && wq.size(3) == 8 &&
+               wq.is_contiguous(),
+           "wq must be an fp8 weight uint8 [N/16, K/32, 64, 8] (ops.pack_weight_w8)");
+  const int N = 16 * wq.size(0), K = 32 * wq.size(1);
+  MP_CHECK(wsc.is_cuda() && wsc.scalar_type() == at::kFloat && wsc.is_contiguous() && wsc.numel() == N,
+           "wsc: fp32 [N] column scales");
+  return {N, K};
+}
+
+// decode-GEMM output of M rows: packed (SwiGLU only) or row-major; SwiGLU halves the N columns
+inline void check_gemm_out(const at::Tensor& y, int64_t M, int64_t N, int64_t epilogue, bool opk) {
+  const int64_t ncols = epilogue == 1 ? N / 2 : N;
+  if (opk) {
+    MP_CHECK(epilogue == 1 && y.is_contiguous() && y.numel() >= packed_numel(M, ncols), "packed y");
+  } else {
+    check_rows(y, "y");
+    MP_CHECK(y.size(0) == M && y.size(1) == ncols, "y shape");
+  }
+}
+
+// optional row-major bf16 [M, N] operand -> (pointer, row stride); (nullptr, 0) when absent
+inline std::pair<const void*, int64_t> opt_rows(const c10::optional<at::Tensor>& t, const char* name, int64_t M,
+                                                int64_t N) {
+  if (!t.has_value()) return {nullptr, 0};
+  check_bf16_cuda(*t, name);
+  check_rows(*t, name);
+  MP_CHECK(t->size(0) == M && t->size(1) == N, std::string(name) + " shape");
+  return {t->data_ptr(), t->stride(0)};
+}
+
+// optional packed bf16 copy of the [M, N] output (epilogue 3's ``ap``)
+inline void* opt_packed(const c10::optional<at::Tensor>& ap, int64_t M, int64_t N) {
+  if (!ap.has_value()) return nullptr;
+  check_bf16_cuda(*ap, "ap");
+  MP_CHECK(ap->is_contiguous() && ap->numel() >= packed_numel(M, N), "ap: packed [ceil(M/16)*16*N]");
+  return ap->data_ptr();
+}
+
+// optional GEMM workspace (ops.gemm_workspace)
+inline void* opt_workspace(const c10::optional<at::Tensor>& ws) {
+  if (!ws.has_value()) return nullptr;
+  MP_CHECK(ws->is_cuda() && ws->is_contiguous() && ws->numel() * ws->element_size() >= mp_gemm_workspace_bytes(),
+           "gemm workspace too small (ops.gemm_workspace)");
+  return ws->data_ptr();
 }
 
 void rmsnorm(const at::Tensor& x, at::Tensor& residual, const at::Tensor& w, at::Tensor& y, double eps, int64_t mode,
@@ -533,41 +581,16 @@ void gemm(const at::Tensor& x, const at::Tensor& wp, at::Tensor& y, const c10::o
     M = x.size(0);
     MP_CHECK(x.size(1) == K, "K mismatch between x and packed weight");
   }
-  const int ncols = epilogue == 1 ? N / 2 : N;
-  if (opk) {
-    MP_CHECK(epilogue == 1 && y.is_contiguous() && y.numel() >= packed_numel(M, ncols), "packed y");
-  } else {
-    check_rows(y, "y");
-    MP_CHECK(y.size(0) == M && y.size(1) == ncols, "y shape");
-  }
-  const void* rp = nullptr;
-  int64_t rs = 0;
-  if (residual.has_value()) {
-    check_bf16_cuda(*residual, "residual");
-    check_rows(*residual, "residual");
-    MP_CHECK(residual->size(0) == M && residual->size(1) == N, "residual shape");
-    rp = residual->data_ptr();
-    rs = residual->stride(0);
-  }
+  check_gemm_out(y, M, N, epilogue, opk);
+  const auto [rp, rs] = opt_rows(residual, "residual", M, N);
   MP_CHECK(epilogue < 2 || rp != nullptr, "residual epilogue needs residual");
   MP_CHECK(epilogue >= 0 && epilogue <= 3, "epilogue");
-  void* app = nullptr;
-  if (ap.has_value()) {
-    check_bf16_cuda(*ap, "ap");
-    MP_CHECK(ap->is_contiguous() && ap->numel() >= packed_numel(M, N), "ap: packed [ceil(M/16)*16*N]");
-    app = ap->data_ptr();
-  }
+  void* app = opt_packed(ap, M, N);
   void* sso = opt_ss(ss_out, "ss_out");
   void* ssz = opt_ss(ss_zero, "ss_zero");
   const void* ssi = opt_ss(ss_in, "ss_in");
   MP_CHECK(epilogue != 3 || (app != nullptr && !opk), "epilogue 3 needs ap (and ss_out outside ablations)");
-  void* ws = nullptr;
-  if (workspace.has_value()) {
-    MP_CHECK(workspace->is_cuda() && workspace->is_contiguous() &&
-                 workspace->numel() * workspace->element_size() >= mp_gemm_workspace_bytes(),
-             "gemm workspace too small (ops.gemm_workspace)");
-    ws = workspace->data_ptr();
-  }
+  void* ws = opt_workspace(workspace);
   const int* gp = nullptr;
   if (gate.has_value()) {  // MoE expert gate: one int32 on the device (0 -> the GEMM is skipped)
     MP_CHECK(gate->is_cuda() && gate->scalar_type() == at::kInt && gate->numel() == 1, "gate must be one cuda int32");
@@ -606,47 +629,17 @@ void gemm_w8(const at::Tensor& x, const at::Tensor& wq, const at::Tensor& wsc, a
              const c10::optional<at::Tensor>& ss_in, double inv_k, double eps) {
   check_bf16_cuda(x, "x");
   check_bf16_cuda(y, "y");
-  MP_CHECK(wq.is_cuda() && wq.scalar_type() == at::kByte && wq.dim() == 4 && wq.size(2) == 64 && wq.size(3) == 8 &&
-               wq.is_contiguous(),
-           "wq must be an fp8 weight uint8 [N/16, K/32, 64, 8] (ops.pack_weight_w8)");
-  const int N = 16 * wq.size(0), K = 32 * wq.size(1);
-  MP_CHECK(wsc.is_cuda() && wsc.scalar_type() == at::kFloat && wsc.is_contiguous() && wsc.numel() == N,
-           "wsc: fp32 [N] column scales");
+  const auto [N, K] = check_w8_weight(wq, wsc);
   const int M = (int)M_;
   const bool opk = flags & 2;
   MP_CHECK(M >= 0 && M <= 64, "gemm_w8: 0 <= M <= 64");
   MP_CHECK(x.is_contiguous() && x.numel() >= packed_numel(M, K), "packed x too small");
-  const int ncols = epilogue == 1 ? N / 2 : N;
-  if (opk) {
-    MP_CHECK(epilogue == 1 && y.is_contiguous() && y.numel() >= packed_numel(M, ncols), "packed y");
-  } else {
-    check_rows(y, "y");
-    MP_CHECK(y.size(0) == M && y.size(1) == ncols, "y shape");
-  }
+  check_gemm_out(y, M, N, epilogue, opk);
   MP_CHECK(epilogue == 0 || epilogue == 3 || (epilogue == 1 && opk), "gemm_w8: epilogue 0, 3 or packed SwiGLU");
-  const void* rp = nullptr;
-  int64_t rs = 0;
-  if (residual.has_value()) {
-    check_bf16_cuda(*residual, "residual");
-    check_rows(*residual, "residual");
-    MP_CHECK(residual->size(0) == M && residual->size(1) == N, "residual shape");
-    rp = residual->data_ptr();
-    rs = residual->stride(0);
-  }
-  void* app = nullptr;
-  if (ap.has_value()) {
-    check_bf16_cuda(*ap, "ap");
-    MP_CHECK(ap->is_contiguous() && ap->numel() >= packed_numel(M, N), "ap: packed [ceil(M/16)*16*N]");
-    app = ap->data_ptr();
-  }
+  const auto [rp, rs] = opt_rows(residual, "residual", M, N);
+  void* app = opt_packed(ap, M, N);
   MP_CHECK(epilogue != 3 || (app != nullptr && rp != nullptr), "epilogue 3 needs residual and ap");
-  void* ws = nullptr;
-  if (workspace.has_value()) {
-    MP_CHECK(workspace->is_cuda() && workspace->is_contiguous() &&
-                 workspace->numel() * workspace->element_size() >= mp_gemm_workspace_bytes(),
-             "gemm workspace too small (ops.gemm_workspace)");
-    ws = workspace->data_ptr();
-  }
+  void* ws = opt_workspace(workspace);
   const int rc = mp_gemm_w8(x.data_ptr(), wq.data_ptr(), wsc.data_ptr<float>(), y.data_ptr(), opk ? 0 : y.stride(0),
                             rp, rs, M, N, K, (int)epilogue, (int)flags, ws, app, opt_ss(ss_out, "ss_out"),
                             opt_ss(ss_zero, "ss_zero"), opt_ss(ss_in, "ss_in"), (float)inv_k, (float)eps, cur_stream());
@@ -683,28 +676,9 @@ void gemm_w4(const at::Tensor& x, const at::Tensor& w4, const at::Tensor& s4, at
   MP_CHECK(x.is_contiguous() && x.numel() >= packed_numel(M, K), "packed x too small");
   MP_CHECK(epilogue == 0 || epilogue == 3 || (epilogue == 1 && opk), "gemm_w4: epilogue 0, 3 or packed SwiGLU");
   MP_CHECK(epilogue != 1 || N % 32 == 0, "gemm_w4: SwiGLU needs N % 32 == 0");
-  const int ncols = epilogue == 1 ? N / 2 : N;
-  if (opk) {
-    MP_CHECK(epilogue == 1 && y.is_contiguous() && y.numel() >= packed_numel(M, ncols), "packed y");
-  } else {
-    check_rows(y, "y");
-    MP_CHECK(y.size(0) == M && y.size(1) == ncols, "y shape");
-  }
-  const void* rp = nullptr;
-  int64_t rs = 0;
-  if (residual.has_value()) {
-    check_bf16_cuda(*residual, "residual");
-    check_rows(*residual, "residual");
-    MP_CHECK(residual->size(0) == M && residual->size(1) == N, "residual shape");
-    rp = residual->data_ptr();
-    rs = residual->stride(0);
-  }
-  void* app = nullptr;
-  if (ap.has_value()) {
-    check_bf16_cuda(*ap, "ap");
-    MP_CHECK(ap->is_contiguous() && ap->numel() >= packed_numel(M, N), "ap: packed [ceil(M/16)*16*N]");
-    app = ap->data_ptr();
-  }
+  check_gemm_out(y, M, N, epilogue, opk);
+  const auto [rp, rs] = opt_rows(residual, "residual", M, N);
+  void* app = opt_packed(ap, M, N);
   MP_CHECK(epilogue != 3 || (app != nullptr && rp != nullptr), "epilogue 3 needs residual and ap");
   const int rc = mp_gemm_w4(x.data_ptr(), w4.data_ptr(), s4.data_ptr(), y.data_ptr(), opk ? 0 : y.stride(0), rp, rs, M,
                             N, K, (int)epilogue, (int)flags, app, opt_ss(ss_out, "ss_out"), opt_ss(ss_zero, "ss_zero"),
@@ -778,46 +752,25 @@ void gemm_mx(const at::Tensor& ax, const at::Tensor& as, const at::Tensor& wq, c
              const at::Tensor& workspace, const c10::optional<at::Tensor>& ap,
              const c10::optional<at::Tensor>& ss_out, const c10::optional<at::Tensor>& ss_zero,
              const c10::optional<at::Tensor>& ss_in, double inv_k, double eps) {
-  MP_CHECK(wq.is_cuda() && wq.scalar_type() == at::kByte && wq.dim() == 4 && wq.size(2) == 64 && wq.size(3) == 8 &&
-               wq.is_contiguous(),
-           "wq must be an fp8 weight uint8 [N/16, K/32, 64, 8] (ops.pack_weight_w8)");
-  const int N = 16 * wq.size(0), K = 32 * wq.size(1);
+  const auto [N, K] = check_w8_weight(wq, wsc);
   const int M = (int)M_;
   MP_CHECK(M >= 1 && M <= 64 && K % 128 == 0, "gemm_mx: 1 <= M <= 64, K % 128 == 0");
   const int64_t rows = ((M + 15) / 16) * 16;
   MP_CHECK(ax.is_cuda() && ax.scalar_type() == at::kByte && ax.is_contiguous() && ax.numel() >= rows * K, "ax size");
   MP_CHECK(as.is_cuda() && as.scalar_type() == at::kByte && as.is_contiguous() && as.numel() >= 2 * K, "as size");
-  MP_CHECK(wsc.is_cuda() && wsc.scalar_type() == at::kFloat && wsc.is_contiguous() && wsc.numel() == N,
-           "wsc: fp32 [N] column scales");
   MP_CHECK(epilogue == 0 || epilogue == 3, "gemm_mx: epilogue 0 or 3");
   const bool partial = flags & 16384;
   if (!partial) {
     check_bf16_cuda(y, "y");
-    check_rows(y, "y");
-    MP_CHECK(y.size(0) == M && y.size(1) == N, "y shape");
+    check_gemm_out(y, M, N, epilogue, false);
   }
-  const void* rp = nullptr;
-  int64_t rs = 0;
-  if (residual.has_value()) {
-    check_bf16_cuda(*residual, "residual");
-    check_rows(*residual, "residual");
-    MP_CHECK(residual->size(0) == M && residual->size(1) == N, "residual shape");
-    rp = residual->data_ptr();
-    rs = residual->stride(0);
-  }
-  void* app = nullptr;
-  if (ap.has_value()) {
-    check_bf16_cuda(*ap, "ap");
-    MP_CHECK(ap->is_contiguous() && ap->numel() >= packed_numel(M, N), "ap: packed [ceil(M/16)*16*N]");
-    app = ap->data_ptr();
-  }
+  const auto [rp, rs] = opt_rows(residual, "residual", M, N);
+  void* app = opt_packed(ap, M, N);
   MP_CHECK(epilogue != 3 || (app != nullptr && rp != nullptr), "epilogue 3 needs residual and ap");
-  MP_CHECK(workspace.is_cuda() && workspace.is_contiguous() &&
-               workspace.numel() * workspace.element_size() >= mp_gemm_workspace_bytes(),
-           "gemm workspace too small (ops.gemm_workspace)");
+  void* ws = opt_workspace(workspace);
   const int rc = mp_gemm_mx(ax.data_ptr(), as.data_ptr(), wq.data_ptr(), wsc.data_ptr<float>(),
                             partial ? nullptr : y.data_ptr(), partial ? 0 : y.stride(0), rp, rs, M, N, K,
-                            (int)epilogue, (int)flags, workspace.data_ptr(), app, opt_ss(ss_out, "ss_out"),
+                            (int)epilogue, (int)flags, ws, app, opt_ss(ss_out, "ss_out"),
                             opt_ss(ss_zero, "ss_zero"), opt_ss(ss_in, "ss_in"), (float)inv_k, (float)eps, cur_stream());
   TORCH_CHECK(rc != 1, "mpamd: gemm_mx: no split-K geometry for M=", M, " N=", N, " K=", K);
   check_launch(rc, "gemm_mx");
@@ -849,13 +802,7 @@ void gemm_fp8(const at::Tensor& a8, const at::Tensor& as, const at::Tensor& wq, 
   MP_CHECK(as.is_cuda() && as.scalar_type() == at::kFloat && as.numel() >= M, "as");
   MP_CHECK(ws.is_cuda() && ws.scalar_type() == at::kFloat && ws.numel() == N, "ws: fp32 [N]");
   check_bf16_cuda(y, "y");
-  const int ncols = epilogue == 1 ? N / 2 : N;
-  if (out_packed) {
-    MP_CHECK(epilogue == 1 && y.is_contiguous() && y.numel() >= packed_numel(M, ncols), "packed y");
-  } else {
-    check_rows(y, "y");
-    MP_CHECK(y.size(0) == M && y.size(1) == ncols, "y shape");
-  }
+  check_gemm_out(y, M, N, epilogue, out_packed);
   const void* rp = nullptr;
   int64_t rs = 0;
   if (residual.has_value()) {

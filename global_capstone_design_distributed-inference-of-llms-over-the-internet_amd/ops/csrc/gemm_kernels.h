@@ -1783,7 +1783,7 @@ static int launch_gemm_rwk(const void* x, const void* w, void* y, int64_t ys, co
   int* tick = (int*)ws + SK_MAX_GROUPS / 2;  // rwk arrival tickets (the stream-K kernel uses the low half)
   if (inl && MT <= 4 && nt >= 2 && tiles / nt <= SK_MAX_GROUPS / 8 - 1 &&
       (int64_t)tiles * MT * S * 1024 <= RWK_SLAB_BYTES) {
-    if constexpr (MT <= 4) {
+    if constexpr (MT <= 4 && !MX) {  // the MX form has no in-launch combine (inl is false there)
 #define MP_RWKI(NT_, E_)                                                                                       \
   hipLaunchKernelGGL((gemm_rwk_kernel<MT, NT_, F8, E_>), g1, dim3(RW_WAVES * 64), 0, stream, (const bf16_t*)x,    \
                      (const bf16_t*)w, part, M, N, K, S, ep, (bf16_t*)y, ys, (const bf16_t*)res, rs, tick)

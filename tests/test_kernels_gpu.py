@@ -1,6 +1,7 @@
 """Numerics of every gfx950 HIP kernel against a plain-PyTorch fp32 reference of the same op."""
 import math
 
+import numpy as np
 import pytest
 import torch
 
@@ -663,6 +664,8 @@ def test_fa_blocks():
     assert ops.fa_blocks([5, 1, 300], 1, 4).tolist() == [[0, 5, 6, 134, 262], [5, 1, 128, 128, 44]]
     assert ops.fa_blocks([40], 4, 4).tolist() == [[0, 32], [32, 8]]
     assert ops.fa_blocks([40], 8, 8).tolist() == [[0, 32], [32, 8]]
+    fb = ops.fa_blocks([], 4, 4)  # an empty step: no blocks, still [2, 0] int32
+    assert fb.shape == (2, 0) and fb.dtype == np.int32
 
 
 def test_query_superblocks():
@@ -677,6 +680,8 @@ def test_query_blocks():
     assert qb.tolist() == [[0, 5, 6, 22], [5, 1, 16, 1]]
     qb = ops.query_blocks([5, 1], 8)  # 2 tokens x 8 heads per block
     assert qb.tolist() == [[0, 2, 4, 5], [2, 2, 1, 1]]
+    qb = ops.query_blocks([], 8)  # an empty step: no blocks, still [2, 0] int32
+    assert qb.shape == (2, 0) and qb.dtype == np.int32
 
 
 @pytest.mark.parametrize("nh,nkv,D", [(32, 32, 128), (32, 8, 128), (12, 12, 64)])
