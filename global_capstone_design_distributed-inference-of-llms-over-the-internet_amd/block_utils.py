@@ -63,14 +63,16 @@ def default_attn_cache_tokens(cfg: ModelConfig) -> int:
     return 16384 if cfg.num_key_value_heads < cfg.num_attention_heads else 4096
 
 
-def kv_cache_bytes_per_block(cfg: ModelConfig, tokens: Optional[int] = None, dtype=torch.bfloat16) -> int:
+def kv_cache_bytes_per_block(cfg: ModelConfig, tokens: Optional[int] = None, dtype=torch.bfloat16,
+                             kv_cache_dtype: str = "bf16") -> int:
     tokens = default_attn_cache_tokens(cfg) if tokens is None else int(tokens)
-    return tokens * cfg.kv_bytes_per_token_per_layer(_DTYPE_BYTES[resolve_block_dtype(cfg, dtype)])
+    return tokens * cfg.kv_bytes_per_token_per_layer(_DTYPE_BYTES[resolve_block_dtype(cfg, dtype)], kv_cache_dtype)
 
 
 def auto_num_blocks(cfg: ModelConfig, free_bytes: Optional[int] = None, dtype=torch.bfloat16,
                     quant_type: Optional[str] = None, attn_cache_tokens: Optional[int] = None,
-                    reserve_bytes: int = 2 << 30, device=None, total_blocks: Optional[int] = None) -> int:
+                    reserve_bytes: int = 2 << 30, device=None, total_blocks: Optional[int] = None,
+                    kv_cache_dtype: str = "bf16") -> int:
     """How many blocks this GPU can serve: floor((free - reserve) / (block + KV per block)).
 
     ``free_bytes`` defaults to the device's free memory (``torch.cuda.mem_get_info``); on a
@@ -81,7 +83,7 @@ def auto_num_blocks(cfg: ModelConfig, free_bytes: Optional[int] = None, dtype=to
             raise ValueError("free_bytes is required off-GPU")
         free_bytes = torch.cuda.mem_get_info(torch.device(device))[0]
     per_block = get_block_size(cfg, "memory", dtype, quant_type) + kv_cache_bytes_per_block(cfg, attn_cache_tokens,
-                                                                                           dtype)
+                                                                                           dtype, kv_cache_dtype)
     n = int((int(free_bytes) - int(reserve_bytes)) // per_block)
     total = cfg.num_hidden_layers if total_blocks is None else int(total_blocks)
     return max(1, min(n, total))

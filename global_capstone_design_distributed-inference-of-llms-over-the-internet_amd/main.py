@@ -81,6 +81,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--quant_type", default="none", choices=list(QUANT_CHOICES),
                    help="stage servers: stored weight format of the blocks (mxfp4 = OCP MXFP4, 4.25 bits per "
                         "weight; fp8 = OCP e4m3; upstream's nf4 / int8 map to mxfp4 / fp8)")
+    p.add_argument("--kv_cache_dtype", default="bf16", choices=["bf16", "fp8"],
+                   help="stage servers: KV cache format (fp8 = OCP e4m3 pages + one e8m0 scale byte per token and "
+                        "kv head: (head_dim + 1) bytes per token-head instead of 2 x head_dim)")
     p.add_argument("--use_cpu_offload", action="store_true")
     p.add_argument("--keep_layers_on_gpu", type=int, default=0)
     p.add_argument("--use_load_balancing", action="store_true")
@@ -157,6 +160,8 @@ def _peers(s: str) -> List[str]:
 
 def _executor_kwargs(args) -> dict:
     kw = dict(max_sessions=args.max_sessions)
+    if getattr(args, "kv_cache_dtype", "bf16") != "bf16":
+        kw["kv_cache_dtype"] = args.kv_cache_dtype
     if args.kv_cache_gb is not None:
         kw["kv_cache_bytes"] = int(args.kv_cache_gb * (1 << 30))
     if args.max_seq_len is not None:
@@ -532,7 +537,8 @@ class _Server:
         a, ex = self.args, self.ex
         exp = get_dht_time() + a.ttl
         extra = dict(start_block=ex.start, end_block=ex.end, final_stage=self.final,
-                     cache_tokens_left=int(ex.sessions.cache_tokens_left()), quant_type=ex.quant_type)
+                     cache_tokens_left=int(ex.sessions.cache_tokens_left()), quant_type=ex.quant_type,
+                     kv_cache_dtype=getattr(ex, "kv_cache_dtype", "bf16"))
         if self.next_pings:
             extra["next_pings"] = dict(self.next_pings)
         if self.lb:
@@ -672,7 +678,8 @@ def run_stage_server_with_load_balancing(args, device, cuts: List[int], stop: Op
         from .block_utils import auto_num_blocks
 
         num_blocks = auto_num_blocks(cfg, dtype=dtype, quant_type=quant, device=device,
-                                     total_blocks=total - min_block)
+                                     total_blocks=total - min_block,
+                                     kv_cache_dtype=getattr(args, "kv_cache_dtype", "bf16"))
         logger.info(f"auto num_blocks = {num_blocks}")
     else:
         num_blocks = args.num_blocks or 4

@@ -73,7 +73,13 @@ class ModelConfig:
             n = H * (self.q_dim + 2 * self.kv_dim) + self.q_dim * H + mlp + 2 * H
         return int(n * bytes_per_param)
 
-    def kv_bytes_per_token_per_layer(self, bytes_per_elt: int = 2) -> int:
+    def kv_bytes_per_token_per_layer(self, bytes_per_elt: int = 2, kv_dtype: str = "bf16") -> int:
+        """K + V bytes one token takes in one layer's cache; ``kv_dtype="fp8"``: e4m3 codes plus
+        one e8m0 scale byte per kv head, (head_dim + 1) bytes per token-head."""
+        if kv_dtype == "fp8":
+            return 2 * self.num_key_value_heads * (self.head_dim + 1)
+        if kv_dtype != "bf16":
+            raise ValueError(f"kv_dtype must be 'bf16' or 'fp8', got {kv_dtype!r}")
         return 2 * self.kv_dim * bytes_per_elt
 
     def validate(self) -> None:

@@ -7,7 +7,7 @@ causal mask, in fp32.  Pipeline/executor outputs are compared against it.
 from __future__ import annotations
 
 import math
-from typing import List, Optional
+from typing import Callable, List, Optional
 
 import torch
 import torch.nn.functional as F
@@ -21,8 +21,11 @@ def _rms(x, w, eps):
     return x * torch.rsqrt(x.pow(2).mean(-1, keepdim=True) + eps) * w
 
 
-def llama_forward(weights: List[StageWeights], ids: torch.Tensor, return_hidden: bool = False) -> torch.Tensor:
-    """ids [L] -> logits [L, V] in fp32 through all stages' layers (causal)."""
+def llama_forward(weights: List[StageWeights], ids: torch.Tensor, return_hidden: bool = False,
+                  kv_hook: Optional[Callable] = None) -> torch.Tensor:
+    """ids [L] -> logits [L, V] in fp32 through all stages' layers (causal).  ``kv_hook(k, v) -> (k, v)``
+    (default off) sees every layer's post-RoPE k and v [L, nkv, D] before attention: the oracle of a
+    quantized KV cache passes a fake-quantizer there."""
     cfg = weights[0].cfg
     H, nh, nkv, D = cfg.hidden_size, cfg.num_attention_heads, cfg.num_key_value_heads, cfg.head_dim
     L = ids.numel()
@@ -44,6 +47,8 @@ def llama_forward(weights: List[StageWeights], ids: torch.Tensor, return_hidden:
                 return torch.cat([t1 * c - t2 * s, t2 * c + t1 * s], -1)
 
             q, k = rot(q), rot(k)
+            if kv_hook is not None:
+                k, v = kv_hook(k, v)
             rep = nh // nkv
             k = k.repeat_interleave(rep, 1)
             v = v.repeat_interleave(rep, 1)
@@ -88,10 +93,12 @@ def gpt2_forward(weights: List[StageWeights], ids: torch.Tensor) -> torch.Tensor
     return x @ last.lm_head.float().t()
 
 
-def reference_forward(weights: List[StageWeights], ids: torch.Tensor) -> torch.Tensor:
+def reference_forward(weights: List[StageWeights], ids: torch.Tensor, kv_hook: Optional[Callable] = None) -> torch.Tensor:
     if weights[0].cfg.model_type == "gpt2":
+        if kv_hook is not None:
+            raise ValueError("kv_hook: LLaMA-family oracles only")
         return gpt2_forward(weights, ids)
-    return llama_forward(weights, ids)
+    return llama_forward(weights, ids, kv_hook=kv_hook)
 
 
 def greedy_generate(weights: List[StageWeights], prompt: torch.Tensor, n_new: int) -> List[int]:

@@ -22,6 +22,7 @@ import torch
 
 from . import reference as ref
 from .reference import GU_BLOCK, rope_cos_sin  # noqa: F401  (re-export)
+from .reference import KVF8, dequant_kv_fp8, fake_quant_kv_fp8, quant_kv_fp8  # noqa: F401  (fp8 KV cache)
 
 _LOCK = threading.Lock()
 _LOADED: Optional[bool] = None
@@ -528,13 +529,36 @@ def embed_stage_entry(ids, table, out, residual, ss):
     return out
 
 
+def _kv_f8(k_cache, v_cache) -> bool:
+    """True when the caches are fp8 (``KVF8`` codes + scales); both or neither."""
+    f8 = isinstance(k_cache, KVF8)
+    if f8 != isinstance(v_cache, KVF8):
+        raise TypeError("k_cache and v_cache must both be bf16 tensors or both be fp8 (ops.KVF8) caches")
+    return f8
+
+
+def _no_kv_f8(k_cache, v_cache, what: str) -> None:
+    if isinstance(k_cache, KVF8) or isinstance(v_cache, KVF8):
+        raise NotImplementedError(f"ops.{what} has no fp8 KV cache form: an fp8 cache runs on the flash-decoding "
+                                  "kernel (ops.paged_attention / ops.paged_attention_rope)")
+
+
 def rope_kv_write(qkv, positions, cos, sin, k_cache, v_cache, slots, nh, nkv):
+    """RoPE of q (in place) and the new tokens' k / v into their page slots; an fp8 cache (``KVF8``)
+    gets k (rotated, rounded to bf16) and v quantized per head (``quant_kv_fp8``)."""
+    if _kv_f8(k_cache, v_cache):
+        if not _native(qkv):
+            return ref.rope_kv_write_f8(qkv, positions, cos, sin, k_cache, v_cache, slots, nh, nkv)
+        torch.ops.mpamd.rope_kv_write_f8(qkv, positions, cos, sin, k_cache.codes, v_cache.codes, k_cache.scales,
+                                         v_cache.scales, slots, int(nh), int(nkv))
+        return
     if not _native(qkv):
         return ref.rope_kv_write(qkv, positions, cos, sin, k_cache, v_cache, slots, nh, nkv)
     torch.ops.mpamd.rope_kv_write(qkv, positions, cos, sin, k_cache, v_cache, slots, int(nh), int(nkv))
 
 
 def kv_write(k, v, k_cache, v_cache, slots):
+    _no_kv_f8(k_cache, v_cache, "kv_write")
     if not _native(k):
         return ref.kv_write(k, v, k_cache, v_cache, slots)
     torch.ops.mpamd.kv_write(k, v, k_cache, v_cache, slots)
@@ -607,6 +631,7 @@ def attention_mfma(q, k_cache, v_cache, block_tables, q_seq, q_ctx, qblocks, nh,
     decode.  Same semantics and output as ``paged_attention``; ``qblocks`` from
     ``query_blocks`` (device int32 [2, NB]); ``superblocks`` (``query_superblocks``, device)
     selects the grouped prefill kernel (up to 4 blocks of a sequence per workgroup)."""
+    _no_kv_f8(k_cache, v_cache, "attention_mfma")
     if not _native(q):
         return paged_attention(q, k_cache, v_cache, block_tables, q_seq, q_ctx, nh, nkv, scale, out=out,
                                packed=packed)
@@ -676,6 +701,7 @@ def attention_fa(q, k_cache, v_cache, block_tables, q_seq, q_ctx, fablocks, nh, 
     (csrc/attention_fa.hip).  Same semantics as ``paged_attention``; row-major output only.
     ``fablocks`` from ``fa_blocks`` (device int32 [2, NB]).  The context is split over parts
     only when the grid would leave CUs idle."""
+    _no_kv_f8(k_cache, v_cache, "attention_fa")
     if not _native(q):
         return paged_attention(q, k_cache, v_cache, block_tables, q_seq, q_ctx, nh, nkv, scale, out=out)
     T = q.shape[0]
@@ -709,6 +735,7 @@ def attention_mfma_rope(qkv, k_cache, v_cache, block_tables, q_seq, q_ctx, qbloc
     (ax, as_)`` (packed, one part, head_dim 128): the kernel writes its output as the W8A8-MX GEMM's
     activation (``quant_mx`` layout) there instead of ``out`` - the o projection's input, quantized
     in the attention epilogue."""
+    _no_kv_f8(k_cache, v_cache, "attention_mfma_rope")
     if qkv_part is not None and not _native(qkv):
         qkv = reduce_qkv_part(qkv_part, qkv.dtype)
         qkv_part = None
@@ -774,9 +801,12 @@ def _attn_workspace(workspace, num_queries: int, nh: int, head_dim: int, num_par
 
 def paged_attention(q, k_cache, v_cache, block_tables, q_seq, q_ctx, nh, nkv, scale, out=None, workspace=None,
                     part_size=None, num_parts=None, max_ctx=None, packed=False):
+    """Flash-decoding paged attention (csrc/attention.hip).  ``k_cache`` / ``v_cache``: bf16 pages, or
+    an fp8 cache (``KVF8``), read by the kernel's fp8 form."""
+    f8 = _kv_f8(k_cache, v_cache)
     if not _native(q):
-        y = ref.paged_attention(q, k_cache, v_cache, block_tables, q_seq, q_ctx, nh, nkv, scale,
-                                out=None if packed else out)
+        y = (ref.paged_attention_f8 if f8 else ref.paged_attention)(
+            q, k_cache, v_cache, block_tables, q_seq, q_ctx, nh, nkv, scale, out=None if packed else out)
         return ref.pack_act(y, out=out) if packed else y
     T = q.shape[0]
     D = k_cache.shape[-1]
@@ -788,6 +818,12 @@ def paged_attention(q, k_cache, v_cache, block_tables, q_seq, q_ctx, nh, nkv, sc
         out = _gemm_out(T, nh * D, packed, q.dtype, q.device)
     if workspace is None:
         workspace = attention_workspace(T, nh, D, num_parts, q.device)
+    if f8:
+        torch.ops.mpamd.paged_attention_f8(q, k_cache.codes, v_cache.codes, k_cache.scales, v_cache.scales,
+                                           block_tables, q_seq, q_ctx, out, workspace, int(nh), int(nkv),
+                                           float(scale), int(part_size), int(num_parts), int(bool(packed)),
+                                           _attn_cnt(q.device))
+        return out
     torch.ops.mpamd.paged_attention(q, k_cache, v_cache, block_tables, q_seq, q_ctx, out, workspace, int(nh), int(nkv),
                                     float(scale), int(part_size), int(num_parts), int(bool(packed)), _attn_cnt(q.device))
     return out
@@ -822,13 +858,15 @@ def paged_attention_rope(qkv, k_cache, v_cache, block_tables, q_seq, q_ctx, posi
     token's page-slot write and paged attention in ONE kernel (csrc/attention.hip ROPE path).
     ``qkv`` is the unrotated fused projection and is not modified; with ``qkv_part``
     (``linear_partials`` slabs + row statistics) the kernel reads q / k / v from the slabs and
-    ``qkv`` is not read at all."""
+    ``qkv`` is not read at all.  On an fp8 cache (``KVF8``) the new token is quantized per head,
+    written as codes + scale, and attended to through its dequantized values."""
+    f8 = _kv_f8(k_cache, v_cache)
     if qkv_part is not None and not _native(qkv):
         qkv = reduce_qkv_part(qkv_part, qkv.dtype)
         qkv_part = None
     if not _native(qkv):
         q = qkv.clone()
-        ref.rope_kv_write(q, positions, cos, sin, k_cache, v_cache, slots, nh, nkv)
+        (ref.rope_kv_write_f8 if f8 else ref.rope_kv_write)(q, positions, cos, sin, k_cache, v_cache, slots, nh, nkv)
         return paged_attention(q, k_cache, v_cache, block_tables, q_seq, q_ctx, nh, nkv, scale, out=out,
                                workspace=workspace, part_size=part_size, num_parts=num_parts, max_ctx=max_ctx,
                                packed=packed)
@@ -842,6 +880,13 @@ def paged_attention_rope(qkv, k_cache, v_cache, block_tables, q_seq, q_ctx, posi
         out = _gemm_out(T, nh * D, packed, qkv.dtype, qkv.device)
     if workspace is None:
         workspace = attention_workspace(T, nh, D, num_parts, qkv.device)
+    if f8:
+        torch.ops.mpamd.paged_attention_rope_f8(qkv, k_cache.codes, v_cache.codes, k_cache.scales, v_cache.scales,
+                                                block_tables, q_seq, q_ctx, positions, cos, sin, slots, out,
+                                                workspace, int(nh), int(nkv), float(scale), int(part_size),
+                                                int(num_parts), int(bool(packed)), _attn_cnt(qkv.device),
+                                                *_qkv_part_args(qkv_part))
+        return out
     torch.ops.mpamd.paged_attention_rope(qkv, k_cache, v_cache, block_tables, q_seq, q_ctx, positions, cos, sin,
                                          slots, out, workspace, int(nh), int(nkv), float(scale), int(part_size),
                                          int(num_parts), int(bool(packed)), _attn_cnt(qkv.device),

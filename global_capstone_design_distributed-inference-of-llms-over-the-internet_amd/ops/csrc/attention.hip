@@ -31,7 +31,9 @@
 // first workgroup of the kv head whose context slice holds that token writes them to the
 // page slot (slots[t] < 0: padded row, nothing written) for later steps.
 #include "attn_common.h"
+#include "kv_f8.h"
 #include <stdlib.h>
+#include <type_traits>
 
 // K/V page loads of the single-pass decode kernel: each cached row is read once per step, so
 // by default they carry the non-temporal hint (MI355X_MICROARCH nt-weights: issued -> landed
@@ -66,6 +68,13 @@ struct RopeFuse {
   bf16_t* kw;           // the k / v caches, written only at the new token's slot
   bf16_t* vw;
   QkvPart qp;           // qp.part != nullptr: q / k / v from the qkv GEMM's split-K partials
+};
+
+// One cached token's 8 head dims of a lane on an fp8 cache (kv_f8.h): 8 codes + the token's scale
+// byte, converted to the bf16 operand when its iteration computes.
+struct KvF8Reg {
+  kvf8x8 c;
+  unsigned e;
 };
 
 // The folded qkv projection (rf.qp: split-K partial slabs): the workgroup's NREP rotated query
@@ -156,13 +165,19 @@ __device__ __forceinline__ void split_combine(int* cnt_slot, int NP, const float
 // stream (always on).
 // (16-wave workgroups for small grids stopped paying once the 4-wave form was pipelined,
 // profiles/r4o; the unpipelined form measured slower: both removed.)
-template <int D, int NREP, bool ROPE, int NW, bool PIPE, int U = 4>
+// F8: the caches hold e4m3 codes + e8m0 row scales (kv_f8.h, f8 = the scale tensors): the stream is
+// 8 B + 1 scale byte per lane per token, each iteration's registers are converted to the bf16
+// operands right before its compute (exactly: the arithmetic below is the bf16 kernel's), and the
+// ROPE form quantizes the new token per head, writes codes + scale and attends to the DEQUANTIZED
+// values - what every later step will read.
+template <int D, int NREP, bool ROPE, int NW, bool PIPE, int U = 4, bool F8 = false>
 __global__ __launch_bounds__(NW * 64, MP_ATTN_MINW) void paged_attn1_kernel(
     const bf16_t* __restrict__ q, int64_t q_stride, const bf16_t* __restrict__ kc,
     const bf16_t* __restrict__ vc, const int32_t* __restrict__ block_tables, int bt_stride,
     const int32_t* __restrict__ q_seq, const int32_t* __restrict__ q_ctx, bf16_t* __restrict__ out,
     float* __restrict__ part_o, float* __restrict__ part_ml, int nkv, int nh, int page_log2, int PS, int NP,
-    float scale_log2, int packed_mt, RopeFuse rf, int* __restrict__ cnt) {
+    float scale_log2, int packed_mt, RopeFuse rf, int* __restrict__ cnt, KvF8 f8) {
+  using kvreg_t = std::conditional_t<F8, KvF8Reg, u16x8>;
   constexpr int LPT = D / 8;
   constexpr int TPI = 64 / LPT;
   static_assert(U % 2 == 0, "P V pairs the tokens u, u + 1");
@@ -211,13 +226,24 @@ __global__ __launch_bounds__(NW * 64, MP_ATTN_MINW) void paged_attn1_kernel(
     for (int u = 0; u < U; ++u) pgn[u] = bt[min(b0 + u * TPI + tg, end - 1) >> page_log2];
   }
 
-  auto issue = [&](int b, const int* pg, u16x8* kd, u16x8* vd) {
+  auto issue = [&](int b, const int* pg, kvreg_t* kd, kvreg_t* vd) {
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const int tc = min(b + u * TPI + tg, end - 1);
-      const int64_t off = (int64_t)pg[u] * page_stride + head_off + (int64_t)(tc & (page_size - 1)) * D;
-      kd[u] = MP_KV_LOAD(reinterpret_cast<const u16x8*>(kc + off));
-      vd[u] = MP_KV_LOAD(reinterpret_cast<const u16x8*>(vc + off));
+      if constexpr (F8) {
+        // (token, kv head) row index = the scale's offset; its codes start at row * D bytes
+        const int64_t row = ((int64_t)pg[u] * nkv + g) * page_size + (tc & (page_size - 1));
+        const uint8_t* kb = reinterpret_cast<const uint8_t*>(kc) + row * D + sl * 8;
+        const uint8_t* vb = reinterpret_cast<const uint8_t*>(vc) + row * D + sl * 8;
+        kd[u].c = MP_KV_LOAD(reinterpret_cast<const kvf8x8*>(kb));
+        vd[u].c = MP_KV_LOAD(reinterpret_cast<const kvf8x8*>(vb));
+        kd[u].e = MP_KV_LOAD(f8.ks + row);
+        vd[u].e = MP_KV_LOAD(f8.vs + row);
+      } else {
+        const int64_t off = (int64_t)pg[u] * page_stride + head_off + (int64_t)(tc & (page_size - 1)) * D;
+        kd[u] = MP_KV_LOAD(reinterpret_cast<const u16x8*>(kc + off));
+        vd[u] = MP_KV_LOAD(reinterpret_cast<const u16x8*>(vc + off));
+      }
     }
   };
   auto page_ids = [&](int b, int* pg) {
@@ -226,7 +252,7 @@ __global__ __launch_bounds__(NW * 64, MP_ATTN_MINW) void paged_attn1_kernel(
   };
   // first iteration's K / V (PIPE) issued here, ahead of the query / RoPE loads: the cache
   // stream's round trip overlaps the rotary-table round trip instead of following it
-  u16x8 kv[U], vv[U];
+  kvreg_t kv[U], vv[U];
   int pgm[U];
   if constexpr (PIPE) {
     page_ids(start + w * TPW + NW * TPW, pgm);
@@ -271,7 +297,25 @@ __global__ __launch_bounds__(NW * 64, MP_ATTN_MINW) void paged_attn1_kernel(
     }
     tnew = ctx - 1;
     const int64_t slot = rf.slots[t];
-    if (tnew >= start && tnew < end && slot >= 0 && tid < LPT && hbase % (nh / nkv) == 0) {
+    if constexpr (F8) {
+      // quantize the new token's head (its D values sit in the LPT lanes of a token group; every
+      // group holds the same copy) and keep the dequantized values for this step's attention
+      const int ek = mx_e8m0(kvf8_group_max<LPT>(kvf8_amax8(kn)));
+      const int ev = mx_e8m0(kvf8_group_max<LPT>(kvf8_amax8(vn)));
+      const kvf8x8 kq = kvf8_quant8(kn, ek), vq = kvf8_quant8(vn, ev);
+      kn = kvf8_dequant8(kq, (unsigned)ek);
+      vn = kvf8_dequant8(vq, (unsigned)ev);
+      if (tnew >= start && tnew < end && slot >= 0 && tid < LPT && hbase % (nh / nkv) == 0) {
+        const int64_t pg = slot >> page_log2, off = slot & (page_size - 1);
+        const int64_t row = (pg * nkv + g) * page_size + off;
+        *reinterpret_cast<kvf8x8*>(reinterpret_cast<uint8_t*>(rf.kw) + row * D + sl * 8) = kq;
+        *reinterpret_cast<kvf8x8*>(reinterpret_cast<uint8_t*>(rf.vw) + row * D + sl * 8) = vq;
+        if (tid == 0) {
+          f8.ks[row] = (uint8_t)ek;
+          f8.vs[row] = (uint8_t)ev;
+        }
+      }
+    } else if (tnew >= start && tnew < end && slot >= 0 && tid < LPT && hbase % (nh / nkv) == 0) {
       const int64_t pg = slot >> page_log2, off = slot & (page_size - 1);
       const int64_t dst = pg * page_stride + head_off + off * D;
       *reinterpret_cast<u16x8*>(rf.kw + dst) = kn;
@@ -344,16 +388,30 @@ __global__ __launch_bounds__(NW * 64, MP_ATTN_MINW) void paged_attn1_kernel(
       }
 
   };
+  // one iteration's registers -> compute: the fp8 stream is converted here, the bf16 one passes through
+  auto step = [&](int base, kvreg_t (&kr)[U], kvreg_t (&vr)[U]) {
+    if constexpr (F8) {
+      u16x8 kb[U], vb[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        kb[u] = kvf8_dequant8(kr[u].c, kr[u].e);
+        vb[u] = kvf8_dequant8(vr[u].c, vr[u].e);
+      }
+      compute(base, kb, vb);
+    } else {
+      compute(base, kr, vr);
+    }
+  };
   if constexpr (PIPE) {
     // software-pipelined: iteration i+1's K / V (and i+2's page ids) are in flight while
     // iteration i computes, so the stream never stops between iterations (the first
     // iteration's loads were issued ahead of the query / RoPE prologue)
     for (int base = start + w * TPW; base < end; base += NW * TPW) {
       const int nb = base + NW * TPW;
-      u16x8 kx[U], vx[U];
+      kvreg_t kx[U], vx[U];
       page_ids(nb + NW * TPW, pgn);
       if (nb < end) issue(nb, pgm, kx, vx);
-      compute(base, kv, vv);
+      step(base, kv, vv);
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         kv[u] = kx[u];
@@ -362,6 +420,7 @@ __global__ __launch_bounds__(NW * 64, MP_ATTN_MINW) void paged_attn1_kernel(
       }
     }
   } else {
+    static_assert(PIPE || !F8, "the fp8 cache runs the pipelined form only");
     for (int base = start + w * TPW; base < end; base += NW * TPW) {
       issue(base, pgn, kv, vv);
       // next iteration's page ids, in flight behind the K / V loads
@@ -457,19 +516,19 @@ __global__ void paged_attn_reduce_kernel(const float* __restrict__ part_o, const
   }
 }
 
-template <int D, int NREP, int NW>
+template <int D, int NREP, int NW, bool F8>
 static void launch_attn_nw(const void* q, int64_t q_stride, const void* kc, const void* vc, const int32_t* bt,
                            int bt_stride, const int32_t* q_seq, const int32_t* q_ctx, void* out, float* ws_o,
                            float* ws_ml, int T, int nkv, int nh, int page_log2, int PS, int NP, float scale_log2,
-                           int packed_mt, const RopeFuse& rf, int* cnt, hipStream_t stream) {
+                           int packed_mt, const RopeFuse& rf, int* cnt, KvF8 f8, hipStream_t stream) {
   const size_t lds = (size_t)(NW * NREP * D + 2 * NW * NREP + 4) * sizeof(float);
   auto go = [&](auto kern) {
     hipLaunchKernelGGL(kern, dim3(NP, nh / NREP, T), dim3(64 * NW), lds, stream, (const bf16_t*)q, q_stride,
                        (const bf16_t*)kc, (const bf16_t*)vc, bt, bt_stride, q_seq, q_ctx, (bf16_t*)out, ws_o, ws_ml,
-                       nkv, nh, page_log2, PS, NP, scale_log2, packed_mt, rf, cnt);
+                       nkv, nh, page_log2, PS, NP, scale_log2, packed_mt, rf, cnt, f8);
   };
-  if (rf.pos) go(paged_attn1_kernel<D, NREP, true, NW, true>);
-  else go(paged_attn1_kernel<D, NREP, false, NW, true>);
+  if (rf.pos) go(paged_attn1_kernel<D, NREP, true, NW, true, 4, F8>);
+  else go(paged_attn1_kernel<D, NREP, false, NW, true, 4, F8>);
 }
 
 // Waves per workgroup from the grid: one (query, head group, context part) per workgroup, so a
@@ -477,17 +536,17 @@ static void launch_attn_nw(const void* q, int64_t q_stride, const void* kc, cons
 // covered in one or two dependent iterations (cold 1 x 170 MHA: 10.4 -> 9.9 us) - and every other
 // grid 4-wave ones.  (2-wave workgroups, the 64-session step's 2048 in one round of residency,
 // measured 36.5 -> 38.1 us cold at 64 x 170: profiles/r6attn.)
-template <int D, int NREP>
+template <int D, int NREP, bool F8>
 static void launch_attn(const void* q, int64_t q_stride, const void* kc, const void* vc, const int32_t* bt,
                         int bt_stride, const int32_t* q_seq, const int32_t* q_ctx, void* out, float* ws_o,
                         float* ws_ml, int T, int nkv, int nh, int page_log2, int PS, int NP, float scale_log2,
-                        int packed_mt, const RopeFuse& rf, int* cnt, hipStream_t stream) {
+                        int packed_mt, const RopeFuse& rf, int* cnt, KvF8 f8, hipStream_t stream) {
   const int64_t wgs = (int64_t)NP * (nh / NREP) * T;
   const int nw = MP_ATTN_NW ? MP_ATTN_NW : (wgs <= 128 ? 8 : 4);
 #define MP_ATTN_NW_CASE(W)                                                                                     \
   if (nw == W) {                                                                                               \
-    launch_attn_nw<D, NREP, W>(q, q_stride, kc, vc, bt, bt_stride, q_seq, q_ctx, out, ws_o, ws_ml, T, nkv, nh,  \
-                               page_log2, PS, NP, scale_log2, packed_mt, rf, cnt, stream);                     \
+    launch_attn_nw<D, NREP, W, F8>(q, q_stride, kc, vc, bt, bt_stride, q_seq, q_ctx, out, ws_o, ws_ml, T, nkv, \
+                                   nh, page_log2, PS, NP, scale_log2, packed_mt, rf, cnt, f8, stream);         \
     return;                                                                                                    \
   }
   MP_ATTN_NW_CASE(8)
@@ -497,12 +556,13 @@ static void launch_attn(const void* q, int64_t q_stride, const void* kc, const v
 
 }  // namespace mp
 
-extern "C" int mp_paged_attention(const void* q, int64_t q_stride, const void* kc, const void* vc,
+// kc / vc: bf16 pages, or with scales (ks, vs) the fp8 cache's code pages (kv_f8.h)
+static int paged_attention_launch(const void* q, int64_t q_stride, const void* kc, const void* vc,
                                   const int32_t* bt, int bt_stride, const int32_t* q_seq, const int32_t* q_ctx,
                                   void* out, float* workspace, int T, int nh, int nkv, int D, int page_size,
                                   int PS, int NP, float scale, int packed_mt, const int64_t* rope_pos,
                                   const float* cos_t, const float* sin_t, const int64_t* slots, int* counters,
-                                  int n_counters, const void* qkv_part_v, hipStream_t stream) {
+                                  int n_counters, const void* qkv_part_v, mp::KvF8 f8, hipStream_t stream) {
   (void)hipGetLastError();  // an earlier non-mpamd HIP call's stale error is not this launch's
   using namespace mp;
   RopeFuse rf{rope_pos, cos_t, sin_t, slots, (bf16_t*)const_cast<void*>(kc), (bf16_t*)const_cast<void*>(vc),
@@ -529,8 +589,12 @@ extern "C" int mp_paged_attention(const void* q, int64_t q_stride, const void* k
   int* cnt = (NP > 1 && counters != nullptr && (int64_t)T * (nh / hpb) <= n_counters) ? counters : nullptr;
 #define MP_ATTN_CASE(DD, RR)                                                                                  \
   if (D == DD && hpb == RR) {                                                                                 \
-    launch_attn<DD, RR>(q, q_stride, kc, vc, bt, bt_stride, q_seq, q_ctx, out, ws_o, ws_ml, T, nkv, nh,       \
-                        page_log2, PS, NP, scale_log2, packed_mt, rf, cnt, stream);                           \
+    if (f8.ks != nullptr)                                                                                     \
+      launch_attn<DD, RR, true>(q, q_stride, kc, vc, bt, bt_stride, q_seq, q_ctx, out, ws_o, ws_ml, T, nkv,   \
+                                nh, page_log2, PS, NP, scale_log2, packed_mt, rf, cnt, f8, stream);           \
+    else                                                                                                      \
+      launch_attn<DD, RR, false>(q, q_stride, kc, vc, bt, bt_stride, q_seq, q_ctx, out, ws_o, ws_ml, T, nkv,  \
+                                 nh, page_log2, PS, NP, scale_log2, packed_mt, rf, cnt, f8, stream);          \
     goto launched;                                                                                            \
   }
   MP_ATTN_CASE(128, 1)
@@ -547,4 +611,30 @@ launched:
                        D, nh, packed_mt);
   }
   return (int)hipGetLastError();
+}
+
+extern "C" int mp_paged_attention(const void* q, int64_t q_stride, const void* kc, const void* vc,
+                                  const int32_t* bt, int bt_stride, const int32_t* q_seq, const int32_t* q_ctx,
+                                  void* out, float* workspace, int T, int nh, int nkv, int D, int page_size,
+                                  int PS, int NP, float scale, int packed_mt, const int64_t* rope_pos,
+                                  const float* cos_t, const float* sin_t, const int64_t* slots, int* counters,
+                                  int n_counters, const void* qkv_part_v, hipStream_t stream) {
+  return paged_attention_launch(q, q_stride, kc, vc, bt, bt_stride, q_seq, q_ctx, out, workspace, T, nh, nkv, D,
+                                page_size, PS, NP, scale, packed_mt, rope_pos, cos_t, sin_t, slots, counters,
+                                n_counters, qkv_part_v, mp::KvF8{nullptr, nullptr}, stream);
+}
+
+// The same launch on an fp8 KV cache: kc / vc uint8 e4m3 codes [pages, nkv, page, D], ks / vs their
+// e8m0 row scales [pages, nkv, page] (written too on the RoPE form).
+extern "C" int mp_paged_attention_f8(const void* q, int64_t q_stride, const void* kc, const void* vc, void* ks,
+                                     void* vs, const int32_t* bt, int bt_stride, const int32_t* q_seq,
+                                     const int32_t* q_ctx, void* out, float* workspace, int T, int nh, int nkv,
+                                     int D, int page_size, int PS, int NP, float scale, int packed_mt,
+                                     const int64_t* rope_pos, const float* cos_t, const float* sin_t,
+                                     const int64_t* slots, int* counters, int n_counters, const void* qkv_part_v,
+                                     hipStream_t stream) {
+  if (ks == nullptr || vs == nullptr) return -5;
+  return paged_attention_launch(q, q_stride, kc, vc, bt, bt_stride, q_seq, q_ctx, out, workspace, T, nh, nkv, D,
+                                page_size, PS, NP, scale, packed_mt, rope_pos, cos_t, sin_t, slots, counters,
+                                n_counters, qkv_part_v, mp::KvF8{(uint8_t*)ks, (uint8_t*)vs}, stream);
 }

@@ -25,6 +25,15 @@ int mp_paged_attention(const void* q, int64_t q_stride, const void* kc, const vo
                        int nh, int nkv, int D, int page_size, int PS, int NP, float scale, int packed_mt,
                        const int64_t* rope_pos, const float* cos_t, const float* sin_t, const int64_t* slots,
                        int* counters, int n_counters, const void* qkv_part, hipStream_t stream);
+int mp_paged_attention_f8(const void* q, int64_t q_stride, const void* kc, const void* vc, void* ks, void* vs,
+                          const int32_t* bt, int bt_stride, const int32_t* q_seq, const int32_t* q_ctx, void* out,
+                          float* workspace, int T, int nh, int nkv, int D, int page_size, int PS, int NP, float scale,
+                          int packed_mt, const int64_t* rope_pos, const float* cos_t, const float* sin_t,
+                          const int64_t* slots, int* counters, int n_counters, const void* qkv_part,
+                          hipStream_t stream);
+int mp_rope_kv_write_f8(void* qkv, int64_t qkv_stride, const int64_t* pos, const float* cos_t, const float* sin_t,
+                        void* kc, void* vc, void* ks, void* vs, const int64_t* slots, int T, int nh, int nkv, int D,
+                        int page_size, hipStream_t stream);
 int mp_embedding(const int64_t* ids, const void* table, void* out, int T, int H, int64_t vocab, hipStream_t stream);
 int mp_swiglu(const void* gu, void* out, int64_t T, int F, hipStream_t stream);
 int mp_add(const void* a, const void* b, void* y, int64_t n, hipStream_t stream);
@@ -242,6 +251,42 @@ void rope_kv_write(at::Tensor& qkv, const at::Tensor& positions, const at::Tenso
                "rope_kv_write");
 }
 
+// fp8 KV cache (kv_f8.h): codes uint8 [pages, nkv, page, D] + e8m0 scales uint8 [pages, nkv, page]
+static void check_kv_f8(const at::Tensor& k_cache, const at::Tensor& v_cache, const at::Tensor& k_scale,
+                        const at::Tensor& v_scale, int64_t nkv) {
+  for (const at::Tensor* t : {&k_cache, &v_cache, &k_scale, &v_scale})
+    MP_CHECK(t->is_cuda() && t->scalar_type() == at::kByte && t->is_contiguous() && t->device() == k_cache.device(),
+             "fp8 KV cache: codes and scales are contiguous uint8 tensors on one GPU");
+  MP_CHECK(k_cache.dim() == 4 && k_cache.sizes() == v_cache.sizes() && k_cache.size(1) == nkv,
+           "fp8 KV codes [pages, nkv, page, D]");
+  MP_CHECK(k_cache.size(3) == 64 || k_cache.size(3) == 128, "fp8 KV cache: head_dim 64 or 128");
+  MP_CHECK(k_scale.dim() == 3 && k_scale.sizes() == v_scale.sizes() && k_scale.size(0) == k_cache.size(0) &&
+               k_scale.size(1) == nkv && k_scale.size(2) == k_cache.size(2),
+           "fp8 KV scales [pages, nkv, page] must match the codes' pages, heads and page_size");
+  MP_CHECK(reinterpret_cast<uintptr_t>(k_cache.data_ptr()) % 8 == 0 &&
+               reinterpret_cast<uintptr_t>(v_cache.data_ptr()) % 8 == 0, "fp8 KV codes must be 8-B aligned");
+}
+
+void rope_kv_write_f8(at::Tensor& qkv, const at::Tensor& positions, const at::Tensor& cos, const at::Tensor& sin,
+                      at::Tensor& k_cache, at::Tensor& v_cache, at::Tensor& k_scale, at::Tensor& v_scale,
+                      const at::Tensor& slots, int64_t nh, int64_t nkv) {
+  check_bf16_cuda(qkv, "qkv");
+  check_rows(qkv, "qkv");
+  check_kv_f8(k_cache, v_cache, k_scale, v_scale, nkv);
+  const int D = k_cache.size(3), page = k_cache.size(2);
+  MP_CHECK(qkv.size(1) == (nh + 2 * nkv) * D, "qkv width");
+  const int T = qkv.size(0);
+  MP_CHECK(positions.scalar_type() == at::kLong && positions.numel() == T && positions.is_contiguous(), "positions");
+  MP_CHECK(slots.scalar_type() == at::kLong && slots.numel() == T && slots.is_contiguous(), "slots");
+  MP_CHECK(cos.scalar_type() == at::kFloat && sin.scalar_type() == at::kFloat && cos.is_contiguous() &&
+               sin.is_contiguous() && cos.size(1) == D / 2 && sin.sizes() == cos.sizes(),
+           "cos/sin tables fp32 [max_pos, D/2]");
+  check_launch(mp_rope_kv_write_f8(qkv.data_ptr(), qkv.stride(0), positions.data_ptr<int64_t>(), cos.data_ptr<float>(),
+                                   sin.data_ptr<float>(), k_cache.data_ptr(), v_cache.data_ptr(), k_scale.data_ptr(),
+                                   v_scale.data_ptr(), slots.data_ptr<int64_t>(), T, nh, nkv, D, page, cur_stream()),
+               "rope_kv_write_f8");
+}
+
 void kv_write(const at::Tensor& k, const at::Tensor& v, at::Tensor& k_cache, at::Tensor& v_cache,
               const at::Tensor& slots) {
   check_bf16_cuda(k, "k");
@@ -290,11 +335,20 @@ static void paged_attention_impl(const at::Tensor& q, const at::Tensor& k_cache,
                                  at::Tensor& out, at::Tensor& workspace, int64_t nh, int64_t nkv, double scale,
                                  int64_t part_size, int64_t num_parts, int64_t packed, const int64_t* rope_pos,
                                  const float* cos_t, const float* sin_t, const int64_t* slots,
-                                 const c10::optional<at::Tensor>& counters, const QkvPartArgs* qp = nullptr) {
+                                 const c10::optional<at::Tensor>& counters, const QkvPartArgs* qp = nullptr,
+                                 const at::Tensor* k_scale = nullptr, const at::Tensor* v_scale = nullptr) {
   check_bf16_cuda(q, "q");
   check_rows(q, "q");
   check_bf16_cuda(out, "out");
   MP_CHECK(out.is_contiguous(), "out contiguous");
+  if (k_scale != nullptr) {
+    check_kv_f8(k_cache, v_cache, *k_scale, *v_scale, nkv);
+  } else {
+    // (an fp8 cache's byte pages handed to the bf16 kernel would be read past their end)
+    check_bf16_cuda(k_cache, "k_cache");
+    check_bf16_cuda(v_cache, "v_cache");
+    MP_CHECK(k_cache.dim() == 4 && k_cache.sizes() == v_cache.sizes(), "cache [pages, nkv, page, D]");
+  }
   const int D = k_cache.size(3);
   const int T = q.size(0);
   MP_CHECK(q.size(1) >= nh * D, "q width");
@@ -317,6 +371,16 @@ static void paged_attention_impl(const at::Tensor& q, const at::Tensor& k_cache,
              "counters: zero-initialised cuda int32");
     cp = counters->data_ptr<int32_t>();
     ncnt = (int)counters->numel();
+  }
+  if (k_scale != nullptr) {
+    check_launch(mp_paged_attention_f8(q.data_ptr(), q.stride(0), k_cache.data_ptr(), v_cache.data_ptr(),
+                                       k_scale->data_ptr(), v_scale->data_ptr(), block_tables.data_ptr<int32_t>(),
+                                       block_tables.stride(0), q_seq.data_ptr<int32_t>(), q_ctx.data_ptr<int32_t>(),
+                                       out.data_ptr(), workspace.data_ptr<float>(), T, nh, nkv, D, k_cache.size(2),
+                                       part_size, num_parts, (float)scale, packed ? (int)((T + 15) / 16) : 0,
+                                       rope_pos, cos_t, sin_t, slots, cp, ncnt, qp, cur_stream()),
+                 "paged_attention_f8");
+    return;
   }
   check_launch(mp_paged_attention(q.data_ptr(), q.stride(0), k_cache.data_ptr(), v_cache.data_ptr(),
                                   block_tables.data_ptr<int32_t>(), block_tables.stride(0), q_seq.data_ptr<int32_t>(),
@@ -362,6 +426,40 @@ void paged_attention_rope(const at::Tensor& qkv, at::Tensor& k_cache, at::Tensor
                        slots.data_ptr<int64_t>(), counters, has_qp ? &qp : nullptr);
 }
 
+// The flash-decoding kernel on an fp8 KV cache (attention.hip F8 form).
+void paged_attention_f8(const at::Tensor& q, const at::Tensor& k_cache, const at::Tensor& v_cache,
+                        const at::Tensor& k_scale, const at::Tensor& v_scale, const at::Tensor& block_tables,
+                        const at::Tensor& q_seq, const at::Tensor& q_ctx, at::Tensor& out, at::Tensor& workspace,
+                        int64_t nh, int64_t nkv, double scale, int64_t part_size, int64_t num_parts, int64_t packed,
+                        const c10::optional<at::Tensor>& counters) {
+  paged_attention_impl(q, k_cache, v_cache, block_tables, q_seq, q_ctx, out, workspace, nh, nkv, scale, part_size,
+                       num_parts, packed, nullptr, nullptr, nullptr, nullptr, counters, nullptr, &k_scale, &v_scale);
+}
+
+// Its fused decode form: RoPE, the new token's quantization + page write and attention in one launch.
+void paged_attention_rope_f8(const at::Tensor& qkv, at::Tensor& k_cache, at::Tensor& v_cache, at::Tensor& k_scale,
+                             at::Tensor& v_scale, const at::Tensor& block_tables, const at::Tensor& q_seq,
+                             const at::Tensor& q_ctx, const at::Tensor& positions, const at::Tensor& cos,
+                             const at::Tensor& sin, const at::Tensor& slots, at::Tensor& out, at::Tensor& workspace,
+                             int64_t nh, int64_t nkv, double scale, int64_t part_size, int64_t num_parts,
+                             int64_t packed, const c10::optional<at::Tensor>& counters,
+                             const c10::optional<at::Tensor>& qkv_part, int64_t part_splits,
+                             const c10::optional<at::Tensor>& part_ss, double inv_k, double eps) {
+  check_kv_f8(k_cache, v_cache, k_scale, v_scale, nkv);
+  const int D = k_cache.size(3), T = qkv.size(0);
+  MP_CHECK(qkv.size(1) == (nh + 2 * nkv) * D, "qkv width");
+  MP_CHECK(positions.scalar_type() == at::kLong && positions.numel() == T && positions.is_contiguous(), "positions");
+  MP_CHECK(slots.scalar_type() == at::kLong && slots.numel() == T && slots.is_contiguous(), "slots");
+  MP_CHECK(cos.scalar_type() == at::kFloat && sin.scalar_type() == at::kFloat && cos.is_contiguous() &&
+               sin.is_contiguous() && cos.size(1) == D / 2 && sin.sizes() == cos.sizes(),
+           "cos/sin tables fp32 [max_pos, D/2]");
+  QkvPartArgs qp;
+  const bool has_qp = qkv_part_args(qkv_part, part_splits, part_ss, inv_k, eps, T, qkv.size(1), qp);
+  paged_attention_impl(qkv, k_cache, v_cache, block_tables, q_seq, q_ctx, out, workspace, nh, nkv, scale, part_size,
+                       num_parts, packed, positions.data_ptr<int64_t>(), cos.data_ptr<float>(), sin.data_ptr<float>(),
+                       slots.data_ptr<int64_t>(), counters, has_qp ? &qp : nullptr, &k_scale, &v_scale);
+}
+
 static void attention_mfma_impl(const at::Tensor& q, const at::Tensor& k_cache, const at::Tensor& v_cache,
                                 const at::Tensor& block_tables, const at::Tensor& q_seq, const at::Tensor& q_ctx,
                                 const at::Tensor& qblocks, at::Tensor& out, at::Tensor& workspace, int64_t nh,
@@ -373,6 +471,9 @@ static void attention_mfma_impl(const at::Tensor& q, const at::Tensor& k_cache, 
   check_rows(q, "q");
   check_bf16_cuda(out, "out");
   MP_CHECK(out.is_contiguous(), "out contiguous");
+  check_bf16_cuda(k_cache, "k_cache");
+  check_bf16_cuda(v_cache, "v_cache");
+  MP_CHECK(k_cache.dim() == 4 && k_cache.sizes() == v_cache.sizes(), "cache [pages, nkv, page, D]");
   const int D = k_cache.size(3);
   const int T = q.size(0);
   MP_CHECK(q.size(1) >= nh * D, "q width");
@@ -853,6 +954,19 @@ TORCH_LIBRARY(mpamd, m) {
       "int nh, int nkv, float scale, int part_size, int num_parts, int packed, Tensor(e!)? counters=None, "
       "Tensor? qkv_part=None, int part_splits=0, Tensor? part_ss=None, float inv_k=0., float eps=0.) -> ()");
   m.def(
+      "rope_kv_write_f8(Tensor(a!) qkv, Tensor positions, Tensor cos, Tensor sin, Tensor(b!) k_cache, "
+      "Tensor(c!) v_cache, Tensor(d!) k_scale, Tensor(e!) v_scale, Tensor slots, int nh, int nkv) -> ()");
+  m.def(
+      "paged_attention_f8(Tensor q, Tensor k_cache, Tensor v_cache, Tensor k_scale, Tensor v_scale, "
+      "Tensor block_tables, Tensor q_seq, Tensor q_ctx, Tensor(a!) out, Tensor(b!) workspace, int nh, int nkv, "
+      "float scale, int part_size, int num_parts, int packed, Tensor(c!)? counters=None) -> ()");
+  m.def(
+      "paged_attention_rope_f8(Tensor qkv, Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor(c!) k_scale, "
+      "Tensor(d!) v_scale, Tensor block_tables, Tensor q_seq, Tensor q_ctx, Tensor positions, Tensor cos, Tensor sin, "
+      "Tensor slots, Tensor(e!) out, Tensor(f!) workspace, int nh, int nkv, float scale, int part_size, "
+      "int num_parts, int packed, Tensor(g!)? counters=None, Tensor? qkv_part=None, int part_splits=0, "
+      "Tensor? part_ss=None, float inv_k=0., float eps=0.) -> ()");
+  m.def(
       "attention_mfma(Tensor q, Tensor k_cache, Tensor v_cache, Tensor block_tables, Tensor q_seq, Tensor q_ctx, "
       "Tensor qblocks, Tensor(a!) out, Tensor(b!) workspace, int nh, int nkv, float scale, int part_size, "
       "int num_parts, int packed, Tensor? superblocks=None) -> ()");
@@ -907,6 +1021,9 @@ TORCH_LIBRARY_IMPL(mpamd, CUDA, m) {
   m.impl("kv_write", &kv_write);
   m.impl("paged_attention", &paged_attention);
   m.impl("paged_attention_rope", &paged_attention_rope);
+  m.impl("rope_kv_write_f8", &rope_kv_write_f8);
+  m.impl("paged_attention_f8", &paged_attention_f8);
+  m.impl("paged_attention_rope_f8", &paged_attention_rope_f8);
   m.impl("attention_mfma", &attention_mfma);
   m.impl("attention_fa", &attention_fa);
   m.impl("attention_mfma_rope", &attention_mfma_rope);

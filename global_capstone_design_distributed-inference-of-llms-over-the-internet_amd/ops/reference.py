@@ -157,6 +157,117 @@ def paged_attention(q, k_cache, v_cache, block_tables, q_seq, q_ctx, nh, nkv, sc
     return y
 
 
+# ---------------------------------------------------------------------------------------
+# fp8 KV cache (csrc/kv_f8.h): per layer K and V are e4m3 codes uint8 [pages, nkv, page, D] plus one
+# e8m0 scale byte per (token, kv head) uint8 [pages, nkv, page] - (D + 1) bytes per token-head.
+class KVF8:
+    """One fp8 K or V cache of a layer: ``codes`` + ``scales``.  The attention / KV-write ops take
+    it where they take a bf16 cache tensor."""
+
+    __slots__ = ("codes", "scales")
+
+    def __init__(self, codes: torch.Tensor, scales: torch.Tensor):
+        if codes.dtype != torch.uint8 or scales.dtype != torch.uint8:
+            raise TypeError("KVF8: codes and scales are uint8 tensors")
+        if codes.dim() != 4 or tuple(scales.shape) != tuple(codes.shape[:3]):
+            raise ValueError(f"KVF8: codes [pages, nkv, page, D] and scales [pages, nkv, page], got "
+                             f"{tuple(codes.shape)} / {tuple(scales.shape)}")
+        self.codes, self.scales = codes, scales
+
+    @property
+    def shape(self):
+        return self.codes.shape
+
+    @property
+    def device(self):
+        return self.codes.device
+
+    dtype = torch.uint8
+
+    @classmethod
+    def empty(cls, num_pages, nkv, page_size, head_dim, device="cpu"):
+        """Zero codes, unit scales (e = 127): every row dequantizes to zeros."""
+        return cls(torch.zeros(num_pages, nkv, page_size, head_dim, dtype=torch.uint8, device=device),
+                   torch.full((num_pages, nkv, page_size), 127, dtype=torch.uint8, device=device))
+
+    @classmethod
+    def from_dense(cls, x: torch.Tensor):
+        """Quantize a bf16 cache [pages, nkv, page, D]."""
+        return cls(*quant_kv_fp8(x))
+
+    def dequant(self, dtype=torch.bfloat16) -> torch.Tensor:
+        return dequant_kv_fp8(self.codes, self.scales, dtype)
+
+
+_INV448 = torch.tensor(1.0 / 448.0, dtype=torch.float32)
+
+
+def kv_fp8_exponent(amax: torch.Tensor) -> torch.Tensor:
+    """The kernels' ``mx_e8m0`` on fp32 ``amax`` (int32 result): the biased exponent of the smallest
+    power-of-two scale s with amax / s <= 448, 127 for a zero row, clamped to [1, 253] - computed
+    as the kernels do, from the bits of the fp32 product amax * (1 / 448)."""
+    a = amax.float()
+    b = (a * _INV448.to(a.device)).view(torch.int32)
+    e = ((b >> 23) & 255) + ((b & 0x7FFFFF) != 0).to(torch.int32)
+    e = e.clamp(1, 253)
+    return torch.where(a > 0, e, torch.full_like(e, 127))
+
+
+def quant_kv_fp8(x: torch.Tensor):
+    """Rows [..., D] (read as bf16) -> (codes uint8 [..., D] e4m3fn, scales uint8 [...] e8m0): the
+    fp8 KV cache's row rule, matched by the kernels bit for bit.  amax over the row's bf16 values,
+    e = ``kv_fp8_exponent(amax)``, code = e4m3 (RNE, saturating) of x * 2^(127 - e)."""
+    v = x.to(torch.bfloat16).float()
+    e = kv_fp8_exponent(v.abs().amax(-1))
+    inv = ((254 - e) << 23).view(torch.float32)  # 2^(127 - e), as mx_inv_scale
+    q = (v * inv.unsqueeze(-1)).clamp(-448.0, 448.0).to(torch.float8_e4m3fn).view(torch.uint8)
+    return q, e.to(torch.uint8)
+
+
+def dequant_kv_fp8(codes: torch.Tensor, scales: torch.Tensor, dtype=torch.bfloat16) -> torch.Tensor:
+    """code * 2^(e - 127): exact in bf16."""
+    sc = (scales.to(torch.int32) << 23).view(torch.float32)
+    return (codes.view(torch.float8_e4m3fn).float() * sc.unsqueeze(-1)).to(dtype)
+
+
+def fake_quant_kv_fp8(x: torch.Tensor) -> torch.Tensor:
+    """dequant(quant(x)) in x's dtype: what an fp8 KV cache returns for a written row."""
+    return dequant_kv_fp8(*quant_kv_fp8(x), dtype=x.dtype)
+
+
+def _scatter_cache_f8(cache: KVF8, slots, rows):
+    """rows [T, nkv, D] bf16 -> quantized into cache[page, :, off] for slots >= 0."""
+    ps = cache.codes.shape[2]
+    valid = slots >= 0
+    if not bool(valid.any()):
+        return
+    s = slots[valid]
+    page, off = s // ps, s % ps
+    q, e = quant_kv_fp8(rows[valid])
+    cache.codes[page, :, off, :] = q
+    cache.scales[page, :, off] = e
+
+
+def rope_kv_write_f8(qkv, positions, cos, sin, k_cache: KVF8, v_cache: KVF8, slots, nh, nkv):
+    """``rope_kv_write`` on an fp8 cache: k is rotated, rounded to bf16, then quantized per head."""
+    T = qkv.shape[0]
+    D = k_cache.shape[-1]
+    view = qkv[:, : (nh + 2 * nkv) * D].view(T, nh + 2 * nkv, D)
+    c, s = cos[positions.long()], sin[positions.long()]
+    q = _rotate(view[:, :nh], c, s).to(qkv.dtype)
+    k = _rotate(view[:, nh : nh + nkv], c, s).to(qkv.dtype)
+    v = view[:, nh + nkv :]
+    view[:, :nh] = q
+    _scatter_cache_f8(k_cache, slots, k)
+    _scatter_cache_f8(v_cache, slots, v)
+
+
+def paged_attention_f8(q, k_cache: KVF8, v_cache: KVF8, block_tables, q_seq, q_ctx, nh, nkv, scale, out=None):
+    """Dequantize, then ``paged_attention``."""
+    return paged_attention(q, k_cache.dequant(torch.float32), v_cache.dequant(torch.float32), block_tables, q_seq,
+                           q_ctx, nh, nkv, scale, out=out)
+
+
 def embedding(ids, table, out=None):
     y = table[ids.long()]
     if out is not None:

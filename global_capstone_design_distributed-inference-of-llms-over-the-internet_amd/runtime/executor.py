@@ -34,7 +34,7 @@ from .. import native, ops
 from ..ops import moe
 from ..models.config import ModelConfig
 from ..models.weights import StageWeights
-from .kv_cache import PagedKVCache
+from .kv_cache import KV_DTYPES, PagedKVCache
 from .session import SessionManager, SessionState
 
 logger = logging.getLogger(__name__)
@@ -133,11 +133,21 @@ class StageExecutor:
                  page_size: int = 64, max_sessions: int = 256, max_seq_len: Optional[int] = None,
                  kv_cache_bytes: Optional[int] = None, kv_fraction: float = 0.9, use_graphs: Optional[bool] = None,
                  graph_max_batch: int = 256, max_tokens_per_step: int = 8192, offload: bool = False,
-                 keep_layers_on_gpu: int = 0, tp=None, warmup: Optional[bool] = None):
+                 keep_layers_on_gpu: int = 0, tp=None, warmup: Optional[bool] = None,
+                 kv_cache_dtype: str = "bf16"):
         """``tp``: a ``parallel.tensor_parallel.TPGroup`` when ``weights`` is a tensor-parallel
         shard (``cfg`` is then the shard config); partial sums are all-reduced after the
-        o and down projections."""
+        o and down projections.  ``kv_cache_dtype="fp8"``: e4m3 pages + e8m0 row scales
+        (runtime/kv_cache.py); every attention step then runs the flash-decoding kernel's fp8 form."""
         cfg.validate()
+        if kv_cache_dtype not in KV_DTYPES:
+            raise ValueError(f"kv_cache_dtype must be one of {KV_DTYPES}, got {kv_cache_dtype!r}")
+        if kv_cache_dtype == "fp8" and cfg.model_type == "gpt2":
+            raise ValueError("the fp8 KV cache needs the RoPE attention path: GPT-2 keeps a bf16 cache")
+        if kv_cache_dtype == "fp8" and cfg.head_dim not in (64, 128):
+            raise ValueError(f"the fp8 KV cache supports head_dim 64 and 128, got {cfg.head_dim}")
+        self.kv_cache_dtype = kv_cache_dtype
+        self._kv_fp8 = kv_cache_dtype == "fp8"
         if offload and cfg.is_moe:
             # the streamed slot layers carry only the per-path projection fields; the MoE MLP
             # also reads the router and per-expert row-major weights.  Mixtral-8x7B (93 GB bf16)
@@ -166,10 +176,12 @@ class StageExecutor:
                                                   cfg.rope_scaling)
         if kv_cache_bytes is None:
             kv_cache_bytes = PagedKVCache.auto_budget_bytes(self.device, fraction=kv_fraction)
-        num_pages = PagedKVCache.pages_for_bytes(kv_cache_bytes, self.n_layers, self.nkv, self.D, page_size)
+        num_pages = PagedKVCache.pages_for_bytes(kv_cache_bytes, self.n_layers, self.nkv, self.D, page_size,
+                                                 kv_dtype=kv_cache_dtype)
         max_useful = max_sessions * math.ceil(self.max_seq_len / page_size)
         num_pages = max(1, min(num_pages, max_useful))
-        self.cache = PagedKVCache(self.n_layers, num_pages, self.nkv, self.D, page_size, dtype, self.device)
+        self.cache = PagedKVCache(self.n_layers, num_pages, self.nkv, self.D, page_size, dtype, self.device,
+                                  kv_dtype=kv_cache_dtype)
         self.sessions = SessionManager(self.cache, max_sessions, self.max_seq_len)
         self.use_graphs = (self.device.type == "cuda") if use_graphs is None else bool(use_graphs)
         self.use_graphs = self.use_graphs and self.device.type == "cuda" and cfg.model_type != "gpt2" and \
@@ -209,7 +221,8 @@ class StageExecutor:
         self._attn_mfma_gqa = self._attn_mfma_prefill and self.nh // self.nkv >= 4
         # decode steps of GQA models on the MFMA kernel (a lab script may flip this before the
         # first decode step to A/B the flash-decoding kernel)
-        self.gqa_decode_mfma = self._attn_mfma_gqa
+        # (an fp8 KV cache has the flash-decoding kernel only: no MFMA GQA decode, no MX epilogue)
+        self.gqa_decode_mfma = self._attn_mfma_gqa and not self._kv_fp8
         # prefill: up to 4 query blocks of a sequence per workgroup share each K/V step
         # (csrc/attention_mfma.hip attn_mfma_grp_kernel)
         self._attn_grouped = True
@@ -516,8 +529,12 @@ class StageExecutor:
 
     def _attend(self, qkv, kc, vc, q_seq, q_ctx, out, ws, ps, np_, packed, qblocks, max_ctx):
         """Paged attention: MFMA flash attention for prefill blocks (``qblocks``) and GQA decode,
-        else the flash-decoding kernel."""
+        else the flash-decoding kernel - which is also the one kernel of an fp8 KV cache: its
+        prefill blocks run as per-query causal rows (``qblocks`` and the FA blocks are ignored)."""
         table = self.sessions.table_dev
+        if self._kv_fp8:
+            return ops.paged_attention(qkv, kc, vc, table, q_seq, q_ctx, self.nh, self.nkv, self.scale, out=out,
+                                       workspace=ws, part_size=ps, num_parts=np_, packed=packed)
         if qblocks is None and self.gqa_decode_mfma and self.device.type == "cuda":
             T = qkv.shape[0]
             ps2 = 128 * math.ceil(ps / 128)
@@ -554,7 +571,8 @@ class StageExecutor:
         ``qkv_part``: q / k / v as the qkv GEMM's split-K slabs (decode RoPE paths only).  ``mx_out``:
         (ax, as_) MX buffers the GQA kernel writes instead of ``out`` when it can (one part, packed,
         head_dim 128); it then appends True to ``mx_used``."""
-        if decode and qblocks is None and self._fuse_rope and self.gqa_decode_mfma and self.device.type == "cuda":
+        if decode and qblocks is None and self._fuse_rope and self.gqa_decode_mfma and not self._kv_fp8 and \
+                self.device.type == "cuda":
             T = qkv.shape[0]
             ps2 = 128 * math.ceil(ps / 128)
             np2 = max(1, math.ceil(ps * np_ / ps2))
@@ -566,7 +584,7 @@ class StageExecutor:
                                            out=out, workspace=ws, part_size=ps2, num_parts=np2, packed=packed,
                                            qkv_part=qkv_part, mx_out=mx)
         if decode and qblocks is None and self._fuse_rope and not (
-                self.gqa_decode_mfma and self.device.type == "cuda"):
+                self.gqa_decode_mfma and not self._kv_fp8 and self.device.type == "cuda"):
             return ops.paged_attention_rope(qkv, kc, vc, self.sessions.table_dev, q_seq, q_ctx, positions, self.cos,
                                             self.sin, slots, self.nh, self.nkv, self.scale, out=out, workspace=ws,
                                             part_size=ps, num_parts=np_, packed=packed, qkv_part=qkv_part)
@@ -660,7 +678,8 @@ class StageExecutor:
             # W8A8-MX o projection: the attention epilogue writes the MX activation (GQA decode)
             Q = cfg.q_dim
             mx_o = None
-            if (self._mx and decode and qblocks is None and T <= 64 and self.gqa_decode_mfma and self._fuse_rope and
+            if (self._mx and decode and qblocks is None and T <= 64 and self.gqa_decode_mfma and not self._kv_fp8 and
+                    self._fuse_rope and
                     ops.rwk_split(T, H, Q, 2) > 0):
                 mx_o = (e(f"mx_ax{Q}", (16 * ((T + 15) // 16) * Q,), torch.uint8), e(f"mx_as{Q}", (2 * Q,), torch.uint8))
             for li, L in self._iter_layers(_PACKED_FIELDS):

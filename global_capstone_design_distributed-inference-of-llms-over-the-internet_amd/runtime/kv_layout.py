@@ -19,6 +19,8 @@ from typing import List, Optional, Sequence, Tuple
 
 import torch
 
+from ..ops.reference import dequant_kv_fp8, quant_kv_fp8
+
 KV = Tuple[torch.Tensor, torch.Tensor]
 
 
@@ -49,9 +51,13 @@ def export_session_kv(cache, session, layers: Optional[Sequence[int]] = None,
     npg = -(-t // ps)
     idx = torch.tensor(session.pages[:npg], dtype=torch.long, device=cache.device)
     out = []
+    f8 = getattr(cache, "is_fp8", False)
     for l in _layer_ids(cache, layers):
         kk = cache.k[l].index_select(0, idx)  # [P, kvh, ps, hd]
         vv = cache.v[l].index_select(0, idx)
+        if f8:  # fp8 pages leave as their (exact) bf16 values, same dense layout
+            kk = dequant_kv_fp8(kk, cache.k_scale[l].index_select(0, idx), cache.dtype)
+            vv = dequant_kv_fp8(vv, cache.v_scale[l].index_select(0, idx), cache.dtype)
         kk = kk.permute(1, 0, 2, 3).reshape(cache.nkv, npg * ps, cache.head_dim)[:, :t]
         vv = vv.permute(1, 0, 2, 3).reshape(cache.nkv, npg * ps, cache.head_dim)[:, :t]
         out.append((kk.unsqueeze(0).contiguous(), vv.unsqueeze(0).contiguous()))
@@ -79,6 +85,14 @@ def import_session_kv(sessions, sid: str, kv: Sequence[KV], max_length: Optional
     for l, (k, v) in enumerate(kv):
         if k.shape != (1, cache.nkv, t, cache.head_dim) or v.shape != k.shape:
             raise ValueError(f"layer {l}: bad kv shape {tuple(k.shape)}")
+        if getattr(cache, "is_fp8", False):  # quantize per (token, kv head) row on the way in
+            for src, dst, dsc in ((k, cache.k[l], cache.k_scale[l]), (v, cache.v[l], cache.v_scale[l])):
+                pad = torch.zeros(cache.nkv, npg * ps, cache.head_dim, dtype=cache.dtype, device=dst.device)
+                pad[:, :t] = src[0].to(device=dst.device, dtype=cache.dtype)
+                q, e = quant_kv_fp8(pad)
+                dst.index_copy_(0, idx, q.view(cache.nkv, npg, ps, cache.head_dim).permute(1, 0, 2, 3))
+                dsc.index_copy_(0, idx, e.view(cache.nkv, npg, ps).permute(1, 0, 2))
+            continue
         for src, dst in ((k, cache.k[l]), (v, cache.v[l])):
             pad = torch.zeros(cache.nkv, npg * ps, cache.head_dim, dtype=dst.dtype, device=dst.device)
             pad[:, :t] = src[0].to(device=dst.device, dtype=dst.dtype)

@@ -146,6 +146,9 @@ class ThroughputCache:
         # keys the cache by quant type too); unquantized keys keep their form
         quant = getattr(executor, "quant_type", "none")
         q = "" if quant in (None, "none") else f"|{quant}"
+        # (so does an fp8 KV cache: its attention reads half the bytes, on another kernel)
+        kvd = getattr(executor, "kv_cache_dtype", "bf16")
+        q += "" if kvd in (None, "bf16") else f"|kv{kvd}"
         return f"{executor.cfg.name}|{executor.start}-{executor.end}|{executor.dtype}|{name}|b{int(batch)}{q}"
 
     def get(self, key: str) -> Optional[dict]:

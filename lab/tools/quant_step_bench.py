@@ -4,6 +4,9 @@ synthetic Llama-2-7B weights (all 32 blocks, embeddings and head on one GPU), ba
 for quant_type none / fp8 / mxfp4.  Per case: prefill, warm-up decode steps (graph capture, the
 start-up autotuners), then HIP events around ``--steps`` (>= 20) replayed steps; the median of
 ``--windows`` such windows is reported with their min / max.  One JSON line per case.
+``--kv_cache_dtype bf16,fp8`` runs every case per KV cache format; ``--synthetic_kv`` fills the
+prompt's KV pages with random values through ``import_session_kv`` instead of prefilling (long
+prompts: the decode step's time does not depend on what the pages hold).
 
     python lab/tools/quant_step_bench.py --batches 1,64 --steps 32
 """
@@ -20,22 +23,33 @@ from src import ops  # noqa: E402
 from src.models.config import resolve_model  # noqa: E402
 from src.models.weights import random_stage_weights  # noqa: E402
 from src.runtime.executor import StageExecutor  # noqa: E402
+from src.runtime.kv_layout import import_session_kv  # noqa: E402
 
 
-def run_case(cfg, quant, batch, a, dev):
+def run_case(cfg, quant, batch, a, dev, kv_dtype="bf16"):
     w = random_stage_weights(cfg, 0, cfg.num_hidden_layers, has_embed=True, has_head=True, device=dev, seed=0,
                              quant_type=quant)
     total = a.prompt_len + a.warmup + a.windows * a.steps + 8
     ex = StageExecutor(cfg, w, dev, max_sessions=batch + 8, max_seq_len=max(256, total),
                        kv_cache_bytes=max(1 << 30, 2 * batch * total * cfg.kv_bytes_per_token_per_layer(2)
                                           * cfg.num_hidden_layers),
-                       use_graphs=True, graph_max_batch=max(batch, 1))
+                       use_graphs=True, graph_max_batch=max(batch, 1),
+                       **({"kv_cache_dtype": kv_dtype} if kv_dtype != "bf16" else {}))
     gen = torch.Generator(device=dev).manual_seed(1)
     seqs = [(f"s{i}", a.prompt_len) for i in range(batch)]
-    ids = torch.randint(0, cfg.vocab_size, (batch * a.prompt_len,), device=dev, generator=gen)
-    logits = ex.forward(seqs, ids, reset=[True] * batch)
+    if a.synthetic_kv:
+        shape = (1, cfg.num_key_value_heads, a.prompt_len, cfg.head_dim)
+        kv = [tuple(torch.randn(shape, device=dev, generator=gen).to(torch.bfloat16) for _ in range(2))
+              for _ in range(cfg.num_hidden_layers)]
+        for s, _ in seqs:
+            import_session_kv(ex.sessions, s, kv)
+        del kv
+        tok = torch.randint(0, cfg.vocab_size, (batch,), device=dev, generator=gen)
+    else:
+        ids = torch.randint(0, cfg.vocab_size, (batch * a.prompt_len,), device=dev, generator=gen)
+        logits = ex.forward(seqs, ids, reset=[True] * batch)
+        tok = torch.argmax(logits.float(), -1)
     step = [(s, 1) for s, _ in seqs]
-    tok = torch.argmax(logits.float(), -1)
 
     def one(tok):
         return torch.argmax(ex.forward(step, tok).float(), -1)
@@ -53,7 +67,8 @@ def run_case(cfg, quant, batch, a, dev):
         e1.synchronize()
         ms.append(e0.elapsed_time(e1) / a.steps)
     path = "w4a16" if ex._w4 else ("w8a16" if ex._w8 else "bf16")
-    row = {"model": cfg.name, "quant_type": quant, "batch": batch, "prompt_len": a.prompt_len, "steps": a.steps,
+    row = {"model": cfg.name, "quant_type": quant, "kv_cache_dtype": kv_dtype, "synthetic_kv": bool(a.synthetic_kv),
+           "batch": batch, "prompt_len": a.prompt_len, "steps": a.steps,
            "windows": a.windows, "ms_per_step": round(statistics.median(ms), 4), "min": round(min(ms), 4),
            "max": round(max(ms), 4), "path": path, "fused_norm": bool(ex._fused),
            "weight_gib": round(w.nbytes() / 2 ** 30, 3)}
@@ -71,6 +86,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=8)
     ap.add_argument("--steps", type=int, default=32)
     ap.add_argument("--windows", type=int, default=5)
+    ap.add_argument("--kv_cache_dtype", default="bf16", help="comma-separated: bf16, fp8")
+    ap.add_argument("--synthetic_kv", action="store_true")
     a = ap.parse_args()
     if a.steps < 20:
         raise SystemExit("--steps must be at least 20")
@@ -79,7 +96,8 @@ def main():
     cfg = resolve_model(a.model)
     for quant in a.quants.split(","):
         for batch in [int(b) for b in a.batches.split(",")]:
-            print(json.dumps(run_case(cfg, quant, batch, a, dev)), flush=True)
+            for kvd in a.kv_cache_dtype.split(","):
+                print(json.dumps(run_case(cfg, quant, batch, a, dev, kvd)), flush=True)
 
 
 if __name__ == "__main__":
