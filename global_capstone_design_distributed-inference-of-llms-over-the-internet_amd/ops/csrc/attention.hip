@@ -517,15 +517,14 @@ __global__ void paged_attn_reduce_kernel(const float* __restrict__ part_o, const
 }
 
 template <int D, int NREP, int NW, bool F8>
-static void launch_attn_nw(const void* q, int64_t q_stride, const void* kc, const void* vc, const int32_t* bt,
-                           int bt_stride, const int32_t* q_seq, const int32_t* q_ctx, void* out, float* ws_o,
-                           float* ws_ml, int T, int nkv, int nh, int page_log2, int PS, int NP, float scale_log2,
-                           int packed_mt, const RopeFuse& rf, int* cnt, KvF8 f8, hipStream_t stream) {
+static void launch_attn_nw(const AttnArgs& a, int page_log2, const RopeFuse& rf, int* cnt, KvF8 f8,
+                           hipStream_t stream) {
   const size_t lds = (size_t)(NW * NREP * D + 2 * NW * NREP + 4) * sizeof(float);
   auto go = [&](auto kern) {
-    hipLaunchKernelGGL(kern, dim3(NP, nh / NREP, T), dim3(64 * NW), lds, stream, (const bf16_t*)q, q_stride,
-                       (const bf16_t*)kc, (const bf16_t*)vc, bt, bt_stride, q_seq, q_ctx, (bf16_t*)out, ws_o, ws_ml,
-                       nkv, nh, page_log2, PS, NP, scale_log2, packed_mt, rf, cnt, f8);
+    hipLaunchKernelGGL(kern, dim3(a.NP, a.nh / NREP, a.T), dim3(64 * NW), lds, stream, (const bf16_t*)a.q, a.q_stride,
+                       (const bf16_t*)a.kc, (const bf16_t*)a.vc, a.bt, a.bt_stride, a.q_seq, a.q_ctx, (bf16_t*)a.out,
+                       a.workspace, attn_ws_ml(a), a.nkv, a.nh, page_log2, a.PS, a.NP, attn_scale_log2(a), a.packed_mt,
+                       rf, cnt, f8);
   };
   if (rf.pos) go(paged_attn1_kernel<D, NREP, true, NW, true, 4, F8>);
   else go(paged_attn1_kernel<D, NREP, false, NW, true, 4, F8>);
@@ -537,65 +536,43 @@ static void launch_attn_nw(const void* q, int64_t q_stride, const void* kc, cons
 // grid 4-wave ones.  (2-wave workgroups, the 64-session step's 2048 in one round of residency,
 // measured 36.5 -> 38.1 us cold at 64 x 170: profiles/r6attn.)
 template <int D, int NREP, bool F8>
-static void launch_attn(const void* q, int64_t q_stride, const void* kc, const void* vc, const int32_t* bt,
-                        int bt_stride, const int32_t* q_seq, const int32_t* q_ctx, void* out, float* ws_o,
-                        float* ws_ml, int T, int nkv, int nh, int page_log2, int PS, int NP, float scale_log2,
-                        int packed_mt, const RopeFuse& rf, int* cnt, KvF8 f8, hipStream_t stream) {
-  const int64_t wgs = (int64_t)NP * (nh / NREP) * T;
+static void launch_attn(const AttnArgs& a, int page_log2, const RopeFuse& rf, int* cnt, KvF8 f8, hipStream_t stream) {
+  const int64_t wgs = (int64_t)a.NP * (a.nh / NREP) * a.T;
   const int nw = MP_ATTN_NW ? MP_ATTN_NW : (wgs <= 128 ? 8 : 4);
-#define MP_ATTN_NW_CASE(W)                                                                                     \
-  if (nw == W) {                                                                                               \
-    launch_attn_nw<D, NREP, W, F8>(q, q_stride, kc, vc, bt, bt_stride, q_seq, q_ctx, out, ws_o, ws_ml, T, nkv, \
-                                   nh, page_log2, PS, NP, scale_log2, packed_mt, rf, cnt, f8, stream);         \
-    return;                                                                                                    \
-  }
-  MP_ATTN_NW_CASE(8)
-  MP_ATTN_NW_CASE(4)
-#undef MP_ATTN_NW_CASE
+  if (nw == 8) launch_attn_nw<D, NREP, 8, F8>(a, page_log2, rf, cnt, f8, stream);
+  else if (nw == 4) launch_attn_nw<D, NREP, 4, F8>(a, page_log2, rf, cnt, f8, stream);
 }
 
 }  // namespace mp
 
-// kc / vc: bf16 pages, or with scales (ks, vs) the fp8 cache's code pages (kv_f8.h)
-static int paged_attention_launch(const void* q, int64_t q_stride, const void* kc, const void* vc,
-                                  const int32_t* bt, int bt_stride, const int32_t* q_seq, const int32_t* q_ctx,
-                                  void* out, float* workspace, int T, int nh, int nkv, int D, int page_size,
-                                  int PS, int NP, float scale, int packed_mt, const int64_t* rope_pos,
-                                  const float* cos_t, const float* sin_t, const int64_t* slots, int* counters,
-                                  int n_counters, const void* qkv_part_v, mp::KvF8 f8, hipStream_t stream) {
+// a.kc / a.vc: bf16 pages, or with scales (a.ks, a.vs) the fp8 cache's e4m3 code pages (kv_f8.h;
+// the scales are written too on the RoPE form)
+extern "C" int mp_paged_attention(const mp::AttnArgs* args, int* counters, int n_counters, hipStream_t stream) {
   (void)hipGetLastError();  // an earlier non-mpamd HIP call's stale error is not this launch's
   using namespace mp;
-  RopeFuse rf{rope_pos, cos_t, sin_t, slots, (bf16_t*)const_cast<void*>(kc), (bf16_t*)const_cast<void*>(vc),
-              QkvPart{nullptr, 0, 0, 0, nullptr, 0.f, 0.f}};
-  const QkvPart* qkv_part = static_cast<const QkvPart*>(qkv_part_v);  // layout mirrored by bindings.cpp
-  if (qkv_part != nullptr && qkv_part->part != nullptr) {
-    if (rope_pos == nullptr || qkv_part->S < 1) return -4;  // partials only on the fused RoPE decode path
-    rf.qp = *qkv_part;
+  const AttnArgs& a = *args;
+  RopeFuse rf{a.rope_pos, a.cos_t, a.sin_t, a.slots, (bf16_t*)a.kc, (bf16_t*)a.vc, QkvPart{}};
+  if (a.qp.part != nullptr) {
+    if (a.rope_pos == nullptr || a.qp.S < 1) return -4;  // partials only on the fused RoPE decode path
+    rf.qp = a.qp;
   }
-  if (T == 0) return 0;
-  if (nh % nkv != 0 || PS % 64 != 0 || PS > 2048 || NP < 1) return -1;
-  int page_log2 = 0;
-  while ((1 << page_log2) < page_size) ++page_log2;
-  if ((1 << page_log2) != page_size) return -2;
-  const int nrep = nh / nkv;
-  const float scale_log2 = scale * 1.4426950408889634f;
-  float* ws_o = workspace;
-  float* ws_ml = workspace + (int64_t)T * nh * NP * D;
+  const KvF8 f8{(uint8_t*)a.ks, (uint8_t*)a.vs};
+  if (a.T == 0) return 0;
+  if (a.nh % a.nkv != 0 || a.PS % 64 != 0 || a.PS > 2048 || a.NP < 1) return -1;
+  const int page_log2 = attn_page_log2(a);
+  if (page_log2 < 0) return -2;
+  const int nrep = a.nh / a.nkv;
   // heads per workgroup: at most 4 of a GQA group (register budget), a divisor of nrep
   constexpr int hpb_max = 4;
   int hpb = 1;
   while (hpb * 2 <= hpb_max && nrep % (hpb * 2) == 0) hpb *= 2;
   // in-launch combine when the caller's zeroed counters cover every (query, head group)
-  int* cnt = (NP > 1 && counters != nullptr && (int64_t)T * (nh / hpb) <= n_counters) ? counters : nullptr;
-#define MP_ATTN_CASE(DD, RR)                                                                                  \
-  if (D == DD && hpb == RR) {                                                                                 \
-    if (f8.ks != nullptr)                                                                                     \
-      launch_attn<DD, RR, true>(q, q_stride, kc, vc, bt, bt_stride, q_seq, q_ctx, out, ws_o, ws_ml, T, nkv,   \
-                                nh, page_log2, PS, NP, scale_log2, packed_mt, rf, cnt, f8, stream);           \
-    else                                                                                                      \
-      launch_attn<DD, RR, false>(q, q_stride, kc, vc, bt, bt_stride, q_seq, q_ctx, out, ws_o, ws_ml, T, nkv,  \
-                                 nh, page_log2, PS, NP, scale_log2, packed_mt, rf, cnt, f8, stream);          \
-    goto launched;                                                                                            \
+  int* cnt = (a.NP > 1 && counters != nullptr && (int64_t)a.T * (a.nh / hpb) <= n_counters) ? counters : nullptr;
+#define MP_ATTN_CASE(DD, RR)                                                                  \
+  if (a.D == DD && hpb == RR) {                                                               \
+    if (f8.ks != nullptr) launch_attn<DD, RR, true>(a, page_log2, rf, cnt, f8, stream);       \
+    else launch_attn<DD, RR, false>(a, page_log2, rf, cnt, f8, stream);                       \
+    goto launched;                                                                            \
   }
   MP_ATTN_CASE(128, 1)
   MP_ATTN_CASE(128, 2)
@@ -606,35 +583,9 @@ static int paged_attention_launch(const void* q, int64_t q_stride, const void* k
 #undef MP_ATTN_CASE
   return -3;
 launched:
-  if (NP > 1 && cnt == nullptr) {
-    hipLaunchKernelGGL(paged_attn_reduce_kernel, dim3(T * nh), dim3(D), 0, stream, ws_o, ws_ml, (bf16_t*)out, NP,
-                       D, nh, packed_mt);
+  if (a.NP > 1 && cnt == nullptr) {
+    hipLaunchKernelGGL(paged_attn_reduce_kernel, dim3(a.T * a.nh), dim3(a.D), 0, stream, a.workspace, attn_ws_ml(a),
+                       (bf16_t*)a.out, a.NP, a.D, a.nh, a.packed_mt);
   }
   return (int)hipGetLastError();
-}
-
-extern "C" int mp_paged_attention(const void* q, int64_t q_stride, const void* kc, const void* vc,
-                                  const int32_t* bt, int bt_stride, const int32_t* q_seq, const int32_t* q_ctx,
-                                  void* out, float* workspace, int T, int nh, int nkv, int D, int page_size,
-                                  int PS, int NP, float scale, int packed_mt, const int64_t* rope_pos,
-                                  const float* cos_t, const float* sin_t, const int64_t* slots, int* counters,
-                                  int n_counters, const void* qkv_part_v, hipStream_t stream) {
-  return paged_attention_launch(q, q_stride, kc, vc, bt, bt_stride, q_seq, q_ctx, out, workspace, T, nh, nkv, D,
-                                page_size, PS, NP, scale, packed_mt, rope_pos, cos_t, sin_t, slots, counters,
-                                n_counters, qkv_part_v, mp::KvF8{nullptr, nullptr}, stream);
-}
-
-// The same launch on an fp8 KV cache: kc / vc uint8 e4m3 codes [pages, nkv, page, D], ks / vs their
-// e8m0 row scales [pages, nkv, page] (written too on the RoPE form).
-extern "C" int mp_paged_attention_f8(const void* q, int64_t q_stride, const void* kc, const void* vc, void* ks,
-                                     void* vs, const int32_t* bt, int bt_stride, const int32_t* q_seq,
-                                     const int32_t* q_ctx, void* out, float* workspace, int T, int nh, int nkv,
-                                     int D, int page_size, int PS, int NP, float scale, int packed_mt,
-                                     const int64_t* rope_pos, const float* cos_t, const float* sin_t,
-                                     const int64_t* slots, int* counters, int n_counters, const void* qkv_part_v,
-                                     hipStream_t stream) {
-  if (ks == nullptr || vs == nullptr) return -5;
-  return paged_attention_launch(q, q_stride, kc, vc, bt, bt_stride, q_seq, q_ctx, out, workspace, T, nh, nkv, D,
-                                page_size, PS, NP, scale, packed_mt, rope_pos, cos_t, sin_t, slots, counters,
-                                n_counters, qkv_part_v, mp::KvF8{(uint8_t*)ks, (uint8_t*)vs}, stream);
 }

@@ -300,29 +300,23 @@ __global__ void paged_attn_reduce_kernel(const float* __restrict__ part_o, const
 // Prefill blocks: fb_tok0[i] / fb_ntok[i] = first flat token / token count of block i (<= 32 x NW
 // / heads_per_block consecutive tokens of ONE sequence, ops.fa_blocks).  D = 128, page_size a
 // multiple of 64, heads_per_block = nh / nkv in {1, 2, 4, 8}; row-major output [T, nh * D].
-extern "C" int mp_attention_fa(const void* q, int64_t q_stride, const void* kc, const void* vc, const int32_t* bt,
-                               int bt_stride, const int32_t* q_seq, const int32_t* q_ctx, const int32_t* fb_tok0,
-                               const int32_t* fb_ntok, int NBF, void* out, float* workspace, int T, int nh, int nkv,
-                               int D, int page_size, int PS, int NP, float scale, int nw, int pair,
-                               hipStream_t stream) {
+extern "C" int mp_attention_fa(const mp::AttnArgs* args, const int32_t* fb_tok0, const int32_t* fb_ntok, int NBF,
+                               int nw, int pair, hipStream_t stream) {
   (void)hipGetLastError();  // an earlier non-mpamd HIP call's stale error is not this launch's
   using namespace mp;
-  if (NBF == 0 || T == 0) return 0;
-  if (D != 128 || nh % nkv != 0 || PS % 64 != 0 || NP < 1 || page_size % 64 != 0) return -1;
-  int page_log2 = 0;
-  while ((1 << page_log2) < page_size) ++page_log2;
-  if ((1 << page_log2) != page_size) return -2;
-  const int hb = nh / nkv;
+  const AttnArgs& a = *args;
+  if (NBF == 0 || a.T == 0) return 0;
+  if (a.D != 128 || a.nh % a.nkv != 0 || a.PS % 64 != 0 || a.NP < 1 || a.page_size % 64 != 0) return -1;
+  const int page_log2 = attn_page_log2(a);
+  if (page_log2 < 0) return -2;
+  const int hb = a.nh / a.nkv;
   pair = pair ? 1 : 0;
   const int nbp = pair ? (NBF + 1) / 2 : NBF;
-  const float scale_log2 = scale * 1.4426950408889634f;
-  float* ws_o = workspace;
-  float* ws_ml = workspace + (int64_t)T * nh * NP * D;
-#define MP_FA(HB_, NW_)                                                                                         \
-  hipLaunchKernelGGL((attn_fa_kernel<HB_, NW_>), dim3(nbp * (nh / HB_), NP), dim3(NW_ * 64), 0, stream,           \
-                     (const bf16_t*)q, q_stride, (const bf16_t*)kc, (const bf16_t*)vc, bt, bt_stride, q_seq, q_ctx, \
-                     fb_tok0, fb_ntok, NBF, (bf16_t*)out, (int64_t)nh * D, ws_o, ws_ml, nkv, nh, page_log2, PS, NP,  \
-                     scale_log2, pair)
+#define MP_FA(HB_, NW_)                                                                                          \
+  hipLaunchKernelGGL((attn_fa_kernel<HB_, NW_>), dim3(nbp * (a.nh / HB_), a.NP), dim3(NW_ * 64), 0, stream,      \
+                     (const bf16_t*)a.q, a.q_stride, (const bf16_t*)a.kc, (const bf16_t*)a.vc, a.bt, a.bt_stride, \
+                     a.q_seq, a.q_ctx, fb_tok0, fb_ntok, NBF, (bf16_t*)a.out, (int64_t)a.nh * a.D, a.workspace,   \
+                     attn_ws_ml(a), a.nkv, a.nh, page_log2, a.PS, a.NP, attn_scale_log2(a), pair)
 #define MP_FA_NW(HB_) \
   if (nw == 8) MP_FA(HB_, 8); else MP_FA(HB_, 4);
   switch (hb) {
@@ -334,8 +328,8 @@ extern "C" int mp_attention_fa(const void* q, int64_t q_stride, const void* kc, 
   }
 #undef MP_FA_NW
 #undef MP_FA
-  if (NP > 1)
-    hipLaunchKernelGGL(paged_attn_reduce_kernel, dim3(T * nh), dim3(D), 0, stream, ws_o, ws_ml, (bf16_t*)out, NP, D,
-                       nh, 0);
+  if (a.NP > 1)
+    hipLaunchKernelGGL(paged_attn_reduce_kernel, dim3(a.T * a.nh), dim3(a.D), 0, stream, a.workspace, attn_ws_ml(a),
+                       (bf16_t*)a.out, a.NP, a.D, a.nh, 0);
   return (int)hipGetLastError();
 }

@@ -603,21 +603,23 @@ __global__ __launch_bounds__(NWG * 64) void attn_mfma_grp_kernel(
 }
 
 template <int D, int HB>
-static void launch_attn_mfma(const void* q, int64_t q_stride, const void* kc, const void* vc, const int32_t* bt,
-                             int bt_stride, const int32_t* q_seq, const int32_t* q_ctx, const int32_t* qb_tok0,
-                             const int32_t* qb_ntok, int NB, void* out, float* ws_o, float* ws_ml, int nkv, int nh,
-                             int page_log2, int PS, int NP, float scale_log2, int packed_mt, const RopeFuseM& rf,
-                             const int32_t* sb_first, const int32_t* sb_n, int NSB, hipStream_t stream) {
+static void launch_attn_mfma(const AttnArgs& a, int page_log2, const RopeFuseM& rf, const int32_t* qb_tok0,
+                             const int32_t* qb_ntok, int NB, const int32_t* sb_first, const int32_t* sb_n, int NSB,
+                             hipStream_t stream) {
+  const bf16_t *q = (const bf16_t*)a.q, *kc = (const bf16_t*)a.kc, *vc = (const bf16_t*)a.vc;
+  float* ws_ml = attn_ws_ml(a);
+  const float scale_log2 = attn_scale_log2(a);
   if (sb_first != nullptr && NSB > 0 && rf.pos == nullptr) {
-    hipLaunchKernelGGL((attn_mfma_grp_kernel<D, HB, 8>), dim3(NSB, nh / HB, NP), dim3(512), 0, stream, (const bf16_t*)q,
-                       q_stride, (const bf16_t*)kc, (const bf16_t*)vc, bt, bt_stride, q_seq, q_ctx, qb_tok0, qb_ntok,
-                       sb_first, sb_n, (bf16_t*)out, ws_o, ws_ml, nkv, nh, page_log2, PS, NP, scale_log2, packed_mt);
+    hipLaunchKernelGGL((attn_mfma_grp_kernel<D, HB, 8>), dim3(NSB, a.nh / HB, a.NP), dim3(512), 0, stream, q,
+                       a.q_stride, kc, vc, a.bt, a.bt_stride, a.q_seq, a.q_ctx, qb_tok0, qb_ntok, sb_first, sb_n,
+                       (bf16_t*)a.out, a.workspace, ws_ml, a.nkv, a.nh, page_log2, a.PS, a.NP, scale_log2,
+                       a.packed_mt);
     return;
   }
   auto go = [&](auto kern) {
-    hipLaunchKernelGGL(kern, dim3(NB, nh / HB, NP), dim3(256), 0, stream, (const bf16_t*)q, q_stride,
-                       (const bf16_t*)kc, (const bf16_t*)vc, bt, bt_stride, q_seq, q_ctx, qb_tok0, qb_ntok,
-                       (bf16_t*)out, ws_o, ws_ml, nkv, nh, page_log2, PS, NP, scale_log2, packed_mt, rf);
+    hipLaunchKernelGGL(kern, dim3(NB, a.nh / HB, a.NP), dim3(256), 0, stream, q, a.q_stride, kc, vc, a.bt,
+                       a.bt_stride, a.q_seq, a.q_ctx, qb_tok0, qb_ntok, (bf16_t*)a.out, a.workspace, ws_ml, a.nkv,
+                       a.nh, page_log2, a.PS, a.NP, scale_log2, a.packed_mt, rf);
   };
   if (rf.pos && rf.qp.part) go(attn_mfma_kernel<D, HB, true, true>);
   else if (rf.pos) go(attn_mfma_kernel<D, HB, true, false>);
@@ -633,46 +635,35 @@ __global__ void paged_attn_reduce_kernel(const float* __restrict__ part_o, const
 // (<= 16 / heads_per_block, all from one sequence).  heads_per_block = min(nh / nkv, 16).
 // Superblocks (optional, prefill): sb_first[j] / sb_n[j] = runs of <= 8 consecutive query blocks
 // of one sequence, one workgroup each (attn_mfma_grp_kernel).
-extern "C" int mp_attention_mfma(const void* q, int64_t q_stride, const void* kc, const void* vc, const int32_t* bt,
-                                 int bt_stride, const int32_t* q_seq, const int32_t* q_ctx, const int32_t* qb_tok0,
-                                 const int32_t* qb_ntok, int NB, void* out, float* workspace, int T, int nh, int nkv,
-                                 int D, int page_size, int PS, int NP, float scale, int packed_mt,
-                                 const int64_t* rope_pos, const float* cos_t, const float* sin_t,
-                                 const int64_t* slots, const int32_t* sb_first, const int32_t* sb_n, int NSB,
-                                 const void* qkv_part_v, void* mx_ax, void* mx_as, hipStream_t stream) {
+extern "C" int mp_attention_mfma(const mp::AttnArgs* args, const int32_t* qb_tok0, const int32_t* qb_ntok, int NB,
+                                 const int32_t* sb_first, const int32_t* sb_n, int NSB, void* mx_ax, void* mx_as,
+                                 hipStream_t stream) {
   (void)hipGetLastError();  // an earlier non-mpamd HIP call's stale error is not this launch's
   using namespace mp;
-  RopeFuseM rf{rope_pos, cos_t, sin_t, slots, (bf16_t*)const_cast<void*>(kc), (bf16_t*)const_cast<void*>(vc),
-               QkvPart{nullptr, 0, 0, 0, nullptr, 0.f, 0.f}};
-  const QkvPart* qkv_part = static_cast<const QkvPart*>(qkv_part_v);  // layout mirrored by bindings.cpp
-  if (qkv_part != nullptr && qkv_part->part != nullptr) {
-    if (rope_pos == nullptr || qkv_part->S < 1) return -4;  // partials only on the fused RoPE decode path
-    rf.qp = *qkv_part;
+  const AttnArgs& a = *args;
+  RopeFuseM rf{a.rope_pos, a.cos_t, a.sin_t, a.slots, (bf16_t*)a.kc, (bf16_t*)a.vc, QkvPart{}};
+  if (a.qp.part != nullptr) {
+    if (a.rope_pos == nullptr || a.qp.S < 1) return -4;  // partials only on the fused RoPE decode path
+    rf.qp = a.qp;
   }
   if (mx_ax != nullptr) {  // MX output: the fused RoPE decode path, one part, packed rows, 128-dim heads
-    if (rope_pos == nullptr || NP != 1 || packed_mt <= 0 || D != 128 || mx_as == nullptr) return -7;
+    if (a.rope_pos == nullptr || a.NP != 1 || a.packed_mt <= 0 || a.D != 128 || mx_as == nullptr) return -7;
     rf.mx_ax = (uint8_t*)mx_ax;
     rf.mx_as = (uint8_t*)mx_as;
   }
-  if (NB == 0 || T == 0) return 0;
-  if (nh % nkv != 0 || PS % 128 != 0 || NP < 1 || page_size % 32 != 0) return -1;
-  int page_log2 = 0;
-  while ((1 << page_log2) < page_size) ++page_log2;
-  if ((1 << page_log2) != page_size) return -2;
-  const int nrep = nh / nkv;
+  if (NB == 0 || a.T == 0) return 0;
+  if (a.nh % a.nkv != 0 || a.PS % 128 != 0 || a.NP < 1 || a.page_size % 32 != 0) return -1;
+  const int page_log2 = attn_page_log2(a);
+  if (page_log2 < 0) return -2;
+  const int nrep = a.nh / a.nkv;
   // the whole GQA group of a kv head in one workgroup's MFMA rows (spreading a group's heads over
   // several workgroups that re-read the same K / V measured 1.6-2.7x slower, profiles/r4k)
   const int hb = nrep >= 16 ? 16 : nrep;
   if (nrep % hb) return -3;
-  const float scale_log2 = scale * 1.4426950408889634f;
-  float* ws_o = workspace;
-  float* ws_ml = workspace + (int64_t)T * nh * NP * D;
-#define MP_AM_CASE(DD, HH)                                                                                      \
-  if (D == DD && hb == HH) {                                                                                    \
-    launch_attn_mfma<DD, HH>(q, q_stride, kc, vc, bt, bt_stride, q_seq, q_ctx, qb_tok0, qb_ntok, NB, out, ws_o,  \
-                             ws_ml, nkv, nh, page_log2, PS, NP, scale_log2, packed_mt, rf, sb_first, sb_n, NSB, \
-                             stream);                                                                           \
-    goto launched;                                                                                              \
+#define MP_AM_CASE(DD, HH)                                                                                  \
+  if (a.D == DD && hb == HH) {                                                                              \
+    launch_attn_mfma<DD, HH>(a, page_log2, rf, qb_tok0, qb_ntok, NB, sb_first, sb_n, NSB, stream);          \
+    goto launched;                                                                                          \
   }
   MP_AM_CASE(128, 1)
   MP_AM_CASE(128, 2)
@@ -687,8 +678,8 @@ extern "C" int mp_attention_mfma(const void* q, int64_t q_stride, const void* kc
 #undef MP_AM_CASE
   return -4;
 launched:
-  if (NP > 1)
-    hipLaunchKernelGGL(paged_attn_reduce_kernel, dim3(T * nh), dim3(D), 0, stream, ws_o, ws_ml, (bf16_t*)out, NP, D,
-                       nh, packed_mt);
+  if (a.NP > 1)
+    hipLaunchKernelGGL(paged_attn_reduce_kernel, dim3(a.T * a.nh), dim3(a.D), 0, stream, a.workspace, attn_ws_ml(a),
+                       (bf16_t*)a.out, a.NP, a.D, a.nh, a.packed_mt);
   return (int)hipGetLastError();
 }

@@ -8,81 +8,10 @@
 #include <torch/library.h>
 
 #include <cmath>
+#include <tuple>
 #include <utility>
 
-extern "C" {
-int mp_rmsnorm(const void* x, int64_t x_stride, void* res, int64_t res_stride, const void* w, void* y,
-               int64_t y_stride, const int32_t* rows, int nrows, int H, float eps, int mode, int packed_mt,
-               void* ss_out, void* a8, float* a8_scale, const int64_t* gather, int64_t gather_n,
-               hipStream_t stream);
-int mp_rope_kv_write(void* qkv, int64_t qkv_stride, const int64_t* pos, const float* cos_t, const float* sin_t,
-                     void* kc, void* vc, const int64_t* slots, int T, int nh, int nkv, int D, int page_size,
-                     hipStream_t stream);
-int mp_kv_write(const void* k, int64_t k_stride, const void* v, int64_t v_stride, void* kc, void* vc,
-                const int64_t* slots, int T, int nkv, int D, int page_size, hipStream_t stream);
-int mp_paged_attention(const void* q, int64_t q_stride, const void* kc, const void* vc, const int32_t* bt,
-                       int bt_stride, const int32_t* q_seq, const int32_t* q_ctx, void* out, float* workspace, int T,
-                       int nh, int nkv, int D, int page_size, int PS, int NP, float scale, int packed_mt,
-                       const int64_t* rope_pos, const float* cos_t, const float* sin_t, const int64_t* slots,
-                       int* counters, int n_counters, const void* qkv_part, hipStream_t stream);
-int mp_paged_attention_f8(const void* q, int64_t q_stride, const void* kc, const void* vc, void* ks, void* vs,
-                          const int32_t* bt, int bt_stride, const int32_t* q_seq, const int32_t* q_ctx, void* out,
-                          float* workspace, int T, int nh, int nkv, int D, int page_size, int PS, int NP, float scale,
-                          int packed_mt, const int64_t* rope_pos, const float* cos_t, const float* sin_t,
-                          const int64_t* slots, int* counters, int n_counters, const void* qkv_part,
-                          hipStream_t stream);
-int mp_rope_kv_write_f8(void* qkv, int64_t qkv_stride, const int64_t* pos, const float* cos_t, const float* sin_t,
-                        void* kc, void* vc, void* ks, void* vs, const int64_t* slots, int T, int nh, int nkv, int D,
-                        int page_size, hipStream_t stream);
-int mp_embedding(const int64_t* ids, const void* table, void* out, int T, int H, int64_t vocab, hipStream_t stream);
-int mp_swiglu(const void* gu, void* out, int64_t T, int F, hipStream_t stream);
-int mp_add(const void* a, const void* b, void* y, int64_t n, hipStream_t stream);
-int mp_argmax(const void* logits, int64_t stride, int R, int V, int64_t* out, hipStream_t stream);
-int mp_sample(const void* logits, int64_t stride, int R, int V, const float* temps, const float* top_ps,
-              const int32_t* top_ks, const float* rep_pens, int32_t* recent, int recent_stride, int32_t* recent_len,
-              const int64_t* seeds, float* ws, int64_t* out, int update, hipStream_t stream);
-int64_t mp_gemm_workspace_bytes();
-int64_t mp_gemm_slab_offset();
-int mp_gemm_rwk_split(int M, int N, int K, int f8);
-int mp_attention_mfma(const void* q, int64_t q_stride, const void* kc, const void* vc, const int32_t* bt, int bt_stride,
-                      const int32_t* q_seq, const int32_t* q_ctx, const int32_t* qb_tok0, const int32_t* qb_ntok, int NB,
-                      void* out, float* workspace, int T, int nh, int nkv, int D, int page_size, int PS, int NP,
-                      float scale, int packed_mt, const int64_t* rope_pos, const float* cos_t, const float* sin_t,
-                      const int64_t* slots, const int32_t* sb_first, const int32_t* sb_n, int NSB,
-                      const void* qkv_part, void* mx_ax, void* mx_as, hipStream_t stream);
-int mp_attention_fa(const void* q, int64_t q_stride, const void* kc, const void* vc, const int32_t* bt, int bt_stride,
-                    const int32_t* q_seq, const int32_t* q_ctx, const int32_t* fb_tok0, const int32_t* fb_ntok, int NBF,
-                    void* out, float* workspace, int T, int nh, int nkv, int D, int page_size, int PS, int NP,
-                    float scale, int nw, int pair, hipStream_t stream);
-int mp_quant_act_fp8(const void* ap, void* a8, float* scale, float* part, int M, int K, hipStream_t stream);
-int mp_gemm_fp8(const void* a8, const float* as, const void* wq, const float* ws, void* y, int64_t ys, const void* res,
-                int64_t rs, int M, int N, int K, int epilogue, int out_packed, int kind, float* part,
-                int64_t part_bytes, hipStream_t stream);
-int64_t mp_gemm_slab_bytes();
-void mp_fp8_set_kernel(int kind);
-int mp_gemm_rw_ok(int M, int N, int K, int epilogue, int out_packed);
-int mp_gemm_t2d_ok(int M, int N, int K, int epilogue, int out_packed, int with_ws);
-int mp_quant_rows_fp8(const void* x, int64_t xs, void* a8, float* scale, int M, int K, hipStream_t stream);
-int mp_gemm_bf16(const void* x, int64_t x_stride, const void* w, void* y, int64_t y_stride, const void* res,
-                 int64_t res_stride, int M, int N, int K, int epilogue, int flags, void* ws, const int* gate,
-                 void* ap, void* ss_out, void* ss_zero, const void* ss_in, float inv_k, float eps,
-                 hipStream_t stream);
-int mp_gemm_ss_elems();
-int mp_gemm_w8(const void* x, const void* wq, const float* wsc, void* y, int64_t y_stride, const void* res,
-               int64_t res_stride, int M, int N, int K, int epilogue, int flags, void* ws, void* ap, void* ss_out,
-               void* ss_zero, const void* ss_in, float inv_k, float eps, hipStream_t stream);
-int mp_gemm_w4(const void* x, const void* w4, const void* s4, void* y, int64_t y_stride, const void* res,
-               int64_t res_stride, int M, int N, int K, int epilogue, int flags, void* ap, void* ss_out, void* ss_zero,
-               const void* ss_in, float inv_k, float eps, hipStream_t stream);
-int mp_gemm_w4_ok(int M, int N, int K, int epilogue);
-int mp_dequant_w4(const void* w4, const void* s4, void* w, int N, int K, hipStream_t stream);
-int mp_pack_act(const void* x, int64_t xs, void* ap, int M, int K, hipStream_t stream);
-int mp_quant_mx(const void* ap, void* ax, void* as, int M, int K, hipStream_t stream);
-int mp_gemm_mx(const void* ax, const void* as, const void* wq, const float* wsc, void* y, int64_t y_stride,
-               const void* res, int64_t res_stride, int M, int N, int K, int epilogue, int flags, void* ws, void* ap,
-               void* ss_out, void* ss_zero, const void* ss_in, float inv_k, float eps, hipStream_t stream);
-int mp_pack_weight(const void* w, void* wp, int N, int K, hipStream_t stream);
-}
+#include "mp_api.h"
 
 namespace {
 
@@ -228,16 +157,10 @@ void rmsnorm(const at::Tensor& x, at::Tensor& residual, const at::Tensor& w, at:
                "rmsnorm");
 }
 
-void rope_kv_write(at::Tensor& qkv, const at::Tensor& positions, const at::Tensor& cos, const at::Tensor& sin,
-                   at::Tensor& k_cache, at::Tensor& v_cache, const at::Tensor& slots, int64_t nh, int64_t nkv) {
-  check_bf16_cuda(qkv, "qkv");
-  check_rows(qkv, "qkv");
-  check_bf16_cuda(k_cache, "k_cache");
-  check_bf16_cuda(v_cache, "v_cache");
-  MP_CHECK(k_cache.dim() == 4 && k_cache.is_contiguous() && v_cache.is_contiguous(), "cache [pages, nkv, page, D]");
-  MP_CHECK(k_cache.sizes() == v_cache.sizes(), "k/v cache shapes differ");
-  const int D = k_cache.size(3), page = k_cache.size(2);
-  MP_CHECK(k_cache.size(1) == nkv, "cache kv heads");
+// RoPE operands of the fused qkv rows [T, (nh + 2 nkv) * D]: rotary positions and cache slots int64 [T],
+// cos / sin tables fp32 [max_pos, D / 2]
+inline void check_rope(const at::Tensor& qkv, const at::Tensor& positions, const at::Tensor& cos,
+                       const at::Tensor& sin, const at::Tensor& slots, int64_t nh, int64_t nkv, int D) {
   MP_CHECK(qkv.size(1) == (nh + 2 * nkv) * D, "qkv width");
   const int T = qkv.size(0);
   MP_CHECK(positions.scalar_type() == at::kLong && positions.numel() == T && positions.is_contiguous(), "positions");
@@ -245,14 +168,18 @@ void rope_kv_write(at::Tensor& qkv, const at::Tensor& positions, const at::Tenso
   MP_CHECK(cos.scalar_type() == at::kFloat && sin.scalar_type() == at::kFloat && cos.is_contiguous() &&
                sin.is_contiguous() && cos.size(1) == D / 2 && sin.sizes() == cos.sizes(),
            "cos/sin tables fp32 [max_pos, D/2]");
-  check_launch(mp_rope_kv_write(qkv.data_ptr(), qkv.stride(0), positions.data_ptr<int64_t>(), cos.data_ptr<float>(),
-                                sin.data_ptr<float>(), k_cache.data_ptr(), v_cache.data_ptr(),
-                                slots.data_ptr<int64_t>(), T, nh, nkv, D, page, cur_stream()),
-               "rope_kv_write");
+}
+
+// bf16 KV cache of the attention ops: pages [pages, nkv, page, D]; attn_args checks it against nkv
+// (an fp8 cache's byte pages handed to a bf16 kernel would be read past their end)
+inline void check_kv_bf16(const at::Tensor& k_cache, const at::Tensor& v_cache) {
+  check_bf16_cuda(k_cache, "k_cache");
+  check_bf16_cuda(v_cache, "v_cache");
+  MP_CHECK(k_cache.dim() == 4 && k_cache.sizes() == v_cache.sizes(), "cache [pages, nkv, page, D]");
 }
 
 // fp8 KV cache (kv_f8.h): codes uint8 [pages, nkv, page, D] + e8m0 scales uint8 [pages, nkv, page]
-static void check_kv_f8(const at::Tensor& k_cache, const at::Tensor& v_cache, const at::Tensor& k_scale,
+inline void check_kv_f8(const at::Tensor& k_cache, const at::Tensor& v_cache, const at::Tensor& k_scale,
                         const at::Tensor& v_scale, int64_t nkv) {
   for (const at::Tensor* t : {&k_cache, &v_cache, &k_scale, &v_scale})
     MP_CHECK(t->is_cuda() && t->scalar_type() == at::kByte && t->is_contiguous() && t->device() == k_cache.device(),
@@ -267,23 +194,35 @@ static void check_kv_f8(const at::Tensor& k_cache, const at::Tensor& v_cache, co
                reinterpret_cast<uintptr_t>(v_cache.data_ptr()) % 8 == 0, "fp8 KV codes must be 8-B aligned");
 }
 
+void rope_kv_write(at::Tensor& qkv, const at::Tensor& positions, const at::Tensor& cos, const at::Tensor& sin,
+                   at::Tensor& k_cache, at::Tensor& v_cache, const at::Tensor& slots, int64_t nh, int64_t nkv) {
+  check_bf16_cuda(qkv, "qkv");
+  check_rows(qkv, "qkv");
+  check_bf16_cuda(k_cache, "k_cache");
+  check_bf16_cuda(v_cache, "v_cache");
+  MP_CHECK(k_cache.dim() == 4 && k_cache.is_contiguous() && v_cache.is_contiguous(), "cache [pages, nkv, page, D]");
+  MP_CHECK(k_cache.sizes() == v_cache.sizes(), "k/v cache shapes differ");
+  MP_CHECK(k_cache.size(1) == nkv, "cache kv heads");
+  const int D = k_cache.size(3);
+  check_rope(qkv, positions, cos, sin, slots, nh, nkv, D);
+  check_launch(mp_rope_kv_write(qkv.data_ptr(), qkv.stride(0), positions.data_ptr<int64_t>(), cos.data_ptr<float>(),
+                                sin.data_ptr<float>(), k_cache.data_ptr(), v_cache.data_ptr(),
+                                slots.data_ptr<int64_t>(), qkv.size(0), nh, nkv, D, k_cache.size(2), cur_stream()),
+               "rope_kv_write");
+}
+
 void rope_kv_write_f8(at::Tensor& qkv, const at::Tensor& positions, const at::Tensor& cos, const at::Tensor& sin,
                       at::Tensor& k_cache, at::Tensor& v_cache, at::Tensor& k_scale, at::Tensor& v_scale,
                       const at::Tensor& slots, int64_t nh, int64_t nkv) {
   check_bf16_cuda(qkv, "qkv");
   check_rows(qkv, "qkv");
   check_kv_f8(k_cache, v_cache, k_scale, v_scale, nkv);
-  const int D = k_cache.size(3), page = k_cache.size(2);
-  MP_CHECK(qkv.size(1) == (nh + 2 * nkv) * D, "qkv width");
-  const int T = qkv.size(0);
-  MP_CHECK(positions.scalar_type() == at::kLong && positions.numel() == T && positions.is_contiguous(), "positions");
-  MP_CHECK(slots.scalar_type() == at::kLong && slots.numel() == T && slots.is_contiguous(), "slots");
-  MP_CHECK(cos.scalar_type() == at::kFloat && sin.scalar_type() == at::kFloat && cos.is_contiguous() &&
-               sin.is_contiguous() && cos.size(1) == D / 2 && sin.sizes() == cos.sizes(),
-           "cos/sin tables fp32 [max_pos, D/2]");
+  const int D = k_cache.size(3);
+  check_rope(qkv, positions, cos, sin, slots, nh, nkv, D);
   check_launch(mp_rope_kv_write_f8(qkv.data_ptr(), qkv.stride(0), positions.data_ptr<int64_t>(), cos.data_ptr<float>(),
                                    sin.data_ptr<float>(), k_cache.data_ptr(), v_cache.data_ptr(), k_scale.data_ptr(),
-                                   v_scale.data_ptr(), slots.data_ptr<int64_t>(), T, nh, nkv, D, page, cur_stream()),
+                                   v_scale.data_ptr(), slots.data_ptr<int64_t>(), qkv.size(0), nh, nkv, D,
+                                   k_cache.size(2), cur_stream()),
                "rope_kv_write_f8");
 }
 
@@ -302,53 +241,18 @@ void kv_write(const at::Tensor& k, const at::Tensor& v, at::Tensor& k_cache, at:
                "kv_write");
 }
 
-// Host mirror of mp::QkvPart (common.h): the qkv projection as split-K partial slabs
-// [S][M][width] fp32 + the fused-norm row statistics, read by the decode attention kernels.
-struct QkvPartArgs {
-  const float* part;
-  int S;
-  int64_t slab;
-  int ldn;
-  const unsigned long long* ss;
-  float inv_k, eps;
-};
-
-static bool qkv_part_args(const c10::optional<at::Tensor>& part, int64_t splits, const c10::optional<at::Tensor>& ss,
-                          double inv_k, double eps, int64_t T, int64_t width, QkvPartArgs& a) {
-  if (!part.has_value()) return false;
-  MP_CHECK(part->is_cuda() && part->scalar_type() == at::kFloat && part->is_contiguous() && part->dim() == 3 &&
-               part->size(0) == splits && part->size(1) == T && part->size(2) == width,
-           "qkv_part: fp32 [S, T, qkv width] split-K slabs (ops.linear_partials)");
-  MP_CHECK(splits >= 1 && splits <= 8, "qkv_part splits");
-  const unsigned long long* ssp = nullptr;
-  if (ss.has_value()) {
-    MP_CHECK(ss->is_cuda() && ss->scalar_type() == at::kLong && ss->is_contiguous() && ss->numel() >= mp_gemm_ss_elems(),
-             "part_ss: row statistics [32, 256] int64");
-    ssp = reinterpret_cast<const unsigned long long*>(ss->data_ptr<int64_t>());
-  }
-  a = QkvPartArgs{part->data_ptr<float>(), (int)splits, T * width, (int)width, ssp, (float)inv_k, (float)eps};
-  return true;
-}
-
-static void paged_attention_impl(const at::Tensor& q, const at::Tensor& k_cache, const at::Tensor& v_cache,
-                                 const at::Tensor& block_tables, const at::Tensor& q_seq, const at::Tensor& q_ctx,
-                                 at::Tensor& out, at::Tensor& workspace, int64_t nh, int64_t nkv, double scale,
-                                 int64_t part_size, int64_t num_parts, int64_t packed, const int64_t* rope_pos,
-                                 const float* cos_t, const float* sin_t, const int64_t* slots,
-                                 const c10::optional<at::Tensor>& counters, const QkvPartArgs* qp = nullptr,
-                                 const at::Tensor* k_scale = nullptr, const at::Tensor* v_scale = nullptr) {
+// The operands every attention op shares -> the launcher's arguments (mp_api.h), the fused-RoPE group
+// and the qkv partials left empty.  The caller has checked the cache pair (check_kv_bf16 / check_kv_f8);
+// k_scale / v_scale: the fp8 cache's scales.  packed: the output in the packed activation layout.
+mp::AttnArgs attn_args(const at::Tensor& q, const at::Tensor& k_cache, const at::Tensor& v_cache,
+                       const at::Tensor& block_tables, const at::Tensor& q_seq, const at::Tensor& q_ctx,
+                       at::Tensor& out, at::Tensor& workspace, int64_t nh, int64_t nkv, double scale,
+                       int64_t part_size, int64_t num_parts, int64_t packed, const at::Tensor* k_scale = nullptr,
+                       const at::Tensor* v_scale = nullptr) {
   check_bf16_cuda(q, "q");
   check_rows(q, "q");
   check_bf16_cuda(out, "out");
   MP_CHECK(out.is_contiguous(), "out contiguous");
-  if (k_scale != nullptr) {
-    check_kv_f8(k_cache, v_cache, *k_scale, *v_scale, nkv);
-  } else {
-    // (an fp8 cache's byte pages handed to the bf16 kernel would be read past their end)
-    check_bf16_cuda(k_cache, "k_cache");
-    check_bf16_cuda(v_cache, "v_cache");
-    MP_CHECK(k_cache.dim() == 4 && k_cache.sizes() == v_cache.sizes(), "cache [pages, nkv, page, D]");
-  }
   const int D = k_cache.size(3);
   const int T = q.size(0);
   MP_CHECK(q.size(1) >= nh * D, "q width");
@@ -364,6 +268,71 @@ static void paged_attention_impl(const at::Tensor& q, const at::Tensor& k_cache,
   MP_CHECK(q_ctx.scalar_type() == at::kInt && q_ctx.numel() == T, "q_ctx");
   MP_CHECK(workspace.scalar_type() == at::kFloat, "workspace fp32");
   if (num_parts > 1) MP_CHECK(workspace.numel() >= (int64_t)T * nh * num_parts * (D + 2), "workspace too small");
+  mp::AttnArgs a{};
+  a.q = q.data_ptr();
+  a.q_stride = q.stride(0);
+  a.kc = k_cache.data_ptr();
+  a.vc = v_cache.data_ptr();
+  if (k_scale != nullptr) {
+    a.ks = k_scale->data_ptr();
+    a.vs = v_scale->data_ptr();
+  }
+  a.bt = block_tables.data_ptr<int32_t>();
+  a.bt_stride = block_tables.stride(0);
+  a.q_seq = q_seq.data_ptr<int32_t>();
+  a.q_ctx = q_ctx.data_ptr<int32_t>();
+  a.out = out.data_ptr();
+  a.workspace = workspace.data_ptr<float>();
+  a.T = T;
+  a.nh = nh;
+  a.nkv = nkv;
+  a.D = D;
+  a.page_size = k_cache.size(2);
+  a.PS = part_size;
+  a.NP = num_parts;
+  a.scale = (float)scale;
+  a.packed_mt = packed ? (T + 15) / 16 : 0;
+  return a;
+}
+
+// The qkv projection as split-K partial slabs [S][T][width] fp32 + the fused-norm row statistics
+// (mp::QkvPart), read by the decode attention kernels; part == nullptr when absent.
+mp::QkvPart qkv_part_args(const c10::optional<at::Tensor>& part, int64_t splits, const c10::optional<at::Tensor>& ss,
+                          double inv_k, double eps, int64_t T, int64_t width) {
+  if (!part.has_value()) return mp::QkvPart{};
+  MP_CHECK(part->is_cuda() && part->scalar_type() == at::kFloat && part->is_contiguous() && part->dim() == 3 &&
+               part->size(0) == splits && part->size(1) == T && part->size(2) == width,
+           "qkv_part: fp32 [S, T, qkv width] split-K slabs (ops.linear_partials)");
+  MP_CHECK(splits >= 1 && splits <= 8, "qkv_part splits");
+  const unsigned long long* ssp = nullptr;
+  if (ss.has_value()) {
+    MP_CHECK(ss->is_cuda() && ss->scalar_type() == at::kLong && ss->is_contiguous() && ss->numel() >= mp_gemm_ss_elems(),
+             "part_ss: row statistics [32, 256] int64");
+    ssp = reinterpret_cast<const unsigned long long*>(ss->data_ptr<int64_t>());
+  }
+  return mp::QkvPart{part->data_ptr<float>(), (int)splits, T * width, (int)width, ssp, (float)inv_k, (float)eps};
+}
+
+// the fused-RoPE group of a decode launch (operands checked by check_rope) and its qkv partials
+inline void fuse_rope(mp::AttnArgs& a, const at::Tensor& positions, const at::Tensor& cos, const at::Tensor& sin,
+                      const at::Tensor& slots, const mp::QkvPart& qp) {
+  a.rope_pos = positions.data_ptr<int64_t>();
+  a.cos_t = cos.data_ptr<float>();
+  a.sin_t = sin.data_ptr<float>();
+  a.slots = slots.data_ptr<int64_t>();
+  a.qp = qp;
+}
+
+// int32 [2, N] block table (row 0: first token or block, row 1: count) -> (row 0, N); row 1 = row 0 + N
+inline std::pair<const int32_t*, int> check_blocks(const at::Tensor& t, bool on_gpu, int64_t max_n, const char* msg) {
+  MP_CHECK((!on_gpu || t.is_cuda()) && t.scalar_type() == at::kInt && t.dim() == 2 && t.size(0) == 2 &&
+               t.is_contiguous() && t.size(1) <= max_n, msg);
+  return {t.data_ptr<int32_t>(), (int)t.size(1)};
+}
+
+// The flash-decoding launch (attention.hip), on a bf16 or an fp8 (a.ks) cache.  counters: optional
+// arrival counters of the in-launch split-K combine.
+void launch_paged(const mp::AttnArgs& a, const c10::optional<at::Tensor>& counters) {
   int* cp = nullptr;
   int ncnt = 0;
   if (counters.has_value()) {
@@ -372,31 +341,30 @@ static void paged_attention_impl(const at::Tensor& q, const at::Tensor& k_cache,
     cp = counters->data_ptr<int32_t>();
     ncnt = (int)counters->numel();
   }
-  if (k_scale != nullptr) {
-    check_launch(mp_paged_attention_f8(q.data_ptr(), q.stride(0), k_cache.data_ptr(), v_cache.data_ptr(),
-                                       k_scale->data_ptr(), v_scale->data_ptr(), block_tables.data_ptr<int32_t>(),
-                                       block_tables.stride(0), q_seq.data_ptr<int32_t>(), q_ctx.data_ptr<int32_t>(),
-                                       out.data_ptr(), workspace.data_ptr<float>(), T, nh, nkv, D, k_cache.size(2),
-                                       part_size, num_parts, (float)scale, packed ? (int)((T + 15) / 16) : 0,
-                                       rope_pos, cos_t, sin_t, slots, cp, ncnt, qp, cur_stream()),
-                 "paged_attention_f8");
-    return;
-  }
-  check_launch(mp_paged_attention(q.data_ptr(), q.stride(0), k_cache.data_ptr(), v_cache.data_ptr(),
-                                  block_tables.data_ptr<int32_t>(), block_tables.stride(0), q_seq.data_ptr<int32_t>(),
-                                  q_ctx.data_ptr<int32_t>(), out.data_ptr(), workspace.data_ptr<float>(), T, nh, nkv,
-                                  D, k_cache.size(2), part_size, num_parts, (float)scale,
-                                  packed ? (int)((T + 15) / 16) : 0, rope_pos, cos_t, sin_t, slots, cp, ncnt,
-                                  qp, cur_stream()),
-               "paged_attention");
+  check_launch(mp_paged_attention(&a, cp, ncnt, cur_stream()),
+               a.ks != nullptr ? "paged_attention_f8" : "paged_attention");
 }
 
 void paged_attention(const at::Tensor& q, const at::Tensor& k_cache, const at::Tensor& v_cache,
                      const at::Tensor& block_tables, const at::Tensor& q_seq, const at::Tensor& q_ctx,
                      at::Tensor& out, at::Tensor& workspace, int64_t nh, int64_t nkv, double scale, int64_t part_size,
                      int64_t num_parts, int64_t packed, const c10::optional<at::Tensor>& counters) {
-  paged_attention_impl(q, k_cache, v_cache, block_tables, q_seq, q_ctx, out, workspace, nh, nkv, scale, part_size,
-                       num_parts, packed, nullptr, nullptr, nullptr, nullptr, counters);
+  check_kv_bf16(k_cache, v_cache);
+  launch_paged(attn_args(q, k_cache, v_cache, block_tables, q_seq, q_ctx, out, workspace, nh, nkv, scale, part_size,
+                         num_parts, packed),
+               counters);
+}
+
+// The flash-decoding kernel on an fp8 KV cache (attention.hip F8 form).
+void paged_attention_f8(const at::Tensor& q, const at::Tensor& k_cache, const at::Tensor& v_cache,
+                        const at::Tensor& k_scale, const at::Tensor& v_scale, const at::Tensor& block_tables,
+                        const at::Tensor& q_seq, const at::Tensor& q_ctx, at::Tensor& out, at::Tensor& workspace,
+                        int64_t nh, int64_t nkv, double scale, int64_t part_size, int64_t num_parts, int64_t packed,
+                        const c10::optional<at::Tensor>& counters) {
+  check_kv_f8(k_cache, v_cache, k_scale, v_scale, nkv);
+  launch_paged(attn_args(q, k_cache, v_cache, block_tables, q_seq, q_ctx, out, workspace, nh, nkv, scale, part_size,
+                         num_parts, packed, &k_scale, &v_scale),
+               counters);
 }
 
 // Decode attention with RoPE + KV write fused in (attention.hip ROPE path): q is the unrotated
@@ -408,35 +376,18 @@ void paged_attention_rope(const at::Tensor& qkv, at::Tensor& k_cache, at::Tensor
                           double scale, int64_t part_size, int64_t num_parts, int64_t packed,
                           const c10::optional<at::Tensor>& counters, const c10::optional<at::Tensor>& qkv_part,
                           int64_t part_splits, const c10::optional<at::Tensor>& part_ss, double inv_k, double eps) {
-  check_bf16_cuda(k_cache, "k_cache");
-  check_bf16_cuda(v_cache, "v_cache");
-  MP_CHECK(k_cache.dim() == 4 && k_cache.sizes() == v_cache.sizes(), "cache [pages, nkv, page, D]");
-  const int D = k_cache.size(3), T = qkv.size(0);
-  MP_CHECK(qkv.size(1) == (nh + 2 * nkv) * D, "qkv width");
-  MP_CHECK(positions.scalar_type() == at::kLong && positions.numel() == T && positions.is_contiguous(), "positions");
-  MP_CHECK(slots.scalar_type() == at::kLong && slots.numel() == T && slots.is_contiguous(), "slots");
-  MP_CHECK(cos.scalar_type() == at::kFloat && sin.scalar_type() == at::kFloat && cos.is_contiguous() &&
-               sin.is_contiguous() && cos.size(1) == D / 2 && sin.sizes() == cos.sizes(),
-           "cos/sin tables fp32 [max_pos, D/2]");
+  check_kv_bf16(k_cache, v_cache);
+  const int D = k_cache.size(3);
+  check_rope(qkv, positions, cos, sin, slots, nh, nkv, D);
   MP_CHECK(D % 16 == 0, "head dim");
-  QkvPartArgs qp;
-  const bool has_qp = qkv_part_args(qkv_part, part_splits, part_ss, inv_k, eps, T, qkv.size(1), qp);
-  paged_attention_impl(qkv, k_cache, v_cache, block_tables, q_seq, q_ctx, out, workspace, nh, nkv, scale, part_size,
-                       num_parts, packed, positions.data_ptr<int64_t>(), cos.data_ptr<float>(), sin.data_ptr<float>(),
-                       slots.data_ptr<int64_t>(), counters, has_qp ? &qp : nullptr);
+  const mp::QkvPart qp = qkv_part_args(qkv_part, part_splits, part_ss, inv_k, eps, qkv.size(0), qkv.size(1));
+  mp::AttnArgs a = attn_args(qkv, k_cache, v_cache, block_tables, q_seq, q_ctx, out, workspace, nh, nkv, scale,
+                             part_size, num_parts, packed);
+  fuse_rope(a, positions, cos, sin, slots, qp);
+  launch_paged(a, counters);
 }
 
-// The flash-decoding kernel on an fp8 KV cache (attention.hip F8 form).
-void paged_attention_f8(const at::Tensor& q, const at::Tensor& k_cache, const at::Tensor& v_cache,
-                        const at::Tensor& k_scale, const at::Tensor& v_scale, const at::Tensor& block_tables,
-                        const at::Tensor& q_seq, const at::Tensor& q_ctx, at::Tensor& out, at::Tensor& workspace,
-                        int64_t nh, int64_t nkv, double scale, int64_t part_size, int64_t num_parts, int64_t packed,
-                        const c10::optional<at::Tensor>& counters) {
-  paged_attention_impl(q, k_cache, v_cache, block_tables, q_seq, q_ctx, out, workspace, nh, nkv, scale, part_size,
-                       num_parts, packed, nullptr, nullptr, nullptr, nullptr, counters, nullptr, &k_scale, &v_scale);
-}
-
-// Its fused decode form: RoPE, the new token's quantization + page write and attention in one launch.
+// Its fp8 cache form: RoPE, the new token's quantization + page write and attention in one launch.
 void paged_attention_rope_f8(const at::Tensor& qkv, at::Tensor& k_cache, at::Tensor& v_cache, at::Tensor& k_scale,
                              at::Tensor& v_scale, const at::Tensor& block_tables, const at::Tensor& q_seq,
                              const at::Tensor& q_ctx, const at::Tensor& positions, const at::Tensor& cos,
@@ -446,68 +397,25 @@ void paged_attention_rope_f8(const at::Tensor& qkv, at::Tensor& k_cache, at::Ten
                              const c10::optional<at::Tensor>& qkv_part, int64_t part_splits,
                              const c10::optional<at::Tensor>& part_ss, double inv_k, double eps) {
   check_kv_f8(k_cache, v_cache, k_scale, v_scale, nkv);
-  const int D = k_cache.size(3), T = qkv.size(0);
-  MP_CHECK(qkv.size(1) == (nh + 2 * nkv) * D, "qkv width");
-  MP_CHECK(positions.scalar_type() == at::kLong && positions.numel() == T && positions.is_contiguous(), "positions");
-  MP_CHECK(slots.scalar_type() == at::kLong && slots.numel() == T && slots.is_contiguous(), "slots");
-  MP_CHECK(cos.scalar_type() == at::kFloat && sin.scalar_type() == at::kFloat && cos.is_contiguous() &&
-               sin.is_contiguous() && cos.size(1) == D / 2 && sin.sizes() == cos.sizes(),
-           "cos/sin tables fp32 [max_pos, D/2]");
-  QkvPartArgs qp;
-  const bool has_qp = qkv_part_args(qkv_part, part_splits, part_ss, inv_k, eps, T, qkv.size(1), qp);
-  paged_attention_impl(qkv, k_cache, v_cache, block_tables, q_seq, q_ctx, out, workspace, nh, nkv, scale, part_size,
-                       num_parts, packed, positions.data_ptr<int64_t>(), cos.data_ptr<float>(), sin.data_ptr<float>(),
-                       slots.data_ptr<int64_t>(), counters, has_qp ? &qp : nullptr, &k_scale, &v_scale);
+  check_rope(qkv, positions, cos, sin, slots, nh, nkv, k_cache.size(3));
+  const mp::QkvPart qp = qkv_part_args(qkv_part, part_splits, part_ss, inv_k, eps, qkv.size(0), qkv.size(1));
+  mp::AttnArgs a = attn_args(qkv, k_cache, v_cache, block_tables, q_seq, q_ctx, out, workspace, nh, nkv, scale,
+                             part_size, num_parts, packed, &k_scale, &v_scale);
+  fuse_rope(a, positions, cos, sin, slots, qp);
+  launch_paged(a, counters);
 }
 
-static void attention_mfma_impl(const at::Tensor& q, const at::Tensor& k_cache, const at::Tensor& v_cache,
-                                const at::Tensor& block_tables, const at::Tensor& q_seq, const at::Tensor& q_ctx,
-                                const at::Tensor& qblocks, at::Tensor& out, at::Tensor& workspace, int64_t nh,
-                                int64_t nkv, double scale, int64_t part_size, int64_t num_parts, int64_t packed,
-                                const int64_t* rope_pos, const float* cos_t, const float* sin_t,
-                                const int64_t* slots, const c10::optional<at::Tensor>& superblocks = c10::nullopt,
-                                const QkvPartArgs* qp = nullptr, void* mx_ax = nullptr, void* mx_as = nullptr) {
-  check_bf16_cuda(q, "q");
-  check_rows(q, "q");
-  check_bf16_cuda(out, "out");
-  MP_CHECK(out.is_contiguous(), "out contiguous");
-  check_bf16_cuda(k_cache, "k_cache");
-  check_bf16_cuda(v_cache, "v_cache");
-  MP_CHECK(k_cache.dim() == 4 && k_cache.sizes() == v_cache.sizes(), "cache [pages, nkv, page, D]");
-  const int D = k_cache.size(3);
-  const int T = q.size(0);
-  MP_CHECK(q.size(1) >= nh * D, "q width");
-  if (packed) {
-    MP_CHECK(out.numel() >= packed_numel(T, nh * D) && (nh * D) % 32 == 0, "packed out numel");
-  } else {
-    MP_CHECK(out.numel() == (int64_t)T * nh * D, "out numel");
-  }
-  MP_CHECK(k_cache.size(1) == nkv && k_cache.is_contiguous() && v_cache.is_contiguous(), "cache");
-  MP_CHECK(block_tables.scalar_type() == at::kInt && block_tables.dim() == 2 && block_tables.stride(1) == 1,
-           "block_tables int32 [S, max_pages]");
-  MP_CHECK(q_seq.scalar_type() == at::kInt && q_seq.numel() == T, "q_seq");
-  MP_CHECK(q_ctx.scalar_type() == at::kInt && q_ctx.numel() == T, "q_ctx");
-  MP_CHECK(workspace.scalar_type() == at::kFloat, "workspace fp32");
-  if (num_parts > 1) MP_CHECK(workspace.numel() >= (int64_t)T * nh * num_parts * (D + 2), "workspace too small");
-  MP_CHECK(qblocks.scalar_type() == at::kInt && qblocks.dim() == 2 && qblocks.size(0) == 2 && qblocks.is_contiguous(),
-           "qblocks int32 [2, NB] (first token, token count)");
-  const int NB = qblocks.size(1);
-  const int32_t* sbp = nullptr;
+// The MFMA launch (attention_mfma.hip): query blocks, optional prefill superblocks int32 [2, NSB]
+// (first query block, count <= 4), optional MX output.
+void launch_mfma(const mp::AttnArgs& a, const at::Tensor& qblocks, const c10::optional<at::Tensor>& superblocks,
+                 void* mx_ax = nullptr, void* mx_as = nullptr) {
+  const auto [qb, NB] = check_blocks(qblocks, false, INT64_MAX, "qblocks int32 [2, NB] (first token, token count)");
+  const int32_t* sb = nullptr;
   int NSB = 0;
-  if (superblocks.has_value()) {  // prefill superblocks: int32 [2, NSB] (first query block, count <= 4)
-    MP_CHECK(superblocks->is_cuda() && superblocks->scalar_type() == at::kInt && superblocks->dim() == 2 &&
-                 superblocks->size(0) == 2 && superblocks->is_contiguous() && superblocks->size(1) <= NB,
-             "superblocks int32 [2, NSB] (ops.query_superblocks)");
-    sbp = superblocks->data_ptr<int32_t>();
-    NSB = superblocks->size(1);
-  }
-  check_launch(mp_attention_mfma(q.data_ptr(), q.stride(0), k_cache.data_ptr(), v_cache.data_ptr(),
-                                 block_tables.data_ptr<int32_t>(), block_tables.stride(0), q_seq.data_ptr<int32_t>(),
-                                 q_ctx.data_ptr<int32_t>(), qblocks.data_ptr<int32_t>(),
-                                 qblocks.data_ptr<int32_t>() + NB, NB, out.data_ptr(), workspace.data_ptr<float>(), T,
-                                 nh, nkv, D, k_cache.size(2), part_size, num_parts, (float)scale,
-                                 packed ? (int)((T + 15) / 16) : 0, rope_pos, cos_t, sin_t, slots, sbp,
-                                 sbp != nullptr ? sbp + NSB : nullptr, NSB, qp, mx_ax, mx_as, cur_stream()),
+  if (superblocks.has_value())
+    std::tie(sb, NSB) = check_blocks(*superblocks, true, NB, "superblocks int32 [2, NSB] (ops.query_superblocks)");
+  check_launch(mp_attention_mfma(&a, qb, qb + NB, NB, sb, sb != nullptr ? sb + NSB : nullptr, NSB, mx_ax, mx_as,
+                                 cur_stream()),
                "attention_mfma");
 }
 
@@ -516,8 +424,10 @@ void attention_mfma(const at::Tensor& q, const at::Tensor& k_cache, const at::Te
                     const at::Tensor& qblocks, at::Tensor& out, at::Tensor& workspace, int64_t nh, int64_t nkv,
                     double scale, int64_t part_size, int64_t num_parts, int64_t packed,
                     const c10::optional<at::Tensor>& superblocks) {
-  attention_mfma_impl(q, k_cache, v_cache, block_tables, q_seq, q_ctx, qblocks, out, workspace, nh, nkv, scale,
-                      part_size, num_parts, packed, nullptr, nullptr, nullptr, nullptr, superblocks);
+  check_kv_bf16(k_cache, v_cache);
+  launch_mfma(attn_args(q, k_cache, v_cache, block_tables, q_seq, q_ctx, out, workspace, nh, nkv, scale, part_size,
+                        num_parts, packed),
+              qblocks, superblocks);
 }
 
 // Causal prefill attention, 32x32x16 MFMA FA2 form (attention_fa.hip): row-major output.
@@ -525,37 +435,14 @@ void attention_fa(const at::Tensor& q, const at::Tensor& k_cache, const at::Tens
                   const at::Tensor& block_tables, const at::Tensor& q_seq, const at::Tensor& q_ctx,
                   const at::Tensor& fablocks, at::Tensor& out, at::Tensor& workspace, int64_t nh, int64_t nkv,
                   double scale, int64_t part_size, int64_t num_parts, int64_t waves, int64_t pair) {
-  check_bf16_cuda(q, "q");
-  check_rows(q, "q");
-  check_bf16_cuda(out, "out");
-  check_bf16_cuda(k_cache, "k_cache");
-  check_bf16_cuda(v_cache, "v_cache");
-  MP_CHECK(out.is_contiguous(), "out contiguous");
-  MP_CHECK(k_cache.dim() == 4 && k_cache.sizes() == v_cache.sizes(), "cache [pages, nkv, page, D]");
-  const int D = k_cache.size(3);
-  const int T = q.size(0);
-  MP_CHECK(D == 128, "attention_fa: head_dim 128");
-  MP_CHECK(q.size(1) >= nh * D, "q width");
-  MP_CHECK(out.numel() == (int64_t)T * nh * D, "out numel");
-  MP_CHECK(k_cache.size(1) == nkv && k_cache.is_contiguous() && v_cache.is_contiguous(), "cache");
-  MP_CHECK(block_tables.scalar_type() == at::kInt && block_tables.dim() == 2 && block_tables.stride(1) == 1,
-           "block_tables int32 [S, max_pages]");
-  MP_CHECK(q_seq.scalar_type() == at::kInt && q_seq.numel() == T, "q_seq");
-  MP_CHECK(q_ctx.scalar_type() == at::kInt && q_ctx.numel() == T, "q_ctx");
-  MP_CHECK(workspace.scalar_type() == at::kFloat, "workspace fp32");
-  if (num_parts > 1) MP_CHECK(workspace.numel() >= (int64_t)T * nh * num_parts * (D + 2), "workspace too small");
-  MP_CHECK(fablocks.is_cuda() && fablocks.scalar_type() == at::kInt && fablocks.dim() == 2 && fablocks.size(0) == 2 &&
-               fablocks.is_contiguous(),
-           "fablocks int32 [2, NB] (first token, token count), ops.fa_blocks");
+  check_kv_bf16(k_cache, v_cache);
+  MP_CHECK(k_cache.size(3) == 128, "attention_fa: head_dim 128");
+  const mp::AttnArgs a = attn_args(q, k_cache, v_cache, block_tables, q_seq, q_ctx, out, workspace, nh, nkv, scale,
+                                   part_size, num_parts, 0);
+  const auto [fb, NB] =
+      check_blocks(fablocks, true, INT64_MAX, "fablocks int32 [2, NB] (first token, token count), ops.fa_blocks");
   MP_CHECK(waves == 4 || waves == 8, "waves 4 or 8");
-  const int NB = fablocks.size(1);
-  check_launch(mp_attention_fa(q.data_ptr(), q.stride(0), k_cache.data_ptr(), v_cache.data_ptr(),
-                               block_tables.data_ptr<int32_t>(), block_tables.stride(0), q_seq.data_ptr<int32_t>(),
-                               q_ctx.data_ptr<int32_t>(), fablocks.data_ptr<int32_t>(),
-                               fablocks.data_ptr<int32_t>() + NB, NB, out.data_ptr(), workspace.data_ptr<float>(), T,
-                               nh, nkv, D, k_cache.size(2), part_size, num_parts, (float)scale, (int)waves,
-                               (int)pair, cur_stream()),
-               "attention_fa");
+  check_launch(mp_attention_fa(&a, fb, fb + NB, NB, (int)waves, (int)pair, cur_stream()), "attention_fa");
 }
 
 // GQA decode with RoPE + KV write fused (attention_mfma.hip ROPE path): one token per query block,
@@ -568,19 +455,11 @@ void attention_mfma_rope(const at::Tensor& qkv, at::Tensor& k_cache, at::Tensor&
                          const c10::optional<at::Tensor>& qkv_part, int64_t part_splits,
                          const c10::optional<at::Tensor>& part_ss, double inv_k, double eps,
                          const c10::optional<at::Tensor>& mx_ax, const c10::optional<at::Tensor>& mx_as) {
-  check_bf16_cuda(k_cache, "k_cache");
-  check_bf16_cuda(v_cache, "v_cache");
-  MP_CHECK(k_cache.dim() == 4 && k_cache.sizes() == v_cache.sizes(), "cache [pages, nkv, page, D]");
+  check_kv_bf16(k_cache, v_cache);
   const int D = k_cache.size(3), T = qkv.size(0);
-  MP_CHECK(qkv.size(1) == (nh + 2 * nkv) * D, "qkv width");
-  MP_CHECK(positions.scalar_type() == at::kLong && positions.numel() == T && positions.is_contiguous(), "positions");
-  MP_CHECK(slots.scalar_type() == at::kLong && slots.numel() == T && slots.is_contiguous(), "slots");
-  MP_CHECK(cos.scalar_type() == at::kFloat && sin.scalar_type() == at::kFloat && cos.is_contiguous() &&
-               sin.is_contiguous() && cos.size(1) == D / 2 && sin.sizes() == cos.sizes(),
-           "cos/sin tables fp32 [max_pos, D/2]");
+  check_rope(qkv, positions, cos, sin, slots, nh, nkv, D);
   MP_CHECK(qblocks.size(1) == T, "fused RoPE needs one query token per block (decode)");
-  QkvPartArgs qp;
-  const bool has_qp = qkv_part_args(qkv_part, part_splits, part_ss, inv_k, eps, T, qkv.size(1), qp);
+  const mp::QkvPart qp = qkv_part_args(qkv_part, part_splits, part_ss, inv_k, eps, T, qkv.size(1));
   void* axp = nullptr;
   void* asp = nullptr;
   if (mx_ax.has_value()) {  // the output as the W8A8-MX GEMM's activation (ops.quant_mx layout)
@@ -593,9 +472,10 @@ void attention_mfma_rope(const at::Tensor& qkv, at::Tensor& k_cache, at::Tensor&
     axp = mx_ax->data_ptr();
     asp = mx_as->data_ptr();
   }
-  attention_mfma_impl(qkv, k_cache, v_cache, block_tables, q_seq, q_ctx, qblocks, out, workspace, nh, nkv, scale,
-                      part_size, num_parts, packed, positions.data_ptr<int64_t>(), cos.data_ptr<float>(),
-                      sin.data_ptr<float>(), slots.data_ptr<int64_t>(), c10::nullopt, has_qp ? &qp : nullptr, axp, asp);
+  mp::AttnArgs a = attn_args(qkv, k_cache, v_cache, block_tables, q_seq, q_ctx, out, workspace, nh, nkv, scale,
+                             part_size, num_parts, packed);
+  fuse_rope(a, positions, cos, sin, slots, qp);
+  launch_mfma(a, qblocks, c10::nullopt, axp, asp);
 }
 
 void embedding(const at::Tensor& ids, const at::Tensor& table, at::Tensor& out) {

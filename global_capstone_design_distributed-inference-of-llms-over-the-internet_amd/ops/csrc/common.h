@@ -10,6 +10,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "mp_api.h"
+
 namespace mp {
 
 typedef unsigned short bf16_t;
@@ -128,22 +130,10 @@ __device__ __forceinline__ int64_t apk_off(int row, int col, int MT) {
   return ((((int64_t)(col >> 5) * MT + (row >> 4)) * 64 + ((col >> 3) & 3) * 16 + (row & 15)) << 3) + (col & 7);
 }
 
-// The qkv projection left as split-K partial slabs (decode GEMM flags bit 14, mp_gemm_rwk_split):
-// part[s][row][col] fp32, s < S, plus the fused-norm row statistics (gemm_kernels.h EpiArgs::ss_in:
-// QP_SS_NSH shards of QP_SS_ROWS rows, fixed-point sums of squares).  The decode attention kernels
-// read q / k / v through qkv_part_load8, which is the split-K reduce launch's epilogue 0 inlined:
-// the S slabs summed in split order from zero, times rsqrt(ss / K + eps), rounded to bf16 - the
-// same bits the reduce launch would have stored, without its launch.
+// Device side of mp::QkvPart (mp_api.h): the qkv projection as split-K partial slabs plus the
+// fused-norm row statistics, QP_SS_NSH shards of QP_SS_ROWS rows of fixed-point sums of squares.
 constexpr int QP_SS_NSH = 32, QP_SS_ROWS = 256;
 constexpr float QP_SS_FX = 1048576.f;
-struct QkvPart {
-  const float* part;               // nullptr: read the bf16 qkv rows instead
-  int S;                           // split count
-  int64_t slab;                    // elements per slab (M x ldn)
-  int ldn;                         // row pitch (the qkv width)
-  const unsigned long long* ss;    // row statistics, or nullptr (no row scale)
-  float inv_k, eps;
-};
 
 // The row scale in two halves, so a kernel can issue the shard loads early and reduce late:
 // lane j < QP_SS_NSH loads shard j; every lane of the wave must call the reduction (the integer

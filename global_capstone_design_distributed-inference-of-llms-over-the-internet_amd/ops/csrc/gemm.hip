@@ -3,10 +3,6 @@
 // gemm_w8.hip (separate translation units: the build compiles them in parallel).
 #include "gemm_kernels.h"
 
-extern "C" int mp_gemm_bf16_wide(const void* x, const void* w, void* y, int64_t y_stride, const void* res,
-                                 int64_t res_stride, int M, int N, int K, int epilogue, int flags, void* ws,
-                                 const mp::EpiArgs& ep, hipStream_t stream);
-
 namespace mp {
 
 // Pack W[N, K] (row-major) into the fragment-native layout Wp[N/16][K/32][64][8].

@@ -1,0 +1,136 @@
+// The seam between the host bindings (bindings.cpp, compiled as plain C++) and the kernel files:
+// the argument structs both sides read and one prototype per extern "C" entry point.  Every .hip
+// file that defines an entry point includes this header, so a definition that disagrees with its
+// prototype does not compile.  No device code here.
+#pragma once
+#include <hip/hip_runtime_api.h>
+#include <stdint.h>
+
+namespace mp {
+
+// The qkv projection left as split-K partial slabs (decode GEMM flags bit 14, mp_gemm_rwk_split):
+// part[s][row][col] fp32, s < S, plus the fused-norm row statistics (gemm_kernels.h EpiArgs::ss_in:
+// QP_SS_NSH shards of QP_SS_ROWS rows, fixed-point sums of squares).  The decode attention kernels
+// read q / k / v through qkv_part_load8 (common.h), which is the split-K reduce launch's epilogue 0
+// inlined: the S slabs summed in split order from zero, times rsqrt(ss / K + eps), rounded to bf16 -
+// the same bits the reduce launch would have stored, without its launch.
+struct QkvPart {
+  const float* part;               // nullptr: read the bf16 qkv rows instead
+  int S;                           // split count
+  int64_t slab;                    // elements per slab (M x ldn)
+  int ldn;                         // row pitch (the qkv width)
+  const unsigned long long* ss;    // row statistics, or nullptr (no row scale)
+  float inv_k, eps;
+};
+
+// What every attention launcher takes (mp_paged_attention, mp_attention_mfma, mp_attention_fa).
+struct AttnArgs {
+  const void* q;                   // bf16 query rows [T, >= nh * D] (fused RoPE: the unrotated qkv rows)
+  int64_t q_stride;
+  void* kc;                        // cache pages [pages, nkv, page_size, D]: bf16, or e4m3 codes with
+  void* vc;                        //   ks / vs (kv_f8.h); written only at slots[t] by the fused RoPE forms
+  void* ks;                        // fp8 cache: e8m0 row scales [pages, nkv, page_size]; nullptr on a bf16 cache
+  void* vs;
+  const int32_t* bt;               // block tables [sequences, bt_stride]
+  int bt_stride;
+  const int32_t* q_seq;            // [T] block-table row of each query
+  const int32_t* q_ctx;            // [T] context length of each query (0: padding row, output 0)
+  void* out;                       // bf16 [T, nh * D], or packed (packed_mt = ceil(T / 16) > 0)
+  float* workspace;                // split-K partials when NP > 1: [T, nh, NP, D] outputs, then (max, sum) pairs
+  int T, nh, nkv, D, page_size;
+  int PS, NP;                      // context tokens per part, parts
+  float scale;
+  int packed_mt;
+  const int64_t* rope_pos;         // fused RoPE + KV write (decode), all nullptr otherwise: [T] positions,
+  const float* cos_t;              //   fp32 tables [max_pos, D / 2],
+  const float* sin_t;
+  const int64_t* slots;            //   [T] cache slot of the new token (< 0: nothing written)
+  QkvPart qp;                      // qp.part == nullptr: absent
+};
+
+// log2 of the page size, or -1 when it is no power of two
+inline int attn_page_log2(const AttnArgs& a) {
+  int s = 0;
+  while ((1 << s) < a.page_size) ++s;
+  return (1 << s) == a.page_size ? s : -1;
+}
+
+// the (max, sum) half of the split-K workspace; the partial outputs start at a.workspace
+inline float* attn_ws_ml(const AttnArgs& a) { return a.workspace + (int64_t)a.T * a.nh * a.NP * a.D; }
+
+// the softmax scale in the exp2 domain
+inline float attn_scale_log2(const AttnArgs& a) { return a.scale * 1.4426950408889634f; }
+
+struct EpiArgs;  // gemm_kernels.h
+
+}  // namespace mp
+
+extern "C" {
+// norm.hip
+int mp_rmsnorm(const void* x, int64_t x_stride, void* res, int64_t res_stride, const void* w, void* y,
+               int64_t y_stride, const int32_t* rows, int nrows, int H, float eps, int mode, int packed_mt,
+               void* ss_out, void* a8, float* a8_scale, const int64_t* gather, int64_t gather_n,
+               hipStream_t stream);
+// rope_kv.hip
+int mp_rope_kv_write(void* qkv, int64_t qkv_stride, const int64_t* pos, const float* cos_t, const float* sin_t,
+                     void* kc, void* vc, const int64_t* slots, int T, int nh, int nkv, int D, int page_size,
+                     hipStream_t stream);
+int mp_rope_kv_write_f8(void* qkv, int64_t qkv_stride, const int64_t* pos, const float* cos_t, const float* sin_t,
+                        void* kc, void* vc, void* ks, void* vs, const int64_t* slots, int T, int nh, int nkv, int D,
+                        int page_size, hipStream_t stream);
+int mp_kv_write(const void* k, int64_t k_stride, const void* v, int64_t v_stride, void* kc, void* vc,
+                const int64_t* slots, int T, int nkv, int D, int page_size, hipStream_t stream);
+// attention.hip (a.ks != nullptr: the fp8 cache form), attention_mfma.hip, attention_fa.hip
+int mp_paged_attention(const mp::AttnArgs* a, int* counters, int n_counters, hipStream_t stream);
+int mp_attention_mfma(const mp::AttnArgs* a, const int32_t* qb_tok0, const int32_t* qb_ntok, int NB,
+                      const int32_t* sb_first, const int32_t* sb_n, int NSB, void* mx_ax, void* mx_as,
+                      hipStream_t stream);
+int mp_attention_fa(const mp::AttnArgs* a, const int32_t* fb_tok0, const int32_t* fb_ntok, int NBF, int nw, int pair,
+                    hipStream_t stream);
+// elementwise.hip
+int mp_embedding(const int64_t* ids, const void* table, void* out, int T, int H, int64_t vocab, hipStream_t stream);
+int mp_swiglu(const void* gu, void* out, int64_t T, int F, hipStream_t stream);
+int mp_add(const void* a, const void* b, void* y, int64_t n, hipStream_t stream);
+int mp_argmax(const void* logits, int64_t stride, int R, int V, int64_t* out, hipStream_t stream);
+// sampling.hip
+int mp_sample(const void* logits, int64_t stride, int R, int V, const float* temps, const float* top_ps,
+              const int32_t* top_ks, const float* rep_pens, int32_t* recent, int recent_stride, int32_t* recent_len,
+              const int64_t* seeds, float* ws, int64_t* out, int update, hipStream_t stream);
+// gemm.hip, gemm_wide.hip
+int mp_gemm_ss_elems();
+int64_t mp_gemm_slab_offset();
+int64_t mp_gemm_slab_bytes();
+int mp_gemm_rwk_split(int M, int N, int K, int f8);
+int64_t mp_gemm_workspace_bytes();
+int mp_gemm_bf16(const void* x, int64_t x_stride, const void* w, void* y, int64_t y_stride, const void* res,
+                 int64_t res_stride, int M, int N, int K, int epilogue, int flags, void* ws, const int* gate,
+                 void* ap, void* ss_out, void* ss_zero, const void* ss_in, float inv_k, float eps,
+                 hipStream_t stream);
+int mp_pack_act(const void* x, int64_t xs, void* ap, int M, int K, hipStream_t stream);
+int mp_pack_weight(const void* w, void* wp, int N, int K, hipStream_t stream);
+int mp_gemm_bf16_wide(const void* x, const void* w, void* y, int64_t y_stride, const void* res, int64_t res_stride,
+                      int M, int N, int K, int epilogue, int flags, void* ws, const mp::EpiArgs& ep,
+                      hipStream_t stream);
+int mp_gemm_t2d_ok(int M, int N, int K, int epilogue, int out_packed, int with_ws);
+int mp_gemm_rw_ok(int M, int N, int K, int epilogue, int out_packed);
+// gemm_w8.hip, gemm_w4.hip, gemm_mx.hip
+int mp_gemm_w8(const void* x, const void* wq, const float* wsc, void* y, int64_t y_stride, const void* res,
+               int64_t res_stride, int M, int N, int K, int epilogue, int flags, void* ws, void* ap, void* ss_out,
+               void* ss_zero, const void* ss_in, float inv_k, float eps, hipStream_t stream);
+int mp_gemm_w4(const void* x, const void* w4, const void* s4, void* y, int64_t y_stride, const void* res,
+               int64_t res_stride, int M, int N, int K, int epilogue, int flags, void* ap, void* ss_out, void* ss_zero,
+               const void* ss_in, float inv_k, float eps, hipStream_t stream);
+int mp_gemm_w4_ok(int M, int N, int K, int epilogue);
+int mp_dequant_w4(const void* w4, const void* s4, void* w, int N, int K, hipStream_t stream);
+int mp_quant_mx(const void* ap, void* ax, void* as, int M, int K, hipStream_t stream);
+int mp_gemm_mx(const void* ax, const void* as, const void* wq, const float* wsc, void* y, int64_t y_stride,
+               const void* res, int64_t res_stride, int M, int N, int K, int epilogue, int flags, void* ws, void* ap,
+               void* ss_out, void* ss_zero, const void* ss_in, float inv_k, float eps, hipStream_t stream);
+// fp8.hip
+void mp_fp8_set_kernel(int kind);
+int mp_quant_act_fp8(const void* ap, void* a8, float* scale, float* part, int M, int K, hipStream_t stream);
+int mp_quant_rows_fp8(const void* x, int64_t xs, void* a8, float* scale, int M, int K, hipStream_t stream);
+int mp_gemm_fp8(const void* a8, const float* as, const void* wq, const float* ws, void* y, int64_t ys, const void* res,
+                int64_t rs, int M, int N, int K, int epilogue, int out_packed, int kind, float* part,
+                int64_t part_bytes, hipStream_t stream);
+}
