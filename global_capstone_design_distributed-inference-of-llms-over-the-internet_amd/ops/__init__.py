@@ -540,7 +540,13 @@ def _kv_f8(k_cache, v_cache) -> bool:
 def _no_kv_f8(k_cache, v_cache, what: str) -> None:
     if isinstance(k_cache, KVF8) or isinstance(v_cache, KVF8):
         raise NotImplementedError(f"ops.{what} has no fp8 KV cache form: an fp8 cache runs on the flash-decoding "
-                                  "kernel (ops.paged_attention / ops.paged_attention_rope)")
+                                  "kernel (ops.paged_attention / ops.paged_attention_rope) or, for GQA decode, on "
+                                  "ops.attention_mfma_f8 / ops.attention_mfma_rope_f8")
+
+
+def _need_kv_f8(k_cache, v_cache, what: str) -> None:
+    if not (isinstance(k_cache, KVF8) and isinstance(v_cache, KVF8)):
+        raise TypeError(f"ops.{what} takes fp8 KV caches (ops.KVF8); bf16 caches run on ops.{what[:-3]}")
 
 
 def rope_kv_write(qkv, positions, cos, sin, k_cache, v_cache, slots, nh, nkv):
@@ -640,16 +646,48 @@ def attention_mfma(q, k_cache, v_cache, block_tables, q_seq, q_ctx, qblocks, nh,
     if part_size is None:
         if max_ctx is None:
             max_ctx = int(q_ctx.max().item()) if T else 1
-        nblk = (superblocks.shape[1] if superblocks is not None else qblocks.shape[1]) * (nh // min(nh // nkv, 16))
-        want = max(1, math.ceil(1024 / max(1, nblk)))
-        num_parts = max(1, min(want, math.ceil(max_ctx / 128)))
-        part_size = 128 * math.ceil(math.ceil(max_ctx / num_parts) / 128)
-        num_parts = math.ceil(max(max_ctx, 1) / part_size)
+        nblk = superblocks.shape[1] if superblocks is not None else qblocks.shape[1]
+        part_size, num_parts = _mfma_partition(nblk, nh, nkv, max_ctx)
     if out is None:
         out = _gemm_out(T, nh * D, packed, q.dtype, q.device)
     workspace = _attn_workspace(workspace, T, nh, D, num_parts, q.device)
     torch.ops.mpamd.attention_mfma(q, k_cache, v_cache, block_tables, q_seq, q_ctx, qblocks, out, workspace, nh, nkv,
                                    float(scale), int(part_size), int(num_parts), int(bool(packed)), superblocks)
+    return out
+
+
+def _mfma_partition(nblocks: int, nh: int, nkv: int, max_ctx: int) -> Tuple[int, int]:
+    """Default (part_size, num_parts) of ``attention_mfma`` / ``attention_mfma_f8``: about 1024
+    workgroups, slices of a multiple of 128 tokens."""
+    nblk = nblocks * (nh // min(nh // nkv, 16))
+    want = max(1, math.ceil(1024 / max(1, nblk)))
+    num_parts = max(1, min(want, math.ceil(max_ctx / 128)))
+    part_size = 128 * math.ceil(math.ceil(max_ctx / num_parts) / 128)
+    return part_size, math.ceil(max(max_ctx, 1) / part_size)
+
+
+def attention_mfma_f8(q, k_cache, v_cache, block_tables, q_seq, q_ctx, qblocks, nh, nkv, scale, out=None,
+                      workspace=None, part_size=None, num_parts=None, max_ctx=None, packed=False):
+    """``attention_mfma`` for GQA decode on an fp8 KV cache (``KVF8``; csrc/attention_mfma.hip F8
+    form): one query token per block (``decode_qblocks``), GQA groups of 4, 8 or a multiple of 16
+    heads.  The kernel converts the codes exactly and then does the bf16 kernel's arithmetic, so the
+    output equals ``attention_mfma`` on the dequantized cache bit for bit."""
+    _need_kv_f8(k_cache, v_cache, "attention_mfma_f8")
+    if not _native(q):
+        return paged_attention(q, k_cache, v_cache, block_tables, q_seq, q_ctx, nh, nkv, scale, out=out,
+                               packed=packed)
+    T = q.shape[0]
+    D = k_cache.shape[-1]
+    if part_size is None:
+        if max_ctx is None:
+            max_ctx = int(q_ctx.max().item()) if T else 1
+        part_size, num_parts = _mfma_partition(qblocks.shape[1], nh, nkv, max_ctx)
+    if out is None:
+        out = _gemm_out(T, nh * D, packed, q.dtype, q.device)
+    workspace = _attn_workspace(workspace, T, nh, D, num_parts, q.device)
+    torch.ops.mpamd.attention_mfma_f8(q, k_cache.codes, v_cache.codes, k_cache.scales, v_cache.scales, block_tables,
+                                      q_seq, q_ctx, qblocks, out, workspace, int(nh), int(nkv), float(scale),
+                                      int(part_size), int(num_parts), int(bool(packed)))
     return out
 
 
@@ -758,6 +796,39 @@ def attention_mfma_rope(qkv, k_cache, v_cache, block_tables, q_seq, q_ctx, qbloc
                                         sin, slots, out, workspace, nh, nkv, float(scale), int(part_size),
                                         int(num_parts), int(bool(packed)), *_qkv_part_args(qkv_part),
                                         *(mx_out if mx_out is not None else (None, None)))
+    return out
+
+
+def attention_mfma_rope_f8(qkv, k_cache, v_cache, block_tables, q_seq, q_ctx, qblocks, positions, cos, sin, slots,
+                           nh, nkv, scale, out=None, workspace=None, part_size=None, num_parts=None, max_ctx=None,
+                           packed=False, qkv_part=None):
+    """``attention_mfma_rope`` on an fp8 KV cache (``KVF8``): the new token's rotated k and its v are
+    quantized per head (``quant_kv_fp8``), written as codes + scale, and attended to through their
+    dequantized values - what every later step reads.  GQA groups of 4, 8 or a multiple of 16 heads;
+    no MX output."""
+    _need_kv_f8(k_cache, v_cache, "attention_mfma_rope_f8")
+    if qkv_part is not None and not _native(qkv):
+        qkv = reduce_qkv_part(qkv_part, qkv.dtype)
+        qkv_part = None
+    if not _native(qkv):
+        q = qkv.clone()
+        ref.rope_kv_write_f8(q, positions, cos, sin, k_cache, v_cache, slots, nh, nkv)
+        return paged_attention(q, k_cache, v_cache, block_tables, q_seq, q_ctx, nh, nkv, scale, out=out,
+                               packed=packed)
+    T = qkv.shape[0]
+    D = k_cache.shape[-1]
+    if part_size is None:
+        if max_ctx is None:
+            max_ctx = int(q_ctx.max().item()) if T else 1
+        part_size = 128 * math.ceil(max(max_ctx, 1) / 128)
+        num_parts = 1
+    if out is None:
+        out = _gemm_out(T, nh * D, packed, qkv.dtype, qkv.device)
+    workspace = _attn_workspace(workspace, T, nh, D, num_parts, qkv.device)
+    torch.ops.mpamd.attention_mfma_rope_f8(qkv, k_cache.codes, v_cache.codes, k_cache.scales, v_cache.scales,
+                                           block_tables, q_seq, q_ctx, qblocks, positions, cos, sin, slots, out,
+                                           workspace, int(nh), int(nkv), float(scale), int(part_size),
+                                           int(num_parts), int(bool(packed)), *_qkv_part_args(qkv_part))
     return out
 
 

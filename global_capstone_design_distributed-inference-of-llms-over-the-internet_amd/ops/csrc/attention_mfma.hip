@@ -35,7 +35,9 @@
 // kernel in attention.hip, measured 12-14 % SLOWER on this kernel at 64 / 256 sessions, cold
 // caches - profiles/r3_i/attn_nt.jsonl vs attn_def.jsonl.)
 #include "common.h"
+#include "kv_f8.h"
 #include "mx_common.h"
+#include <type_traits>
 
 namespace mp {
 
@@ -49,6 +51,8 @@ struct RopeFuseM {
   QkvPart qp;  // qp.part != nullptr: q / k / v from the qkv GEMM's split-K partials (ROPE path)
   uint8_t* mx_ax = nullptr;  // non-null (single-part launches): the output as the W8A8-MX GEMM's
   uint8_t* mx_as = nullptr;  //   activation (mx_common.h) instead of bf16 - the o projection's input
+  uint8_t* ks = nullptr;     // fp8 cache (F8 form): the e8m0 row scales of the code pages kc / vc
+  uint8_t* vs = nullptr;
 };
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_mf;
@@ -64,7 +68,16 @@ constexpr int VT_PITCH = 36;  // bf16 per LDS row of the transposed V tile (32 t
 // compile-time choice: as a run-time one the LDS-or-global q / k / v loads compiled to flat
 // loads, which count against vmcnt, so the RoPE prologue waited for the K / V stream issued
 // before them.
-template <int D, int HB, bool ROPE, bool FOLD = false>
+//
+// F8 (decode blocks): kc / vc hold e4m3 codes and rf.ks / rf.vs one e8m0 scale byte per (token, kv
+// head) (kv_f8.h).  The fragments are the bf16 form's with 8 B per lane instead of 16: the K
+// ping-pong buffers keep the raw codes and a step converts them (exactly, kvf8_dequant8) right
+// before its MFMAs; V is converted before the transposed LDS store.  From there on the arithmetic
+// and its order are the bf16 form's, so the output equals the bf16 kernel's on the dequantized
+// cache bit for bit.  With ROPE the new token's rotated k and its v are quantized by the row rule,
+// the step uses their DEQUANTIZED values (what every later step reads), and the writer stores the
+// codes and the two scale bytes.
+template <int D, int HB, bool ROPE, bool FOLD = false, bool F8 = false>
 __global__ __launch_bounds__(256, 2) void attn_mfma_kernel(
     const bf16_t* __restrict__ q, int64_t q_stride, const bf16_t* __restrict__ kc, const bf16_t* __restrict__ vc,
     const int32_t* __restrict__ block_tables, int bt_stride, const int32_t* __restrict__ q_seq,
@@ -101,27 +114,54 @@ __global__ __launch_bounds__(256, 2) void attn_mfma_kernel(
   for (int i = 0; i < ntok; ++i) blk_ctx = max(blk_ctx, q_ctx[tok0 + i]);
   const int start = p * PS, end = min(start + PS, blk_ctx);
 
-  constexpr int NV = (32 * D * 2) / 1024;  // 16-B V chunks per lane per step
-  auto load_k = [&](int bs, int64_t pg, u16x8 (&kr)[2][KD]) {
-    const bf16_t* kpage = kc + pg * page_stride + head_off + (int64_t)(bs & (page_size - 1)) * D;
+  constexpr int NV = (32 * D * 2) / 1024;  // 8-element V chunks per lane per step
+  // a lane's 8 cache elements: 16 B of bf16, or 8 B of codes (F8) with the token's scale in ke / ve
+  using kv8_t = std::conditional_t<F8, kvf8x8, u16x8>;
+  auto load_k = [&](int bs, int64_t pg, kv8_t (&kr)[2][KD], unsigned (&ke)[2]) {
+    if constexpr (F8) {
+      // (token, kv head) row index = the scale's offset; the row's codes start at row * D bytes
+      const int64_t row0 = (pg * nkv + g) * page_size + (bs & (page_size - 1));
+      const uint8_t* kpage = reinterpret_cast<const uint8_t*>(kc) + row0 * D;
 #pragma unroll
-    for (int sub = 0; sub < 2; ++sub)
+      for (int sub = 0; sub < 2; ++sub) {
 #pragma unroll
-      for (int kd = 0; kd < KD; ++kd)
-        kr[sub][kd] = *reinterpret_cast<const u16x8*>(kpage + (int64_t)(sub * 16 + c) * D + kd * 32 + qd * 8);
+        for (int kd = 0; kd < KD; ++kd)
+          kr[sub][kd] = *reinterpret_cast<const kvf8x8*>(kpage + (int64_t)(sub * 16 + c) * D + kd * 32 + qd * 8);
+        ke[sub] = rf.ks[row0 + sub * 16 + c];
+      }
+    } else {
+      const bf16_t* kpage = kc + pg * page_stride + head_off + (int64_t)(bs & (page_size - 1)) * D;
+#pragma unroll
+      for (int sub = 0; sub < 2; ++sub)
+#pragma unroll
+        for (int kd = 0; kd < KD; ++kd)
+          kr[sub][kd] = *reinterpret_cast<const u16x8*>(kpage + (int64_t)(sub * 16 + c) * D + kd * 32 + qd * 8);
+    }
   };
-  auto load_v = [&](int bs, int64_t pg, u16x8 (&vr)[NV]) {
-    const bf16_t* vpage = vc + pg * page_stride + head_off + (int64_t)(bs & (page_size - 1)) * D;
+  auto load_v = [&](int bs, int64_t pg, kv8_t (&vr)[NV], unsigned& ve) {
+    if constexpr (F8) {
+      const int64_t row0 = (pg * nkv + g) * page_size + (bs & (page_size - 1));
+      const uint8_t* vpage = reinterpret_cast<const uint8_t*>(vc) + row0 * D;
 #pragma unroll
-    for (int i = 0; i < NV; ++i) {
-      const int ci = i * 64 + lane;
-      vr[i] = *reinterpret_cast<const u16x8*>(vpage + (int64_t)(ci % 32) * D + (ci / 32) * 8);
+      for (int i = 0; i < NV; ++i) {
+        const int ci = i * 64 + lane;
+        vr[i] = *reinterpret_cast<const kvf8x8*>(vpage + (int64_t)(ci % 32) * D + (ci / 32) * 8);
+      }
+      ve = rf.vs[row0 + lane % 32];  // ci % 32 == lane % 32 for every i: one token, one scale per lane
+    } else {
+      const bf16_t* vpage = vc + pg * page_stride + head_off + (int64_t)(bs & (page_size - 1)) * D;
+#pragma unroll
+      for (int i = 0; i < NV; ++i) {
+        const int ci = i * 64 + lane;
+        vr[i] = *reinterpret_cast<const u16x8*>(vpage + (int64_t)(ci % 32) * D + (ci / 32) * 8);
+      }
     }
   };
   // K in ping-pong register buffers one step ahead (no register copies: a copy of in-flight
   // loads would force a vmcnt(0) early); a step's V is issued at its top, ahead of the next
   // step's K and the page id two steps ahead, so waiting for it leaves those in flight
-  u16x8 ka[2][KD], kb[2][KD], vr[NV];
+  kv8_t ka[2][KD], kb[2][KD], vr[NV];
+  unsigned kea[2] = {0, 0}, keb[2] = {0, 0}, ve = 0;  // F8: the scale bytes of ka / kb / vr
   int64_t pg_cur = 0, pg_next = 0;
   const int b_first = start + w * 32;
   // The first step's page ids, then (below) the query / RoPE loads, then this step's K AND V:
@@ -189,8 +229,8 @@ __global__ __launch_bounds__(256, 2) void attn_mfma_kernel(
   }
 
   if (b_first < end) {
-    load_k(b_first, pg_cur, ka);
-    load_v(b_first, pg_cur, vr);
+    load_k(b_first, pg_cur, ka, kea);
+    load_v(b_first, pg_cur, vr, ve);
   }
 
   if constexpr (from_part) {
@@ -226,6 +266,26 @@ __global__ __launch_bounds__(256, 2) void attn_mfma_kernel(
     u16x8 qr[KD], kn[KD];
     rot(qf, qr);
     rot(kr, kn);
+    kvf8x8 kq[F8 ? KD : 1], vq;
+    int ek = 0, ev = 0;
+    if constexpr (F8) {
+      // the row rule on the rotated, bf16-rounded key (every c lane holds the same KD chunks; the
+      // 4 qd lanes of a c hold the row) and on the value (its row sits in D / 8 consecutive lanes)
+      float am = 0.f;
+#pragma unroll
+      for (int kd = 0; kd < KD; ++kd) am = fmaxf(am, kvf8_amax8(kn[kd]));
+      am = fmaxf(am, __shfl_xor(am, 16, 64));
+      am = fmaxf(am, __shfl_xor(am, 32, 64));
+      ek = mx_e8m0(am);
+      ev = mx_e8m0(kvf8_group_max<D / 8>(kvf8_amax8(vn)));
+#pragma unroll
+      for (int kd = 0; kd < KD; ++kd) {
+        kq[kd] = kvf8_quant8(kn[kd], ek);
+        kn[kd] = kvf8_dequant8(kq[kd], (unsigned)ek);
+      }
+      vq = kvf8_quant8(vn, ev);
+      vn = kvf8_dequant8(vq, (unsigned)ev);
+    }
 #pragma unroll
     for (int kd = 0; kd < KD; ++kd) qf[kd] = row_ok ? qr[kd] : (u16x8)(0);
     float part = 0.f;
@@ -239,12 +299,27 @@ __global__ __launch_bounds__(256, 2) void attn_mfma_kernel(
     tnew = blk_ctx - 1;
     const int64_t slot = kv_slot;
     if (w == 0 && tnew >= start && tnew < end && slot >= 0 && hbase % (nh / nkv) == 0) {
-      const int64_t dst = (slot >> page_log2) * page_stride + head_off + (slot & (page_size - 1)) * D;
-      if (c == 0) {
+      if constexpr (F8) {
+        const int64_t row = ((slot >> page_log2) * nkv + g) * page_size + (slot & (page_size - 1));
+        uint8_t* kdst = reinterpret_cast<uint8_t*>(rf.kw) + row * D;
+        uint8_t* vdst = reinterpret_cast<uint8_t*>(rf.vw) + row * D;
+        if (c == 0) {
 #pragma unroll
-        for (int kd = 0; kd < KD; ++kd) *reinterpret_cast<u16x8*>(rf.kw + dst + kd * 32 + qd * 8) = kn[kd];
+          for (int kd = 0; kd < KD; ++kd) *reinterpret_cast<kvf8x8*>(kdst + kd * 32 + qd * 8) = kq[kd];
+        }
+        if (lane * 8 < D) *reinterpret_cast<kvf8x8*>(vdst + lane * 8) = vq;
+        if (lane == 0) {
+          rf.ks[row] = (uint8_t)ek;
+          rf.vs[row] = (uint8_t)ev;
+        }
+      } else {
+        const int64_t dst = (slot >> page_log2) * page_stride + head_off + (slot & (page_size - 1)) * D;
+        if (c == 0) {
+#pragma unroll
+          for (int kd = 0; kd < KD; ++kd) *reinterpret_cast<u16x8*>(rf.kw + dst + kd * 32 + qd * 8) = kn[kd];
+        }
+        if (lane * 8 < D) *reinterpret_cast<u16x8*>(rf.vw + dst + lane * 8) = vn;
       }
-      if (lane * 8 < D) *reinterpret_cast<u16x8*>(rf.vw + dst + lane * 8) = vn;
     }
   }
 
@@ -260,14 +335,19 @@ __global__ __launch_bounds__(256, 2) void attn_mfma_kernel(
   // At decode sizes every wave has one or two steps: the chain, not the bytes, set the time
   // (Llama-3-70B, 64 sessions: 16.9 us per layer for 37 MB of K/V).
   // one 32-token step over K / V fragments already in registers
-  auto step = [&](int b0, const u16x8 (&kr)[2][KD], const u16x8 (&vr)[NV]) {
+  auto step = [&](int b0, const kv8_t (&kr)[2][KD], const unsigned (&ke)[2], const kv8_t (&vr)[NV], unsigned ve) {
     // ---- S^T = K . Q^T for tokens b0 .. b0+31 (two 16-token subtiles) ----
+    // (F8: a page tail's 0xFF codes / scales convert to NaN; like a bf16 cache's stale bytes they
+    // stay in their own token's score, which the mask below replaces)
     f32x4 st[2];
 #pragma unroll
     for (int sub = 0; sub < 2; ++sub) {
       st[sub] = (f32x4)(0.f);
 #pragma unroll
-      for (int kd = 0; kd < KD; ++kd) st[sub] = mfma_bf16(kr[sub][kd], qf[kd], st[sub]);
+      for (int kd = 0; kd < KD; ++kd) {
+        if constexpr (F8) st[sub] = mfma_bf16(kvf8_dequant8(kr[sub][kd], ke[sub]), qf[kd], st[sub]);
+        else st[sub] = mfma_bf16(kr[sub][kd], qf[kd], st[sub]);
+      }
     }
     // ---- V tile -> LDS transposed [d][tok] (this wave only; in-order LDS needs no barrier) ----
     // tokens vary fastest across lanes: each half-wave's transposed stores are 32 consecutive
@@ -276,7 +356,9 @@ __global__ __launch_bounds__(256, 2) void attn_mfma_kernel(
     for (int i = 0; i < NV; ++i) {
       const int ci = i * 64 + lane;
       const int tk = ci % 32, d0 = (ci / 32) * 8;
-      u16x8 vv = vr[i];
+      u16x8 vv;
+      if constexpr (F8) vv = kvf8_dequant8(vr[i], ve);
+      else vv = vr[i];
       if (b0 + tk >= end) vv = (u16x8)(0);
 #pragma unroll
       for (int e = 0; e < 8; ++e) vt[(d0 + e) * VT_PITCH + tk] = vv[e];
@@ -343,22 +425,22 @@ __global__ __launch_bounds__(256, 2) void attn_mfma_kernel(
   };
   for (int b0 = b_first; b0 < end; b0 += 256) {
     const bool more1 = b0 + 128 < end;
-    if (b0 != b_first) load_v(b0, pg_cur, vr);
+    if (b0 != b_first) load_v(b0, pg_cur, vr, ve);
     int64_t pg2 = 0;
     if (more1) {
-      load_k(b0 + 128, pg_next, kb);
+      load_k(b0 + 128, pg_next, kb, keb);
       if (b0 + 256 < end) pg2 = bt[(b0 + 256) >> page_log2];
     }
-    step(b0, ka, vr);
+    step(b0, ka, kea, vr, ve);
     if (!more1) break;
     const bool more2 = b0 + 256 < end;
-    load_v(b0 + 128, pg_next, vr);
+    load_v(b0 + 128, pg_next, vr, ve);
     int64_t pg3 = 0;
     if (more2) {
-      load_k(b0 + 256, pg2, ka);
+      load_k(b0 + 256, pg2, ka, kea);
       if (b0 + 384 < end) pg3 = bt[(b0 + 384) >> page_log2];
     }
-    step(b0 + 128, kb, vr);
+    step(b0 + 128, kb, keb, vr, ve);
     pg_cur = pg2;
     pg_next = pg3;
   }
@@ -626,6 +708,21 @@ static void launch_attn_mfma(const AttnArgs& a, int page_log2, const RopeFuseM& 
   else go(attn_mfma_kernel<D, HB, false, false>);
 }
 
+// The fp8 cache form: decode blocks only (one token per block), so no superblocks; HB 4 / 8 / 16.
+template <int D, int HB>
+static void launch_attn_mfma_f8(const AttnArgs& a, int page_log2, const RopeFuseM& rf, const int32_t* qb_tok0,
+                                const int32_t* qb_ntok, int NB, hipStream_t stream) {
+  auto go = [&](auto kern) {
+    hipLaunchKernelGGL(kern, dim3(NB, a.nh / HB, a.NP), dim3(256), 0, stream, (const bf16_t*)a.q, a.q_stride,
+                       (const bf16_t*)a.kc, (const bf16_t*)a.vc, a.bt, a.bt_stride, a.q_seq, a.q_ctx, qb_tok0, qb_ntok,
+                       (bf16_t*)a.out, a.workspace, attn_ws_ml(a), a.nkv, a.nh, page_log2, a.PS, a.NP,
+                       attn_scale_log2(a), a.packed_mt, rf);
+  };
+  if (rf.pos && rf.qp.part) go(attn_mfma_kernel<D, HB, true, true, true>);
+  else if (rf.pos) go(attn_mfma_kernel<D, HB, true, false, true>);
+  else go(attn_mfma_kernel<D, HB, false, false, true>);
+}
+
 __global__ void paged_attn_reduce_kernel(const float* __restrict__ part_o, const float* __restrict__ part_ml,
                                          bf16_t* __restrict__ out, int NP, int D, int nh, int packed_mt);
 
@@ -635,6 +732,8 @@ __global__ void paged_attn_reduce_kernel(const float* __restrict__ part_o, const
 // (<= 16 / heads_per_block, all from one sequence).  heads_per_block = min(nh / nkv, 16).
 // Superblocks (optional, prefill): sb_first[j] / sb_n[j] = runs of <= 8 consecutive query blocks
 // of one sequence, one workgroup each (attn_mfma_grp_kernel).
+// a.ks != nullptr: the fp8 cache's code pages (kv_f8.h) - decode blocks of one token each (the caller
+// builds them so), GQA groups of 4 / 8 / 16+ heads, no superblocks, no MX output.
 extern "C" int mp_attention_mfma(const mp::AttnArgs* args, const int32_t* qb_tok0, const int32_t* qb_ntok, int NB,
                                  const int32_t* sb_first, const int32_t* sb_n, int NSB, void* mx_ax, void* mx_as,
                                  hipStream_t stream) {
@@ -651,6 +750,11 @@ extern "C" int mp_attention_mfma(const mp::AttnArgs* args, const int32_t* qb_tok
     rf.mx_ax = (uint8_t*)mx_ax;
     rf.mx_as = (uint8_t*)mx_as;
   }
+  const bool f8 = a.ks != nullptr;
+  if (f8 && (a.vs == nullptr || mx_ax != nullptr)) return -8;  // no MX epilogue on an fp8 cache
+  if (f8 && sb_first != nullptr && NSB > 0) return -9;       // the grouped prefill kernel has no fp8 form
+  rf.ks = (uint8_t*)a.ks;
+  rf.vs = (uint8_t*)a.vs;
   if (NB == 0 || a.T == 0) return 0;
   if (a.nh % a.nkv != 0 || a.PS % 128 != 0 || a.NP < 1 || a.page_size % 32 != 0) return -1;
   const int page_log2 = attn_page_log2(a);
@@ -660,6 +764,22 @@ extern "C" int mp_attention_mfma(const mp::AttnArgs* args, const int32_t* qb_tok
   // several workgroups that re-read the same K / V measured 1.6-2.7x slower, profiles/r4k)
   const int hb = nrep >= 16 ? 16 : nrep;
   if (nrep % hb) return -3;
+  if (f8) {
+    if (hb != 4 && hb != 8 && hb != 16) return -10;
+#define MP_AM_F8_CASE(DD, HH)                                                            \
+  if (a.D == DD && hb == HH) {                                                           \
+    launch_attn_mfma_f8<DD, HH>(a, page_log2, rf, qb_tok0, qb_ntok, NB, stream);         \
+    goto launched;                                                                       \
+  }
+    MP_AM_F8_CASE(128, 4)
+    MP_AM_F8_CASE(128, 8)
+    MP_AM_F8_CASE(128, 16)
+    MP_AM_F8_CASE(64, 4)
+    MP_AM_F8_CASE(64, 8)
+    MP_AM_F8_CASE(64, 16)
+#undef MP_AM_F8_CASE
+    return -4;
+  }
 #define MP_AM_CASE(DD, HH)                                                                                  \
   if (a.D == DD && hb == HH) {                                                                              \
     launch_attn_mfma<DD, HH>(a, page_log2, rf, qb_tok0, qb_ntok, NB, sb_first, sb_n, NSB, stream);          \

@@ -478,6 +478,44 @@ void attention_mfma_rope(const at::Tensor& qkv, at::Tensor& k_cache, at::Tensor&
   launch_mfma(a, qblocks, c10::nullopt, axp, asp);
 }
 
+// The fp8 cache forms of the two above (attention_mfma.hip F8 form): decode blocks only (one token
+// per query block), the whole GQA group in the MFMA rows - no superblocks, no MX output.
+inline void check_mfma_f8(const at::Tensor& q, const at::Tensor& qblocks, int64_t nh, int64_t nkv) {
+  MP_CHECK(nkv > 0 && nh % nkv == 0 && (nh / nkv == 4 || nh / nkv == 8 || (nh / nkv >= 16 && (nh / nkv) % 16 == 0)),
+           "attention_mfma on an fp8 KV cache supports GQA group sizes nh / nkv of 4, 8 and multiples of 16");
+  MP_CHECK(qblocks.dim() == 2 && qblocks.size(1) == q.size(0),
+           "attention_mfma on an fp8 KV cache needs one query token per block (decode)");
+}
+
+void attention_mfma_f8(const at::Tensor& q, const at::Tensor& k_cache, const at::Tensor& v_cache,
+                       const at::Tensor& k_scale, const at::Tensor& v_scale, const at::Tensor& block_tables,
+                       const at::Tensor& q_seq, const at::Tensor& q_ctx, const at::Tensor& qblocks, at::Tensor& out,
+                       at::Tensor& workspace, int64_t nh, int64_t nkv, double scale, int64_t part_size,
+                       int64_t num_parts, int64_t packed) {
+  check_kv_f8(k_cache, v_cache, k_scale, v_scale, nkv);
+  check_mfma_f8(q, qblocks, nh, nkv);
+  launch_mfma(attn_args(q, k_cache, v_cache, block_tables, q_seq, q_ctx, out, workspace, nh, nkv, scale, part_size,
+                        num_parts, packed, &k_scale, &v_scale),
+              qblocks, c10::nullopt);
+}
+
+void attention_mfma_rope_f8(const at::Tensor& qkv, at::Tensor& k_cache, at::Tensor& v_cache, at::Tensor& k_scale,
+                            at::Tensor& v_scale, const at::Tensor& block_tables, const at::Tensor& q_seq,
+                            const at::Tensor& q_ctx, const at::Tensor& qblocks, const at::Tensor& positions,
+                            const at::Tensor& cos, const at::Tensor& sin, const at::Tensor& slots, at::Tensor& out,
+                            at::Tensor& workspace, int64_t nh, int64_t nkv, double scale, int64_t part_size,
+                            int64_t num_parts, int64_t packed, const c10::optional<at::Tensor>& qkv_part,
+                            int64_t part_splits, const c10::optional<at::Tensor>& part_ss, double inv_k, double eps) {
+  check_kv_f8(k_cache, v_cache, k_scale, v_scale, nkv);
+  check_mfma_f8(qkv, qblocks, nh, nkv);
+  check_rope(qkv, positions, cos, sin, slots, nh, nkv, k_cache.size(3));
+  const mp::QkvPart qp = qkv_part_args(qkv_part, part_splits, part_ss, inv_k, eps, qkv.size(0), qkv.size(1));
+  mp::AttnArgs a = attn_args(qkv, k_cache, v_cache, block_tables, q_seq, q_ctx, out, workspace, nh, nkv, scale,
+                             part_size, num_parts, packed, &k_scale, &v_scale);
+  fuse_rope(a, positions, cos, sin, slots, qp);
+  launch_mfma(a, qblocks, c10::nullopt);
+}
+
 void embedding(const at::Tensor& ids, const at::Tensor& table, at::Tensor& out) {
   check_bf16_cuda(table, "table");
   check_bf16_cuda(out, "out");
@@ -860,6 +898,16 @@ TORCH_LIBRARY(mpamd, m) {
       "Tensor(d!) workspace, int nh, int nkv, float scale, int part_size, int num_parts, int packed, "
       "Tensor? qkv_part=None, int part_splits=0, Tensor? part_ss=None, float inv_k=0., float eps=0., "
       "Tensor(e!)? mx_ax=None, Tensor(f!)? mx_as=None) -> ()");
+  m.def(
+      "attention_mfma_f8(Tensor q, Tensor k_cache, Tensor v_cache, Tensor k_scale, Tensor v_scale, "
+      "Tensor block_tables, Tensor q_seq, Tensor q_ctx, Tensor qblocks, Tensor(a!) out, Tensor(b!) workspace, int nh, "
+      "int nkv, float scale, int part_size, int num_parts, int packed) -> ()");
+  m.def(
+      "attention_mfma_rope_f8(Tensor qkv, Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor(c!) k_scale, "
+      "Tensor(d!) v_scale, Tensor block_tables, Tensor q_seq, Tensor q_ctx, Tensor qblocks, Tensor positions, "
+      "Tensor cos, Tensor sin, Tensor slots, Tensor(e!) out, Tensor(f!) workspace, int nh, int nkv, float scale, "
+      "int part_size, int num_parts, int packed, Tensor? qkv_part=None, int part_splits=0, Tensor? part_ss=None, "
+      "float inv_k=0., float eps=0.) -> ()");
   m.def("embedding(Tensor ids, Tensor table, Tensor(a!) out) -> ()");
   m.def("swiglu(Tensor gu, Tensor(a!) out) -> ()");
   m.def("add(Tensor a, Tensor b, Tensor(a!) y) -> ()");
@@ -907,6 +955,8 @@ TORCH_LIBRARY_IMPL(mpamd, CUDA, m) {
   m.impl("attention_mfma", &attention_mfma);
   m.impl("attention_fa", &attention_fa);
   m.impl("attention_mfma_rope", &attention_mfma_rope);
+  m.impl("attention_mfma_f8", &attention_mfma_f8);
+  m.impl("attention_mfma_rope_f8", &attention_mfma_rope_f8);
   m.impl("embedding", &embedding);
   m.impl("swiglu", &swiglu);
   m.impl("add", &add);

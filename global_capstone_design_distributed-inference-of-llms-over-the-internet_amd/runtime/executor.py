@@ -221,8 +221,12 @@ class StageExecutor:
         self._attn_mfma_gqa = self._attn_mfma_prefill and self.nh // self.nkv >= 4
         # decode steps of GQA models on the MFMA kernel (a lab script may flip this before the
         # first decode step to A/B the flash-decoding kernel)
-        # (an fp8 KV cache has the flash-decoding kernel only: no MFMA GQA decode, no MX epilogue)
+        # (an fp8 KV cache runs none of the bf16 MFMA kernels and has no MX epilogue)
         self.gqa_decode_mfma = self._attn_mfma_gqa and not self._kv_fp8
+        # ... and on an fp8 KV cache the kernel's fp8 form (decode steps only; prefill stays on the
+        # flash-decoding kernel); MPAMD_KV_FP8_MFMA=0 keeps the flash-decoding kernel there too
+        self.gqa_decode_mfma_f8 = self._attn_mfma_gqa and self._kv_fp8 and \
+            os.environ.get("MPAMD_KV_FP8_MFMA", "1") != "0"
         # prefill: up to 4 query blocks of a sequence per workgroup share each K/V step
         # (csrc/attention_mfma.hip attn_mfma_grp_kernel)
         self._attn_grouped = True
@@ -238,7 +242,7 @@ class StageExecutor:
         # decode steps on the flash-decoding kernel fold RoPE + the KV page write into it
         self._fuse_rope = True
         # shortest split-K context slice (ops.attention_partition): longer on the MFMA GQA kernel
-        self._attn_min_part = 256 if self.gqa_decode_mfma else 64
+        self._attn_min_part = 256 if (self.gqa_decode_mfma or self.gqa_decode_mfma_f8) else 64
         self._decode_qb: Dict[int, torch.Tensor] = {}
         self._moe_y: Dict[int, torch.Tensor] = {}
         self.timing = False
@@ -529,9 +533,16 @@ class StageExecutor:
 
     def _attend(self, qkv, kc, vc, q_seq, q_ctx, out, ws, ps, np_, packed, qblocks, max_ctx):
         """Paged attention: MFMA flash attention for prefill blocks (``qblocks``) and GQA decode,
-        else the flash-decoding kernel - which is also the one kernel of an fp8 KV cache: its
-        prefill blocks run as per-query causal rows (``qblocks`` and the FA blocks are ignored)."""
+        else the flash-decoding kernel.  An fp8 KV cache has the fp8 forms of the MFMA GQA decode
+        kernel and of the flash-decoding kernel; its prefill blocks run on the latter as per-query
+        causal rows (``qblocks`` and the FA blocks are ignored)."""
         table = self.sessions.table_dev
+        if qblocks is None and self.gqa_decode_mfma_f8 and self.device.type == "cuda":
+            ps2 = 128 * math.ceil(ps / 128)
+            np2 = max(1, math.ceil(ps * np_ / ps2))
+            return ops.attention_mfma_f8(qkv, kc, vc, table, q_seq, q_ctx, self.decode_qblocks(qkv.shape[0]), self.nh,
+                                         self.nkv, self.scale, out=out, workspace=ws, part_size=ps2, num_parts=np2,
+                                         packed=packed)
         if self._kv_fp8:
             return ops.paged_attention(qkv, kc, vc, table, q_seq, q_ctx, self.nh, self.nkv, self.scale, out=out,
                                        workspace=ws, part_size=ps, num_parts=np_, packed=packed)
@@ -583,6 +594,13 @@ class StageExecutor:
                                            positions, self.cos, self.sin, slots, self.nh, self.nkv, self.scale,
                                            out=out, workspace=ws, part_size=ps2, num_parts=np2, packed=packed,
                                            qkv_part=qkv_part, mx_out=mx)
+        if decode and qblocks is None and self._fuse_rope and self.gqa_decode_mfma_f8 and self.device.type == "cuda":
+            ps2 = 128 * math.ceil(ps / 128)
+            np2 = max(1, math.ceil(ps * np_ / ps2))
+            return ops.attention_mfma_rope_f8(qkv, kc, vc, self.sessions.table_dev, q_seq, q_ctx,
+                                              self.decode_qblocks(qkv.shape[0]), positions, self.cos, self.sin, slots,
+                                              self.nh, self.nkv, self.scale, out=out, workspace=ws, part_size=ps2,
+                                              num_parts=np2, packed=packed, qkv_part=qkv_part)
         if decode and qblocks is None and self._fuse_rope and not (
                 self.gqa_decode_mfma and not self._kv_fp8 and self.device.type == "cuda"):
             return ops.paged_attention_rope(qkv, kc, vc, self.sessions.table_dev, q_seq, q_ctx, positions, self.cos,
@@ -1316,7 +1334,7 @@ class _DecodeGraph:
         h32[2 * B:] = np.arange(B, dtype=np.int32)
         self.blob.copy_(self._stage[0])
         self._stage[1].copy_(self._stage[0])
-        if ex.gqa_decode_mfma:
+        if ex.gqa_decode_mfma or ex.gqa_decode_mfma_f8:
             ex.decode_qblocks(B)  # allocated outside the capture
         self.bufs: dict = {}
         self.done_ev = None  # end of the last replay on the compute stream (graph_input)

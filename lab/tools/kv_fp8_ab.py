@@ -7,9 +7,12 @@ us per call and achieved cache bytes/s of
   bf16  the fused decode attention the executor runs for that model: ``ops.paged_attention_rope``
         (MHA, flash-decoding kernel) or ``ops.attention_mfma_rope`` (GQA, MFMA kernel), with the
         executor's context partition;
-  fp8   ``ops.paged_attention_rope`` on the fp8 cache (the flash-decoding kernel's fp8 form).
+  fp8   ``ops.paged_attention_rope`` on the fp8 cache (the flash-decoding kernel's fp8 form);
+  fp8_mfma  (GQA heads only) ``ops.attention_mfma_rope_f8``: the MFMA kernel's fp8 form, with the bf16
+        side's partition - what the executor runs for a GQA model on an fp8 cache; ``fp8`` is then
+        what it ran before that form existed (MPAMD_KV_FP8_MFMA=0).
 
-The two alternate inside one process, ``--repeats`` times; a row carries every repeat's time, so the
+The sides alternate inside one process, ``--repeats`` times; a row carries every repeat's time, so the
 spread is visible.  One JSON line per (case, format).
 
     python lab/tools/kv_fp8_ab.py --repeats 3
@@ -25,7 +28,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 from src import ops  # noqa: E402
 
-HEADS = {"llama2-7b": (32, 32, 128), "llama3-70b": (64, 8, 128)}
+HEADS = {"llama2-7b": (32, 32, 128), "llama3-70b": (64, 8, 128), "llama3-8b": (32, 8, 128)}
 CASES = [(64, 170), (64, 2048), (64, 4096), (1, 4096)]  # (sessions, context tokens)
 POOL = 1 << 30  # bytes of fp8 pages the copies cover at least (4 x the last-level cache)
 PS = 64
@@ -104,12 +107,21 @@ def main():
                 ops.paged_attention_rope(qkv, kf, vf, perm[c], q_seq, q_ctx, pos, cos, sin, slots[c], nh, nkv, scale,
                                          out=out, workspace=ws, part_size=ps8, num_parts=np8, packed=True)
 
-            us = {"bf16": [], "fp8": []}
+            def fp8_mfma(c):
+                ps2 = 128 * math.ceil(ps / 128)
+                ops.attention_mfma_rope_f8(qkv, kf, vf, perm[c], q_seq, q_ctx, qb, pos, cos, sin, slots[c], nh, nkv,
+                                           scale, out=out, workspace=ws, part_size=ps2,
+                                           num_parts=max(1, math.ceil(ps * np_ / ps2)), packed=True)
+
+            sides = [("bf16", bf16, bytes_bf, "attention_mfma_rope" if gqa else "paged_attention_rope"),
+                     ("fp8", fp8, bytes_f8, "paged_attention_rope_f8")]
+            if gqa:
+                sides.append(("fp8_mfma", fp8_mfma, bytes_f8, "attention_mfma_rope_f8"))
+            us = {label: [] for label, _, _, _ in sides}
             for _ in range(a.repeats):
-                us["bf16"].append(round(_time(bf16, copies, a.iters), 2))
-                us["fp8"].append(round(_time(fp8, copies, a.iters), 2))
-            for label, nbytes, kern in (("bf16", bytes_bf, "attention_mfma_rope" if gqa else "paged_attention_rope"),
-                                        ("fp8", bytes_f8, "paged_attention_rope_f8")):
+                for label, fn, _, _ in sides:
+                    us[label].append(round(_time(fn, copies, a.iters), 2))
+            for label, _, nbytes, kern in sides:
                 best = min(us[label])
                 print(json.dumps({"heads": model, "nh": nh, "nkv": nkv, "D": D, "sessions": B, "ctx": ctx,
                                   "kv": label, "kernel": kern, "copies": copies, "cache_bytes": nbytes,
