@@ -539,9 +539,10 @@ def _kv_f8(k_cache, v_cache) -> bool:
 
 def _no_kv_f8(k_cache, v_cache, what: str) -> None:
     if isinstance(k_cache, KVF8) or isinstance(v_cache, KVF8):
-        raise NotImplementedError(f"ops.{what} has no fp8 KV cache form: an fp8 cache runs on the flash-decoding "
-                                  "kernel (ops.paged_attention / ops.paged_attention_rope) or, for GQA decode, on "
-                                  "ops.attention_mfma_f8 / ops.attention_mfma_rope_f8")
+        raise NotImplementedError(f"ops.{what} does not read an fp8 KV cache: an fp8 cache runs on the flash-decoding "
+                                  "kernel (ops.paged_attention / ops.paged_attention_rope), for GQA decode on "
+                                  "ops.attention_mfma_f8 / ops.attention_mfma_rope_f8, for prefill on "
+                                  "ops.attention_fa_f8")
 
 
 def _need_kv_f8(k_cache, v_cache, what: str) -> None:
@@ -740,6 +741,24 @@ def attention_fa(q, k_cache, v_cache, block_tables, q_seq, q_ctx, fablocks, nh, 
     ``fablocks`` from ``fa_blocks`` (device int32 [2, NB]).  The context is split over parts
     only when the grid would leave CUs idle."""
     _no_kv_f8(k_cache, v_cache, "attention_fa")
+    return _attention_fa(q, k_cache, v_cache, block_tables, q_seq, q_ctx, fablocks, nh, nkv, scale, out, workspace,
+                         max_ctx, waves, num_parts, pair)
+
+
+def attention_fa_f8(q, k_cache, v_cache, block_tables, q_seq, q_ctx, fablocks, nh, nkv, scale, out=None,
+                    workspace=None, max_ctx=None, waves=None, num_parts=None, pair=None):
+    """``attention_fa`` on an fp8 KV cache (``KVF8``; csrc/attention_fa.hip F8 form), with the same
+    blocks, parts and pairing.  The kernel converts the codes exactly while staging them into the LDS
+    tiles and then does the bf16 kernel's arithmetic, so the output equals ``attention_fa`` on the
+    dequantized cache bit for bit."""
+    _need_kv_f8(k_cache, v_cache, "attention_fa_f8")
+    return _attention_fa(q, k_cache, v_cache, block_tables, q_seq, q_ctx, fablocks, nh, nkv, scale, out, workspace,
+                         max_ctx, waves, num_parts, pair)
+
+
+def _attention_fa(q, k_cache, v_cache, block_tables, q_seq, q_ctx, fablocks, nh, nkv, scale, out, workspace, max_ctx,
+                  waves, num_parts, pair):
+    """``attention_fa`` / ``attention_fa_f8``: the partition and pairing rules and the launch."""
     if not _native(q):
         return paged_attention(q, k_cache, v_cache, block_tables, q_seq, q_ctx, nh, nkv, scale, out=out)
     T = q.shape[0]
@@ -758,8 +777,12 @@ def attention_fa(q, k_cache, v_cache, block_tables, q_seq, q_ctx, fablocks, nh, 
     workspace = _attn_workspace(workspace, T, nh, D, num_parts, q.device)
     if pair is None:
         pair = fa_pair(int(fablocks.shape[1]), nh, nkv, num_parts)
-    torch.ops.mpamd.attention_fa(q, k_cache, v_cache, block_tables, q_seq, q_ctx, fablocks, out, workspace, nh, nkv,
-                                 float(scale), int(part_size), int(num_parts), waves, int(bool(pair) and num_parts == 1))
+    tail = (block_tables, q_seq, q_ctx, fablocks, out, workspace, int(nh), int(nkv), float(scale), int(part_size),
+            int(num_parts), waves, int(bool(pair) and num_parts == 1))
+    if isinstance(k_cache, KVF8):
+        torch.ops.mpamd.attention_fa_f8(q, k_cache.codes, v_cache.codes, k_cache.scales, v_cache.scales, *tail)
+    else:
+        torch.ops.mpamd.attention_fa(q, k_cache, v_cache, *tail)
     return out
 
 

@@ -23,7 +23,17 @@
 //   * causal skipping: a wave stops computing at its own rows' context (the diagonal steps
 //     of the earlier waves), workgroups are launched longest-context first.
 // Splits of the context (NP > 1) write (m, l, O) partials reduced by paged_attn_reduce_kernel.
+//
+// F8 (fp8 KV cache, kv_f8.h): kc / vc hold e4m3 codes and ks / vs one e8m0 scale byte per (token, kv
+// head).  Only the staging differs: a lane fetches the 8 code bytes of each of its chunks plus the
+// row's scale byte (half the registers held across the step's compute), and converts them (exactly,
+// kvf8_dequant8) right before the LDS store.  The LDS image is the one the bf16 form builds on a bf16
+// cache of the dequantized values, and everything after it is shared, so the output equals the bf16
+// form's on that cache bit for bit.
+#include <type_traits>
+
 #include "common.h"
+#include "kv_f8.h"
 
 namespace mp {
 
@@ -61,13 +71,14 @@ __device__ __forceinline__ unsigned pk_bf16(float a, float b) {
 
 constexpr float FA_RESCALE_THR = 8.f;  // log2 units: P may reach 2^8 before O / l are rescaled (T13)
 
-template <int HB, int NW>
+template <int HB, int NW, bool F8 = false>
 __global__ __launch_bounds__(NW * 64) void attn_fa_kernel(
     const bf16_t* __restrict__ q, int64_t q_stride, const bf16_t* __restrict__ kc, const bf16_t* __restrict__ vc,
     const int32_t* __restrict__ block_tables, int bt_stride, const int32_t* __restrict__ q_seq,
     const int32_t* __restrict__ q_ctx, const int32_t* __restrict__ fb_tok0, const int32_t* __restrict__ fb_ntok,
     int NBF, bf16_t* __restrict__ out, int64_t out_stride, float* __restrict__ part_o, float* __restrict__ part_ml,
-    int nkv, int nh, int page_log2, int PS, int NP, float scale_log2, int pair) {
+    int nkv, int nh, int page_log2, int PS, int NP, float scale_log2, int pair, const uint8_t* __restrict__ ks,
+    const uint8_t* __restrict__ vs) {
   constexpr int D = 128;
   constexpr int STEP = 64;
   constexpr int TILE = STEP * D * 2;            // bytes of one K or V tile (16 KiB)
@@ -129,16 +140,35 @@ __global__ __launch_bounds__(NW * 64) void attn_fa_kernel(
   for (int dt = 0; dt < D / 32; ++dt) o[dt] = (f32x16)(0.f);
   float m = -INFINITY, l = 0.f;  // running max (log2 units, scale applied) and sum of row r
 
-  u16x8 kreg[CPT], vreg[CPT];
+  // a chunk in flight: 16 B of bf16, or 8 B of codes (F8) with its row's scale byte in ke / ve
+  using kv8_t = std::conditional_t<F8, kvf8x8, u16x8>;
+  kv8_t kreg[CPT], vreg[CPT];
+  unsigned ke[F8 ? CPT : 1], ve[F8 ? CPT : 1];
   auto fetch = [&](int s0) {
     const int64_t pg = bt[s0 >> page_log2];
-    const bf16_t* kp = kc + pg * page_stride + head_off + (int64_t)(s0 & (page_size - 1)) * D;
-    const bf16_t* vp = vc + pg * page_stride + head_off + (int64_t)(s0 & (page_size - 1)) * D;
+    if constexpr (F8) {
+      const int row0 = s0 & (page_size - 1);
+      const int64_t code_off = pg * page_stride + head_off + (int64_t)row0 * D;  // one byte per element
+      const uint8_t* kp = reinterpret_cast<const uint8_t*>(kc) + code_off;
+      const uint8_t* vp = reinterpret_cast<const uint8_t*>(vc) + code_off;
+      const int64_t scale_off = (pg * nkv + g) * page_size + row0;
 #pragma unroll
-    for (int j = 0; j < CPT; ++j) {
-      const int c = tid + NT * j, row = c >> 4, ch = c & 15;
-      kreg[j] = *reinterpret_cast<const u16x8*>(kp + row * D + ch * 8);
-      vreg[j] = *reinterpret_cast<const u16x8*>(vp + row * D + ch * 8);
+      for (int j = 0; j < CPT; ++j) {
+        const int c = tid + NT * j, row = c >> 4, ch = c & 15;
+        kreg[j] = *reinterpret_cast<const kvf8x8*>(kp + row * D + ch * 8);
+        vreg[j] = *reinterpret_cast<const kvf8x8*>(vp + row * D + ch * 8);
+        ke[j] = ks[scale_off + row];
+        ve[j] = vs[scale_off + row];
+      }
+    } else {
+      const bf16_t* kp = kc + pg * page_stride + head_off + (int64_t)(s0 & (page_size - 1)) * D;
+      const bf16_t* vp = vc + pg * page_stride + head_off + (int64_t)(s0 & (page_size - 1)) * D;
+#pragma unroll
+      for (int j = 0; j < CPT; ++j) {
+        const int c = tid + NT * j, row = c >> 4, ch = c & 15;
+        kreg[j] = *reinterpret_cast<const u16x8*>(kp + row * D + ch * 8);
+        vreg[j] = *reinterpret_cast<const u16x8*>(vp + row * D + ch * 8);
+      }
     }
   };
   auto stash = [&](int buf, int s0) {
@@ -147,8 +177,16 @@ __global__ __launch_bounds__(NW * 64) void attn_fa_kernel(
     for (int j = 0; j < CPT; ++j) {
       const int c = tid + NT * j, row = c >> 4, ch = c & 15;
       const bool past = s0 + row >= end;  // past the context: stale cache bytes never meet a p = 0
-      *reinterpret_cast<u16x8*>(kb + fa_off(row, ch)) = past ? (u16x8)(0) : kreg[j];
-      *reinterpret_cast<u16x8*>(kb + TILE + fa_off(row, ch)) = past ? (u16x8)(0) : vreg[j];
+      u16x8 kv, vv;                       // (F8: a page tail's 0xFF codes / scales convert to NaN, zeroed here)
+      if constexpr (F8) {
+        kv = kvf8_dequant8(kreg[j], ke[j]);
+        vv = kvf8_dequant8(vreg[j], ve[j]);
+      } else {
+        kv = kreg[j];
+        vv = vreg[j];
+      }
+      *reinterpret_cast<u16x8*>(kb + fa_off(row, ch)) = past ? (u16x8)(0) : kv;
+      *reinterpret_cast<u16x8*>(kb + TILE + fa_off(row, ch)) = past ? (u16x8)(0) : vv;
     }
   };
 
@@ -300,6 +338,7 @@ __global__ void paged_attn_reduce_kernel(const float* __restrict__ part_o, const
 // Prefill blocks: fb_tok0[i] / fb_ntok[i] = first flat token / token count of block i (<= 32 x NW
 // / heads_per_block consecutive tokens of ONE sequence, ops.fa_blocks).  D = 128, page_size a
 // multiple of 64, heads_per_block = nh / nkv in {1, 2, 4, 8}; row-major output [T, nh * D].
+// a.ks != nullptr: the fp8 cache's code pages and row scales (kv_f8.h), the kernel's F8 form.
 extern "C" int mp_attention_fa(const mp::AttnArgs* args, const int32_t* fb_tok0, const int32_t* fb_ntok, int NBF,
                                int nw, int pair, hipStream_t stream) {
   (void)hipGetLastError();  // an earlier non-mpamd HIP call's stale error is not this launch's
@@ -309,16 +348,23 @@ extern "C" int mp_attention_fa(const mp::AttnArgs* args, const int32_t* fb_tok0,
   if (a.D != 128 || a.nh % a.nkv != 0 || a.PS % 64 != 0 || a.NP < 1 || a.page_size % 64 != 0) return -1;
   const int page_log2 = attn_page_log2(a);
   if (page_log2 < 0) return -2;
+  const bool f8 = a.ks != nullptr;
+  if (f8 && a.vs == nullptr) return -4;
   const int hb = a.nh / a.nkv;
   pair = pair ? 1 : 0;
   const int nbp = pair ? (NBF + 1) / 2 : NBF;
-#define MP_FA(HB_, NW_)                                                                                          \
-  hipLaunchKernelGGL((attn_fa_kernel<HB_, NW_>), dim3(nbp * (a.nh / HB_), a.NP), dim3(NW_ * 64), 0, stream,      \
-                     (const bf16_t*)a.q, a.q_stride, (const bf16_t*)a.kc, (const bf16_t*)a.vc, a.bt, a.bt_stride, \
-                     a.q_seq, a.q_ctx, fb_tok0, fb_ntok, NBF, (bf16_t*)a.out, (int64_t)a.nh * a.D, a.workspace,   \
-                     attn_ws_ml(a), a.nkv, a.nh, page_log2, a.PS, a.NP, attn_scale_log2(a), pair)
-#define MP_FA_NW(HB_) \
-  if (nw == 8) MP_FA(HB_, 8); else MP_FA(HB_, 4);
+#define MP_FA(HB_, NW_, F8_)                                                                                       \
+  hipLaunchKernelGGL((attn_fa_kernel<HB_, NW_, F8_>), dim3(nbp * (a.nh / HB_), a.NP), dim3(NW_ * 64), 0, stream,   \
+                     (const bf16_t*)a.q, a.q_stride, (const bf16_t*)a.kc, (const bf16_t*)a.vc, a.bt, a.bt_stride,   \
+                     a.q_seq, a.q_ctx, fb_tok0, fb_ntok, NBF, (bf16_t*)a.out, (int64_t)a.nh * a.D, a.workspace,     \
+                     attn_ws_ml(a), a.nkv, a.nh, page_log2, a.PS, a.NP, attn_scale_log2(a), pair,                   \
+                     (const uint8_t*)a.ks, (const uint8_t*)a.vs)
+#define MP_FA_NW(HB_)                                             \
+  if (f8) {                                                       \
+    if (nw == 8) MP_FA(HB_, 8, true); else MP_FA(HB_, 4, true);   \
+  } else {                                                        \
+    if (nw == 8) MP_FA(HB_, 8, false); else MP_FA(HB_, 4, false); \
+  }
   switch (hb) {
     case 1: MP_FA_NW(1); break;
     case 2: MP_FA_NW(2); break;

@@ -138,7 +138,8 @@ class StageExecutor:
         """``tp``: a ``parallel.tensor_parallel.TPGroup`` when ``weights`` is a tensor-parallel
         shard (``cfg`` is then the shard config); partial sums are all-reduced after the
         o and down projections.  ``kv_cache_dtype="fp8"``: e4m3 pages + e8m0 row scales
-        (runtime/kv_cache.py); every attention step then runs the flash-decoding kernel's fp8 form."""
+        (runtime/kv_cache.py); attention then runs the fp8 forms of the flash-decoding, MFMA GQA decode
+        and FA2 prefill kernels (``_attend``)."""
         cfg.validate()
         if kv_cache_dtype not in KV_DTYPES:
             raise ValueError(f"kv_cache_dtype must be one of {KV_DTYPES}, got {kv_cache_dtype!r}")
@@ -223,8 +224,8 @@ class StageExecutor:
         # first decode step to A/B the flash-decoding kernel)
         # (an fp8 KV cache runs none of the bf16 MFMA kernels and has no MX epilogue)
         self.gqa_decode_mfma = self._attn_mfma_gqa and not self._kv_fp8
-        # ... and on an fp8 KV cache the kernel's fp8 form (decode steps only; prefill stays on the
-        # flash-decoding kernel); MPAMD_KV_FP8_MFMA=0 keeps the flash-decoding kernel there too
+        # ... and on an fp8 KV cache the kernel's fp8 form (decode steps only; prefill: prefill_fa_f8
+        # below); MPAMD_KV_FP8_MFMA=0 keeps the flash-decoding kernel there too
         self.gqa_decode_mfma_f8 = self._attn_mfma_gqa and self._kv_fp8 and \
             os.environ.get("MPAMD_KV_FP8_MFMA", "1") != "0"
         # prefill: up to 4 query blocks of a sequence per workgroup share each K/V step
@@ -235,6 +236,9 @@ class StageExecutor:
         # transposed LDS reads of V (csrc/attention_fa.hip); other shapes keep the 16x16 one
         self._attn_fa = self._attn_mfma_prefill and \
             ops.fa_ok(cfg.num_attention_heads, cfg.num_key_value_heads, cfg.head_dim, page_size)
+        # ... and on an fp8 KV cache the kernel's fp8 form; MPAMD_KV_FP8_FA=0 keeps those steps on the
+        # flash-decoding kernel (per-query causal rows)
+        self.prefill_fa_f8 = self._attn_fa and self._kv_fp8 and os.environ.get("MPAMD_KV_FP8_FA", "1") != "0"
         self._cur_fb = None
         self._cur_fw = 4
         self._n_cu = torch.cuda.get_device_properties(self.device).multi_processor_count \
@@ -534,8 +538,9 @@ class StageExecutor:
     def _attend(self, qkv, kc, vc, q_seq, q_ctx, out, ws, ps, np_, packed, qblocks, max_ctx):
         """Paged attention: MFMA flash attention for prefill blocks (``qblocks``) and GQA decode,
         else the flash-decoding kernel.  An fp8 KV cache has the fp8 forms of the MFMA GQA decode
-        kernel and of the flash-decoding kernel; its prefill blocks run on the latter as per-query
-        causal rows (``qblocks`` and the FA blocks are ignored)."""
+        kernel, of the FA2 prefill kernel (row-major output) and of the flash-decoding kernel; its
+        other prefill blocks (packed output, shapes outside ``fa_ok``) run on the latter as
+        per-query causal rows (``qblocks`` is ignored)."""
         table = self.sessions.table_dev
         if qblocks is None and self.gqa_decode_mfma_f8 and self.device.type == "cuda":
             ps2 = 128 * math.ceil(ps / 128)
@@ -543,6 +548,10 @@ class StageExecutor:
             return ops.attention_mfma_f8(qkv, kc, vc, table, q_seq, q_ctx, self.decode_qblocks(qkv.shape[0]), self.nh,
                                          self.nkv, self.scale, out=out, workspace=ws, part_size=ps2, num_parts=np2,
                                          packed=packed)
+        fb = getattr(self, "_cur_fb", None)
+        if self.prefill_fa_f8 and qblocks is not None and fb is not None and not packed:
+            return ops.attention_fa_f8(qkv, kc, vc, table, q_seq, q_ctx, fb, self.nh, self.nkv, self.scale, out=out,
+                                       workspace=ws, max_ctx=max_ctx, waves=getattr(self, "_cur_fw", 4))
         if self._kv_fp8:
             return ops.paged_attention(qkv, kc, vc, table, q_seq, q_ctx, self.nh, self.nkv, self.scale, out=out,
                                        workspace=ws, part_size=ps, num_parts=np_, packed=packed)
@@ -553,7 +562,6 @@ class StageExecutor:
             return ops.attention_mfma(qkv, kc, vc, table, q_seq, q_ctx, self.decode_qblocks(T), self.nh, self.nkv,
                                       self.scale, out=out, workspace=ws, part_size=ps2, num_parts=np2,
                                       packed=packed)
-        fb = getattr(self, "_cur_fb", None)
         if qblocks is not None and fb is not None and not packed:
             return ops.attention_fa(qkv, kc, vc, table, q_seq, q_ctx, fb, self.nh, self.nkv, self.scale, out=out,
                                     workspace=ws, max_ctx=max_ctx, waves=getattr(self, "_cur_fw", 4))

@@ -60,6 +60,7 @@ def main():
     flops = 2 * proj * T + attn + 2 * H * cfg.vocab_size * a.batch
     print(json.dumps({"model": a.model, "kv_cache_dtype": a.kv_cache_dtype, "batch": a.batch, "prompt_len": a.prompt_len, "tokens": T,
                       "cold_s": round(times[0], 4), "warm_s": round(warm, 4),
+                      "warm_all_s": [round(t, 5) for t in times[1:]],
                       "warm_tokens_per_s": round(T / warm, 1), "warm_tflops": round(flops / warm / 1e12, 1)}),
           flush=True)
 
