@@ -84,6 +84,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--kv_cache_dtype", default="bf16", choices=["bf16", "fp8"],
                    help="stage servers: KV cache format (fp8 = OCP e4m3 pages + one e8m0 scale byte per token and "
                         "kv head: (head_dim + 1) bytes per token-head instead of 2 x head_dim)")
+    p.add_argument("--sliding_window", default="cap", choices=["cap", "attend"],
+                   help="stage servers, models with a sliding window (mistral-7b: 4096): cap = sessions end at the "
+                        "window; attend = sessions run to max_seq_len, every token attends to the last window "
+                        "tokens and KV memory per session stops growing at the window")
     p.add_argument("--use_cpu_offload", action="store_true")
     p.add_argument("--keep_layers_on_gpu", type=int, default=0)
     p.add_argument("--use_load_balancing", action="store_true")
@@ -162,6 +166,8 @@ def _executor_kwargs(args) -> dict:
     kw = dict(max_sessions=args.max_sessions)
     if getattr(args, "kv_cache_dtype", "bf16") != "bf16":
         kw["kv_cache_dtype"] = args.kv_cache_dtype
+    if getattr(args, "sliding_window", "cap") != "cap":
+        kw["sliding_window"] = args.sliding_window
     if args.kv_cache_gb is not None:
         kw["kv_cache_bytes"] = int(args.kv_cache_gb * (1 << 30))
     if args.max_seq_len is not None:
@@ -539,6 +545,8 @@ class _Server:
         extra = dict(start_block=ex.start, end_block=ex.end, final_stage=self.final,
                      cache_tokens_left=int(ex.sessions.cache_tokens_left()), quant_type=ex.quant_type,
                      kv_cache_dtype=getattr(ex, "kv_cache_dtype", "bf16"))
+        if getattr(ex, "sliding_window", None):  # models with a window: the mode and W
+            extra.update(sliding_window=ex.sliding_window, window=int(ex.cfg.sliding_window))
         if self.next_pings:
             extra["next_pings"] = dict(self.next_pings)
         if self.lb:

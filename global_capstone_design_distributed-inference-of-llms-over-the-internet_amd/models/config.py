@@ -156,6 +156,10 @@ PRESETS = {
     "tiny-llama": ModelConfig(vocab_size=512, hidden_size=256, intermediate_size=512, num_hidden_layers=4,
                               num_attention_heads=4, num_key_value_heads=2, head_dim=64,
                               max_position_embeddings=1024, name="tiny-llama"),
+    # tiny-llama with a sliding window shorter than its positions (--sliding_window cap / attend)
+    "tiny-mistral": ModelConfig(model_type="mistral", vocab_size=512, hidden_size=256, intermediate_size=512,
+                                num_hidden_layers=4, num_attention_heads=4, num_key_value_heads=2, head_dim=64,
+                                max_position_embeddings=1024, sliding_window=96, name="tiny-mistral"),
     "small-llama": ModelConfig(vocab_size=1024, hidden_size=512, intermediate_size=1024, num_hidden_layers=8,
                                num_attention_heads=4, num_key_value_heads=4, head_dim=128,
                                max_position_embeddings=2048, name="small-llama"),

@@ -22,10 +22,11 @@ def _rms(x, w, eps):
 
 
 def llama_forward(weights: List[StageWeights], ids: torch.Tensor, return_hidden: bool = False,
-                  kv_hook: Optional[Callable] = None) -> torch.Tensor:
+                  kv_hook: Optional[Callable] = None, window: int = 0) -> torch.Tensor:
     """ids [L] -> logits [L, V] in fp32 through all stages' layers (causal).  ``kv_hook(k, v) -> (k, v)``
     (default off) sees every layer's post-RoPE k and v [L, nkv, D] before attention: the oracle of a
-    quantized KV cache passes a fake-quantizer there."""
+    quantized KV cache passes a fake-quantizer there.  ``window`` W > 0: sliding-window attention,
+    query i sees keys j with 0 <= i - j < W (HF's Mistral mask)."""
     cfg = weights[0].cfg
     H, nh, nkv, D = cfg.hidden_size, cfg.num_attention_heads, cfg.num_key_value_heads, cfg.head_dim
     L = ids.numel()
@@ -33,6 +34,8 @@ def llama_forward(weights: List[StageWeights], ids: torch.Tensor, return_hidden:
     x = weights[0].embed.float()[ids.long()]
     cos, sin = rope_cos_sin(D, max(L, 1), cfg.rope_theta, dev, cfg.rope_scaling)
     mask = torch.full((L, L), float("-inf"), device=dev).triu(1)
+    if window and int(window) > 0:
+        mask = mask + torch.full((L, L), float("-inf"), device=dev).tril(-int(window))
     for sw in weights:
         for lay in sw.layers:
             h = _rms(x, lay.input_norm.float(), cfg.rms_norm_eps)
@@ -93,12 +96,13 @@ def gpt2_forward(weights: List[StageWeights], ids: torch.Tensor) -> torch.Tensor
     return x @ last.lm_head.float().t()
 
 
-def reference_forward(weights: List[StageWeights], ids: torch.Tensor, kv_hook: Optional[Callable] = None) -> torch.Tensor:
+def reference_forward(weights: List[StageWeights], ids: torch.Tensor, kv_hook: Optional[Callable] = None,
+                      window: int = 0) -> torch.Tensor:
     if weights[0].cfg.model_type == "gpt2":
-        if kv_hook is not None:
-            raise ValueError("kv_hook: LLaMA-family oracles only")
+        if kv_hook is not None or window:
+            raise ValueError("kv_hook / window: LLaMA-family oracles only")
         return gpt2_forward(weights, ids)
-    return llama_forward(weights, ids, kv_hook=kv_hook)
+    return llama_forward(weights, ids, kv_hook=kv_hook, window=window)
 
 
 def greedy_generate(weights: List[StageWeights], prompt: torch.Tensor, n_new: int) -> List[int]:

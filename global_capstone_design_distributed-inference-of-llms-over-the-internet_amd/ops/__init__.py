@@ -592,6 +592,34 @@ def attention_partition(num_queries: int, nkv: int, max_ctx: int, target_wgs: in
     return ps, np_
 
 
+def _window_kw(window: int) -> dict:
+    """The ops' trailing ``window`` argument, passed only when a window is set."""
+    return {"window": int(window)} if window else {}
+
+
+def _window_span(window, max_ctx, pad: int = 0):
+    """Tokens per query a windowed launch streams: ``min(max_ctx, W + pad)`` (``pad`` = 31 on the
+    MFMA kernel, whose slices start at the 32-token step that holds the window's first key);
+    ``max_ctx`` itself without a window.  ``max_ctx`` None (unknown): ``W + pad``."""
+    window = int(window or 0)
+    if window < 0:
+        raise ValueError(f"window must be >= 0 (0: no sliding window), got {window}")
+    if window == 0:
+        return max_ctx
+    return window + pad if max_ctx is None else min(int(max_ctx), window + pad)
+
+
+def _check_window_parts(what: str, window, max_ctx, part_size, num_parts, pad: int = 0) -> None:
+    """Explicit slices of a windowed launch must cover the streamed span (the kernels place them
+    from the window's first key; keys past the last slice would be dropped without a word)."""
+    if not window:
+        return
+    span = _window_span(window, max_ctx, pad)
+    if int(part_size) * int(num_parts) < span:
+        raise ValueError(f"ops.{what}: part_size {part_size} x num_parts {num_parts} does not cover the "
+                         f"{span} tokens a window of {window} streams")
+
+
 def _token_blocks(ntoks, tb: int):
     """int32 [2, NB] = (first flat token, count): runs of <= ``tb`` consecutive tokens of ONE
     sequence.  ``ntoks``: tokens per sequence in flat order."""
@@ -633,27 +661,32 @@ def query_superblocks(ntoks, nrep: int, group: int = 8):
 
 
 def attention_mfma(q, k_cache, v_cache, block_tables, q_seq, q_ctx, qblocks, nh, nkv, scale, out=None,
-                   workspace=None, part_size=None, num_parts=None, max_ctx=None, packed=False, superblocks=None):
+                   workspace=None, part_size=None, num_parts=None, max_ctx=None, packed=False, superblocks=None,
+                   window=0):
     """MFMA flash attention (csrc/attention_mfma.hip): prefill blocks of 16 query rows and GQA
     decode.  Same semantics and output as ``paged_attention``; ``qblocks`` from
     ``query_blocks`` (device int32 [2, NB]); ``superblocks`` (``query_superblocks``, device)
-    selects the grouped prefill kernel (up to 4 blocks of a sequence per workgroup)."""
+    selects the grouped prefill kernel (up to 4 blocks of a sequence per workgroup).  ``window``
+    (sliding window, ``paged_attention``): decode blocks only - one token per block, no superblocks."""
     _no_kv_f8(k_cache, v_cache, "attention_mfma")
     if not _native(q):
         return paged_attention(q, k_cache, v_cache, block_tables, q_seq, q_ctx, nh, nkv, scale, out=out,
-                               packed=packed)
+                               packed=packed, window=window)
     T = q.shape[0]
     D = k_cache.shape[-1]
     if part_size is None:
         if max_ctx is None:
             max_ctx = int(q_ctx.max().item()) if T else 1
         nblk = superblocks.shape[1] if superblocks is not None else qblocks.shape[1]
-        part_size, num_parts = _mfma_partition(nblk, nh, nkv, max_ctx)
+        part_size, num_parts = _mfma_partition(nblk, nh, nkv, _window_span(window, max_ctx, 31))
+    else:
+        _check_window_parts("attention_mfma", window, max_ctx, part_size, num_parts, 31)
     if out is None:
         out = _gemm_out(T, nh * D, packed, q.dtype, q.device)
     workspace = _attn_workspace(workspace, T, nh, D, num_parts, q.device)
     torch.ops.mpamd.attention_mfma(q, k_cache, v_cache, block_tables, q_seq, q_ctx, qblocks, out, workspace, nh, nkv,
-                                   float(scale), int(part_size), int(num_parts), int(bool(packed)), superblocks)
+                                   float(scale), int(part_size), int(num_parts), int(bool(packed)), superblocks,
+                                   **_window_kw(window))
     return out
 
 
@@ -668,7 +701,7 @@ def _mfma_partition(nblocks: int, nh: int, nkv: int, max_ctx: int) -> Tuple[int,
 
 
 def attention_mfma_f8(q, k_cache, v_cache, block_tables, q_seq, q_ctx, qblocks, nh, nkv, scale, out=None,
-                      workspace=None, part_size=None, num_parts=None, max_ctx=None, packed=False):
+                      workspace=None, part_size=None, num_parts=None, max_ctx=None, packed=False, window=0):
     """``attention_mfma`` for GQA decode on an fp8 KV cache (``KVF8``; csrc/attention_mfma.hip F8
     form): one query token per block (``decode_qblocks``), GQA groups of 4, 8 or a multiple of 16
     heads.  The kernel converts the codes exactly and then does the bf16 kernel's arithmetic, so the
@@ -676,19 +709,21 @@ def attention_mfma_f8(q, k_cache, v_cache, block_tables, q_seq, q_ctx, qblocks, 
     _need_kv_f8(k_cache, v_cache, "attention_mfma_f8")
     if not _native(q):
         return paged_attention(q, k_cache, v_cache, block_tables, q_seq, q_ctx, nh, nkv, scale, out=out,
-                               packed=packed)
+                               packed=packed, window=window)
     T = q.shape[0]
     D = k_cache.shape[-1]
     if part_size is None:
         if max_ctx is None:
             max_ctx = int(q_ctx.max().item()) if T else 1
-        part_size, num_parts = _mfma_partition(qblocks.shape[1], nh, nkv, max_ctx)
+        part_size, num_parts = _mfma_partition(qblocks.shape[1], nh, nkv, _window_span(window, max_ctx, 31))
+    else:
+        _check_window_parts("attention_mfma_f8", window, max_ctx, part_size, num_parts, 31)
     if out is None:
         out = _gemm_out(T, nh * D, packed, q.dtype, q.device)
     workspace = _attn_workspace(workspace, T, nh, D, num_parts, q.device)
     torch.ops.mpamd.attention_mfma_f8(q, k_cache.codes, v_cache.codes, k_cache.scales, v_cache.scales, block_tables,
                                       q_seq, q_ctx, qblocks, out, workspace, int(nh), int(nkv), float(scale),
-                                      int(part_size), int(num_parts), int(bool(packed)))
+                                      int(part_size), int(num_parts), int(bool(packed)), **_window_kw(window))
     return out
 
 
@@ -735,32 +770,32 @@ def fa_ok(nh: int, nkv: int, D: int, page_size: int) -> bool:
 
 
 def attention_fa(q, k_cache, v_cache, block_tables, q_seq, q_ctx, fablocks, nh, nkv, scale, out=None,
-                 workspace=None, max_ctx=None, waves=None, num_parts=None, pair=None):
+                 workspace=None, max_ctx=None, waves=None, num_parts=None, pair=None, window=0):
     """Causal prefill attention, FA2 form on 32x32x16 MFMA with the transposed LDS reads of V
     (csrc/attention_fa.hip).  Same semantics as ``paged_attention``; row-major output only.
     ``fablocks`` from ``fa_blocks`` (device int32 [2, NB]).  The context is split over parts
-    only when the grid would leave CUs idle."""
+    only when the grid would leave CUs idle.  The kernel has no sliding-window form: ``window`` > 0 raises."""
     _no_kv_f8(k_cache, v_cache, "attention_fa")
     return _attention_fa(q, k_cache, v_cache, block_tables, q_seq, q_ctx, fablocks, nh, nkv, scale, out, workspace,
-                         max_ctx, waves, num_parts, pair)
+                         max_ctx, waves, num_parts, pair, window)
 
 
 def attention_fa_f8(q, k_cache, v_cache, block_tables, q_seq, q_ctx, fablocks, nh, nkv, scale, out=None,
-                    workspace=None, max_ctx=None, waves=None, num_parts=None, pair=None):
+                    workspace=None, max_ctx=None, waves=None, num_parts=None, pair=None, window=0):
     """``attention_fa`` on an fp8 KV cache (``KVF8``; csrc/attention_fa.hip F8 form), with the same
     blocks, parts and pairing.  The kernel converts the codes exactly while staging them into the LDS
     tiles and then does the bf16 kernel's arithmetic, so the output equals ``attention_fa`` on the
     dequantized cache bit for bit."""
     _need_kv_f8(k_cache, v_cache, "attention_fa_f8")
     return _attention_fa(q, k_cache, v_cache, block_tables, q_seq, q_ctx, fablocks, nh, nkv, scale, out, workspace,
-                         max_ctx, waves, num_parts, pair)
+                         max_ctx, waves, num_parts, pair, window)
 
 
 def _attention_fa(q, k_cache, v_cache, block_tables, q_seq, q_ctx, fablocks, nh, nkv, scale, out, workspace, max_ctx,
-                  waves, num_parts, pair):
+                  waves, num_parts, pair, window=0):
     """``attention_fa`` / ``attention_fa_f8``: the partition and pairing rules and the launch."""
     if not _native(q):
-        return paged_attention(q, k_cache, v_cache, block_tables, q_seq, q_ctx, nh, nkv, scale, out=out)
+        return paged_attention(q, k_cache, v_cache, block_tables, q_seq, q_ctx, nh, nkv, scale, out=out, window=window)
     T = q.shape[0]
     D = k_cache.shape[-1]
     waves = int(waves or FA_WAVES)
@@ -780,15 +815,16 @@ def _attention_fa(q, k_cache, v_cache, block_tables, q_seq, q_ctx, fablocks, nh,
     tail = (block_tables, q_seq, q_ctx, fablocks, out, workspace, int(nh), int(nkv), float(scale), int(part_size),
             int(num_parts), waves, int(bool(pair) and num_parts == 1))
     if isinstance(k_cache, KVF8):
-        torch.ops.mpamd.attention_fa_f8(q, k_cache.codes, v_cache.codes, k_cache.scales, v_cache.scales, *tail)
+        torch.ops.mpamd.attention_fa_f8(q, k_cache.codes, v_cache.codes, k_cache.scales, v_cache.scales, *tail,
+                                        **_window_kw(window))
     else:
-        torch.ops.mpamd.attention_fa(q, k_cache, v_cache, *tail)
+        torch.ops.mpamd.attention_fa(q, k_cache, v_cache, *tail, **_window_kw(window))
     return out
 
 
 def attention_mfma_rope(qkv, k_cache, v_cache, block_tables, q_seq, q_ctx, qblocks, positions, cos, sin, slots, nh,
                         nkv, scale, out=None, workspace=None, part_size=None, num_parts=None, max_ctx=None,
-                        packed=False, qkv_part=None, mx_out=None):
+                        packed=False, qkv_part=None, mx_out=None, window=0):
     """GQA decode step on the MFMA kernel with RoPE of q / new k and the new token's page-slot
     write folded in (csrc/attention_mfma.hip ROPE path).  ``qblocks`` must hold one token per block,
     block i = token i (``decode_qblocks``: the kernel takes that as given and reads no qblocks); ``qkv`` is the unrotated fused projection and is not modified; with
@@ -804,27 +840,29 @@ def attention_mfma_rope(qkv, k_cache, v_cache, block_tables, q_seq, q_ctx, qbloc
         q = qkv.clone()
         ref.rope_kv_write(q, positions, cos, sin, k_cache, v_cache, slots, nh, nkv)
         return paged_attention(q, k_cache, v_cache, block_tables, q_seq, q_ctx, nh, nkv, scale, out=out,
-                               packed=packed)
+                               packed=packed, window=window)
     T = qkv.shape[0]
     D = k_cache.shape[-1]
     if part_size is None:
         if max_ctx is None:
             max_ctx = int(q_ctx.max().item()) if T else 1
-        part_size = 128 * math.ceil(max(max_ctx, 1) / 128)
+        part_size = 128 * math.ceil(max(_window_span(window, max_ctx, 31), 1) / 128)
         num_parts = 1
+    else:
+        _check_window_parts("attention_mfma_rope", window, max_ctx, part_size, num_parts, 31)
     if out is None:
         out = _gemm_out(T, nh * D, packed, qkv.dtype, qkv.device)
     workspace = _attn_workspace(workspace, T, nh, D, num_parts, qkv.device)
     torch.ops.mpamd.attention_mfma_rope(qkv, k_cache, v_cache, block_tables, q_seq, q_ctx, qblocks, positions, cos,
                                         sin, slots, out, workspace, nh, nkv, float(scale), int(part_size),
                                         int(num_parts), int(bool(packed)), *_qkv_part_args(qkv_part),
-                                        *(mx_out if mx_out is not None else (None, None)))
+                                        *(mx_out if mx_out is not None else (None, None)), **_window_kw(window))
     return out
 
 
 def attention_mfma_rope_f8(qkv, k_cache, v_cache, block_tables, q_seq, q_ctx, qblocks, positions, cos, sin, slots,
                            nh, nkv, scale, out=None, workspace=None, part_size=None, num_parts=None, max_ctx=None,
-                           packed=False, qkv_part=None):
+                           packed=False, qkv_part=None, window=0):
     """``attention_mfma_rope`` on an fp8 KV cache (``KVF8``): the new token's rotated k and its v are
     quantized per head (``quant_kv_fp8``), written as codes + scale, and attended to through their
     dequantized values - what every later step reads.  GQA groups of 4, 8 or a multiple of 16 heads;
@@ -837,21 +875,24 @@ def attention_mfma_rope_f8(qkv, k_cache, v_cache, block_tables, q_seq, q_ctx, qb
         q = qkv.clone()
         ref.rope_kv_write_f8(q, positions, cos, sin, k_cache, v_cache, slots, nh, nkv)
         return paged_attention(q, k_cache, v_cache, block_tables, q_seq, q_ctx, nh, nkv, scale, out=out,
-                               packed=packed)
+                               packed=packed, window=window)
     T = qkv.shape[0]
     D = k_cache.shape[-1]
     if part_size is None:
         if max_ctx is None:
             max_ctx = int(q_ctx.max().item()) if T else 1
-        part_size = 128 * math.ceil(max(max_ctx, 1) / 128)
+        part_size = 128 * math.ceil(max(_window_span(window, max_ctx, 31), 1) / 128)
         num_parts = 1
+    else:
+        _check_window_parts("attention_mfma_rope_f8", window, max_ctx, part_size, num_parts, 31)
     if out is None:
         out = _gemm_out(T, nh * D, packed, qkv.dtype, qkv.device)
     workspace = _attn_workspace(workspace, T, nh, D, num_parts, qkv.device)
     torch.ops.mpamd.attention_mfma_rope_f8(qkv, k_cache.codes, v_cache.codes, k_cache.scales, v_cache.scales,
                                            block_tables, q_seq, q_ctx, qblocks, positions, cos, sin, slots, out,
                                            workspace, int(nh), int(nkv), float(scale), int(part_size),
-                                           int(num_parts), int(bool(packed)), *_qkv_part_args(qkv_part))
+                                           int(num_parts), int(bool(packed)), *_qkv_part_args(qkv_part),
+                                           **_window_kw(window))
     return out
 
 
@@ -894,20 +935,25 @@ def _attn_workspace(workspace, num_queries: int, nh: int, head_dim: int, num_par
 
 
 def paged_attention(q, k_cache, v_cache, block_tables, q_seq, q_ctx, nh, nkv, scale, out=None, workspace=None,
-                    part_size=None, num_parts=None, max_ctx=None, packed=False):
+                    part_size=None, num_parts=None, max_ctx=None, packed=False, window=0):
     """Flash-decoding paged attention (csrc/attention.hip).  ``k_cache`` / ``v_cache``: bf16 pages, or
-    an fp8 cache (``KVF8``), read by the kernel's fp8 form."""
+    an fp8 cache (``KVF8``), read by the kernel's fp8 form.  ``window`` W > 0 (sliding window): a
+    query of context ``ctx`` sees cache positions ``[max(0, ctx - W), ctx)`` only, and neither the
+    pages below them nor their block-table entries are read; 0: the whole context."""
     f8 = _kv_f8(k_cache, v_cache)
     if not _native(q):
         y = (ref.paged_attention_f8 if f8 else ref.paged_attention)(
-            q, k_cache, v_cache, block_tables, q_seq, q_ctx, nh, nkv, scale, out=None if packed else out)
+            q, k_cache, v_cache, block_tables, q_seq, q_ctx, nh, nkv, scale, out=None if packed else out,
+            window=window)
         return ref.pack_act(y, out=out) if packed else y
     T = q.shape[0]
     D = k_cache.shape[-1]
     if part_size is None:
         if max_ctx is None:
             max_ctx = int(q_ctx.max().item()) if T else 1
-        part_size, num_parts = attention_partition(T, nkv, max_ctx)
+        part_size, num_parts = attention_partition(T, nkv, _window_span(window, max_ctx))
+    else:
+        _check_window_parts("paged_attention", window, max_ctx, part_size, num_parts)
     if out is None:
         out = _gemm_out(T, nh * D, packed, q.dtype, q.device)
     if workspace is None:
@@ -916,10 +962,11 @@ def paged_attention(q, k_cache, v_cache, block_tables, q_seq, q_ctx, nh, nkv, sc
         torch.ops.mpamd.paged_attention_f8(q, k_cache.codes, v_cache.codes, k_cache.scales, v_cache.scales,
                                            block_tables, q_seq, q_ctx, out, workspace, int(nh), int(nkv),
                                            float(scale), int(part_size), int(num_parts), int(bool(packed)),
-                                           _attn_cnt(q.device))
+                                           _attn_cnt(q.device), **_window_kw(window))
         return out
     torch.ops.mpamd.paged_attention(q, k_cache, v_cache, block_tables, q_seq, q_ctx, out, workspace, int(nh), int(nkv),
-                                    float(scale), int(part_size), int(num_parts), int(bool(packed)), _attn_cnt(q.device))
+                                    float(scale), int(part_size), int(num_parts), int(bool(packed)), _attn_cnt(q.device),
+                                    **_window_kw(window))
     return out
 
 
@@ -947,7 +994,7 @@ def reduce_qkv_part(qkv_part, dtype=torch.bfloat16):
 
 def paged_attention_rope(qkv, k_cache, v_cache, block_tables, q_seq, q_ctx, positions, cos, sin, slots, nh, nkv,
                          scale, out=None, workspace=None, part_size=None, num_parts=None, max_ctx=None,
-                         packed=False, qkv_part=None):
+                         packed=False, qkv_part=None, window=0):
     """Decode step (one query per sequence, q_ctx = position + 1): RoPE of q / new k, the new
     token's page-slot write and paged attention in ONE kernel (csrc/attention.hip ROPE path).
     ``qkv`` is the unrotated fused projection and is not modified; with ``qkv_part``
@@ -963,13 +1010,15 @@ def paged_attention_rope(qkv, k_cache, v_cache, block_tables, q_seq, q_ctx, posi
         (ref.rope_kv_write_f8 if f8 else ref.rope_kv_write)(q, positions, cos, sin, k_cache, v_cache, slots, nh, nkv)
         return paged_attention(q, k_cache, v_cache, block_tables, q_seq, q_ctx, nh, nkv, scale, out=out,
                                workspace=workspace, part_size=part_size, num_parts=num_parts, max_ctx=max_ctx,
-                               packed=packed)
+                               packed=packed, window=window)
     T = qkv.shape[0]
     D = k_cache.shape[-1]
     if part_size is None:
         if max_ctx is None:
             max_ctx = int(q_ctx.max().item()) if T else 1
-        part_size, num_parts = attention_partition(T, nkv, max_ctx)
+        part_size, num_parts = attention_partition(T, nkv, _window_span(window, max_ctx))
+    else:
+        _check_window_parts("paged_attention_rope", window, max_ctx, part_size, num_parts)
     if out is None:
         out = _gemm_out(T, nh * D, packed, qkv.dtype, qkv.device)
     if workspace is None:
@@ -979,12 +1028,12 @@ def paged_attention_rope(qkv, k_cache, v_cache, block_tables, q_seq, q_ctx, posi
                                                 block_tables, q_seq, q_ctx, positions, cos, sin, slots, out,
                                                 workspace, int(nh), int(nkv), float(scale), int(part_size),
                                                 int(num_parts), int(bool(packed)), _attn_cnt(qkv.device),
-                                                *_qkv_part_args(qkv_part))
+                                                *_qkv_part_args(qkv_part), **_window_kw(window))
         return out
     torch.ops.mpamd.paged_attention_rope(qkv, k_cache, v_cache, block_tables, q_seq, q_ctx, positions, cos, sin,
                                          slots, out, workspace, int(nh), int(nkv), float(scale), int(part_size),
                                          int(num_parts), int(bool(packed)), _attn_cnt(qkv.device),
-                                         *_qkv_part_args(qkv_part))
+                                         *_qkv_part_args(qkv_part), **_window_kw(window))
     return out
 
 

@@ -176,7 +176,7 @@ __global__ __launch_bounds__(NW * 64, MP_ATTN_MINW) void paged_attn1_kernel(
     const bf16_t* __restrict__ vc, const int32_t* __restrict__ block_tables, int bt_stride,
     const int32_t* __restrict__ q_seq, const int32_t* __restrict__ q_ctx, bf16_t* __restrict__ out,
     float* __restrict__ part_o, float* __restrict__ part_ml, int nkv, int nh, int page_log2, int PS, int NP,
-    float scale_log2, int packed_mt, RopeFuse rf, int* __restrict__ cnt, KvF8 f8) {
+    float scale_log2, int packed_mt, RopeFuse rf, int* __restrict__ cnt, KvF8 f8, int window) {
   using kvreg_t = std::conditional_t<F8, KvF8Reg, u16x8>;
   constexpr int LPT = D / 8;
   constexpr int TPI = 64 / LPT;
@@ -195,7 +195,9 @@ __global__ __launch_bounds__(NW * 64, MP_ATTN_MINW) void paged_attn1_kernel(
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int sl = lane % LPT, tg = lane / LPT;
   const int ctx = q_ctx[t];
-  const int start = p * PS;
+  // sliding window: the slices tile [lo, ctx) instead of [0, ctx), so no position below lo (and no
+  // block-table entry of a page below it) is ever read; trailing slices past ctx are empty
+  const int start = attn_window_lo(ctx, window) + p * PS;
   const int end = min(start + PS, ctx);
   const int64_t obase = ((int64_t)t * nh + hbase) * D;
   if (start >= end) {
@@ -524,7 +526,7 @@ static void launch_attn_nw(const AttnArgs& a, int page_log2, const RopeFuse& rf,
     hipLaunchKernelGGL(kern, dim3(a.NP, a.nh / NREP, a.T), dim3(64 * NW), lds, stream, (const bf16_t*)a.q, a.q_stride,
                        (const bf16_t*)a.kc, (const bf16_t*)a.vc, a.bt, a.bt_stride, a.q_seq, a.q_ctx, (bf16_t*)a.out,
                        a.workspace, attn_ws_ml(a), a.nkv, a.nh, page_log2, a.PS, a.NP, attn_scale_log2(a), a.packed_mt,
-                       rf, cnt, f8);
+                       rf, cnt, f8, a.window);
   };
   if (rf.pos) go(paged_attn1_kernel<D, NREP, true, NW, true, 4, F8>);
   else go(paged_attn1_kernel<D, NREP, false, NW, true, 4, F8>);
@@ -558,7 +560,7 @@ extern "C" int mp_paged_attention(const mp::AttnArgs* args, int* counters, int n
   }
   const KvF8 f8{(uint8_t*)a.ks, (uint8_t*)a.vs};
   if (a.T == 0) return 0;
-  if (a.nh % a.nkv != 0 || a.PS % 64 != 0 || a.PS > 2048 || a.NP < 1) return -1;
+  if (a.nh % a.nkv != 0 || a.PS % 64 != 0 || a.PS > 2048 || a.NP < 1 || a.window < 0) return -1;
   const int page_log2 = attn_page_log2(a);
   if (page_log2 < 0) return -2;
   const int nrep = a.nh / a.nkv;

@@ -344,6 +344,7 @@ extern "C" int mp_attention_fa(const mp::AttnArgs* args, const int32_t* fb_tok0,
   (void)hipGetLastError();  // an earlier non-mpamd HIP call's stale error is not this launch's
   using namespace mp;
   const AttnArgs& a = *args;
+  if (a.window != 0) return -11;  // no sliding-window form
   if (NBF == 0 || a.T == 0) return 0;
   if (a.D != 128 || a.nh % a.nkv != 0 || a.PS % 64 != 0 || a.NP < 1 || a.page_size % 64 != 0) return -1;
   const int page_log2 = attn_page_log2(a);

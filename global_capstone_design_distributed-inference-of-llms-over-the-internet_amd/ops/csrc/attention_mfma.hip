@@ -83,7 +83,7 @@ __global__ __launch_bounds__(256, 2) void attn_mfma_kernel(
     const int32_t* __restrict__ block_tables, int bt_stride, const int32_t* __restrict__ q_seq,
     const int32_t* __restrict__ q_ctx, const int32_t* __restrict__ qb_tok0, const int32_t* __restrict__ qb_ntok,
     bf16_t* __restrict__ out, float* __restrict__ part_o, float* __restrict__ part_ml, int nkv, int nh,
-    int page_log2, int PS, int NP, float scale_log2, int packed_mt, RopeFuseM rf) {
+    int page_log2, int PS, int NP, float scale_log2, int packed_mt, RopeFuseM rf, int window) {
   constexpr int TB = 16 / HB;
   constexpr int KD = D / 32;  // k-chunks of the QK^T product
   constexpr int DT = D / 16;  // 16-column tiles of O
@@ -112,7 +112,11 @@ __global__ __launch_bounds__(256, 2) void attn_mfma_kernel(
   const int my_ctx = row_ok ? q_ctx[tok0 + my_t] : 0;
   int blk_ctx = 0;  // context the block needs = the largest ctx of its tokens (causal: the last)
   for (int i = 0; i < ntok; ++i) blk_ctx = max(blk_ctx, q_ctx[tok0 + i]);
-  const int start = p * PS, end = min(start + PS, blk_ctx);
+  // sliding window (decode blocks: one token, so blk_ctx is the row's ctx): keys below lo are
+  // masked; the slices start at the 32-token step that holds lo - the same page as lo, so steps stay
+  // aligned (the V tile never straddles a page) and no page below the window is touched
+  const int lo = attn_window_lo(blk_ctx, window);
+  const int start = (lo & ~31) + p * PS, end = min(start + PS, blk_ctx);
 
   constexpr int NV = (32 * D * 2) / 1024;  // 8-element V chunks per lane per step
   // a lane's 8 cache elements: 16 B of bf16, or 8 B of codes (F8) with the token's scale in ke / ve
@@ -359,7 +363,7 @@ __global__ __launch_bounds__(256, 2) void attn_mfma_kernel(
       u16x8 vv;
       if constexpr (F8) vv = kvf8_dequant8(vr[i], ve);
       else vv = vr[i];
-      if (b0 + tk >= end) vv = (u16x8)(0);
+      if (b0 + tk >= end || b0 + tk < lo) vv = (u16x8)(0);
 #pragma unroll
       for (int e = 0; e < 8; ++e) vt[(d0 + e) * VT_PITCH + tk] = vv[e];
     }
@@ -388,7 +392,7 @@ __global__ __launch_bounds__(256, 2) void attn_mfma_kernel(
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int tk = b0 + sub * 16 + qd * 4 + r;
-        const float v = (tk < my_ctx && tk < end) ? st[sub][r] * scale_log2 : -INFINITY;
+        const float v = (tk < my_ctx && tk < end && tk >= lo) ? st[sub][r] * scale_log2 : -INFINITY;
         s8[sub * 4 + r] = v;
         lm = fmaxf(lm, v);
       }
@@ -701,7 +705,7 @@ static void launch_attn_mfma(const AttnArgs& a, int page_log2, const RopeFuseM& 
   auto go = [&](auto kern) {
     hipLaunchKernelGGL(kern, dim3(NB, a.nh / HB, a.NP), dim3(256), 0, stream, q, a.q_stride, kc, vc, a.bt,
                        a.bt_stride, a.q_seq, a.q_ctx, qb_tok0, qb_ntok, (bf16_t*)a.out, a.workspace, ws_ml, a.nkv,
-                       a.nh, page_log2, a.PS, a.NP, scale_log2, a.packed_mt, rf);
+                       a.nh, page_log2, a.PS, a.NP, scale_log2, a.packed_mt, rf, a.window);
   };
   if (rf.pos && rf.qp.part) go(attn_mfma_kernel<D, HB, true, true>);
   else if (rf.pos) go(attn_mfma_kernel<D, HB, true, false>);
@@ -716,7 +720,7 @@ static void launch_attn_mfma_f8(const AttnArgs& a, int page_log2, const RopeFuse
     hipLaunchKernelGGL(kern, dim3(NB, a.nh / HB, a.NP), dim3(256), 0, stream, (const bf16_t*)a.q, a.q_stride,
                        (const bf16_t*)a.kc, (const bf16_t*)a.vc, a.bt, a.bt_stride, a.q_seq, a.q_ctx, qb_tok0, qb_ntok,
                        (bf16_t*)a.out, a.workspace, attn_ws_ml(a), a.nkv, a.nh, page_log2, a.PS, a.NP,
-                       attn_scale_log2(a), a.packed_mt, rf);
+                       attn_scale_log2(a), a.packed_mt, rf, a.window);
   };
   if (rf.pos && rf.qp.part) go(attn_mfma_kernel<D, HB, true, true, true>);
   else if (rf.pos) go(attn_mfma_kernel<D, HB, true, false, true>);
@@ -755,6 +759,9 @@ extern "C" int mp_attention_mfma(const mp::AttnArgs* args, const int32_t* qb_tok
   if (f8 && sb_first != nullptr && NSB > 0) return -9;       // the grouped prefill kernel has no fp8 form
   rf.ks = (uint8_t*)a.ks;
   rf.vs = (uint8_t*)a.vs;
+  // the window is built for decode blocks only (one token per block: NB == T), not for the
+  // grouped prefill kernel
+  if (a.window < 0 || (a.window > 0 && (NB != a.T || (sb_first != nullptr && NSB > 0)))) return -11;
   if (NB == 0 || a.T == 0) return 0;
   if (a.nh % a.nkv != 0 || a.PS % 128 != 0 || a.NP < 1 || a.page_size % 32 != 0) return -1;
   const int page_log2 = attn_page_log2(a);

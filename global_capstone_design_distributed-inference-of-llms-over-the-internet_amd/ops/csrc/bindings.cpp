@@ -295,6 +295,14 @@ mp::AttnArgs attn_args(const at::Tensor& q, const at::Tensor& k_cache, const at:
   return a;
 }
 
+// The sliding window of a launch (mp::AttnArgs::window).  built: this launch implements it; one that
+// does not refuses a window instead of attending to the whole context.
+inline void attn_window(mp::AttnArgs& a, int64_t window, bool built, const char* what) {
+  MP_CHECK(window >= 0 && window <= INT32_MAX, "window must be >= 0 (0: no sliding window)");
+  MP_CHECK(window == 0 || built, std::string(what) + " has no sliding-window form: window must be 0");
+  a.window = (int)window;
+}
+
 // The qkv projection as split-K partial slabs [S][T][width] fp32 + the fused-norm row statistics
 // (mp::QkvPart), read by the decode attention kernels; part == nullptr when absent.
 mp::QkvPart qkv_part_args(const c10::optional<at::Tensor>& part, int64_t splits, const c10::optional<at::Tensor>& ss,
@@ -332,7 +340,8 @@ inline std::pair<const int32_t*, int> check_blocks(const at::Tensor& t, bool on_
 
 // The flash-decoding launch (attention.hip), on a bf16 or an fp8 (a.ks) cache.  counters: optional
 // arrival counters of the in-launch split-K combine.
-void launch_paged(const mp::AttnArgs& a, const c10::optional<at::Tensor>& counters) {
+void launch_paged(mp::AttnArgs a, const c10::optional<at::Tensor>& counters, int64_t window) {
+  attn_window(a, window, true, "paged_attention");
   int* cp = nullptr;
   int ncnt = 0;
   if (counters.has_value()) {
@@ -348,11 +357,12 @@ void launch_paged(const mp::AttnArgs& a, const c10::optional<at::Tensor>& counte
 void paged_attention(const at::Tensor& q, const at::Tensor& k_cache, const at::Tensor& v_cache,
                      const at::Tensor& block_tables, const at::Tensor& q_seq, const at::Tensor& q_ctx,
                      at::Tensor& out, at::Tensor& workspace, int64_t nh, int64_t nkv, double scale, int64_t part_size,
-                     int64_t num_parts, int64_t packed, const c10::optional<at::Tensor>& counters) {
+                     int64_t num_parts, int64_t packed, const c10::optional<at::Tensor>& counters,
+    int64_t window) {
   check_kv_bf16(k_cache, v_cache);
   launch_paged(attn_args(q, k_cache, v_cache, block_tables, q_seq, q_ctx, out, workspace, nh, nkv, scale, part_size,
                          num_parts, packed),
-               counters);
+               counters, window);
 }
 
 // The flash-decoding kernel on an fp8 KV cache (attention.hip F8 form).
@@ -360,11 +370,12 @@ void paged_attention_f8(const at::Tensor& q, const at::Tensor& k_cache, const at
                         const at::Tensor& k_scale, const at::Tensor& v_scale, const at::Tensor& block_tables,
                         const at::Tensor& q_seq, const at::Tensor& q_ctx, at::Tensor& out, at::Tensor& workspace,
                         int64_t nh, int64_t nkv, double scale, int64_t part_size, int64_t num_parts, int64_t packed,
-                        const c10::optional<at::Tensor>& counters) {
+                        const c10::optional<at::Tensor>& counters,
+    int64_t window) {
   check_kv_f8(k_cache, v_cache, k_scale, v_scale, nkv);
   launch_paged(attn_args(q, k_cache, v_cache, block_tables, q_seq, q_ctx, out, workspace, nh, nkv, scale, part_size,
                          num_parts, packed, &k_scale, &v_scale),
-               counters);
+               counters, window);
 }
 
 // Decode attention with RoPE + KV write fused in (attention.hip ROPE path): q is the unrotated
@@ -375,7 +386,8 @@ void paged_attention_rope(const at::Tensor& qkv, at::Tensor& k_cache, at::Tensor
                           const at::Tensor& slots, at::Tensor& out, at::Tensor& workspace, int64_t nh, int64_t nkv,
                           double scale, int64_t part_size, int64_t num_parts, int64_t packed,
                           const c10::optional<at::Tensor>& counters, const c10::optional<at::Tensor>& qkv_part,
-                          int64_t part_splits, const c10::optional<at::Tensor>& part_ss, double inv_k, double eps) {
+                          int64_t part_splits, const c10::optional<at::Tensor>& part_ss, double inv_k, double eps,
+    int64_t window) {
   check_kv_bf16(k_cache, v_cache);
   const int D = k_cache.size(3);
   check_rope(qkv, positions, cos, sin, slots, nh, nkv, D);
@@ -384,7 +396,7 @@ void paged_attention_rope(const at::Tensor& qkv, at::Tensor& k_cache, at::Tensor
   mp::AttnArgs a = attn_args(qkv, k_cache, v_cache, block_tables, q_seq, q_ctx, out, workspace, nh, nkv, scale,
                              part_size, num_parts, packed);
   fuse_rope(a, positions, cos, sin, slots, qp);
-  launch_paged(a, counters);
+  launch_paged(a, counters, window);
 }
 
 // Its fp8 cache form: RoPE, the new token's quantization + page write and attention in one launch.
@@ -395,21 +407,26 @@ void paged_attention_rope_f8(const at::Tensor& qkv, at::Tensor& k_cache, at::Ten
                              int64_t nh, int64_t nkv, double scale, int64_t part_size, int64_t num_parts,
                              int64_t packed, const c10::optional<at::Tensor>& counters,
                              const c10::optional<at::Tensor>& qkv_part, int64_t part_splits,
-                             const c10::optional<at::Tensor>& part_ss, double inv_k, double eps) {
+                             const c10::optional<at::Tensor>& part_ss, double inv_k, double eps,
+    int64_t window) {
   check_kv_f8(k_cache, v_cache, k_scale, v_scale, nkv);
   check_rope(qkv, positions, cos, sin, slots, nh, nkv, k_cache.size(3));
   const mp::QkvPart qp = qkv_part_args(qkv_part, part_splits, part_ss, inv_k, eps, qkv.size(0), qkv.size(1));
   mp::AttnArgs a = attn_args(qkv, k_cache, v_cache, block_tables, q_seq, q_ctx, out, workspace, nh, nkv, scale,
                              part_size, num_parts, packed, &k_scale, &v_scale);
   fuse_rope(a, positions, cos, sin, slots, qp);
-  launch_paged(a, counters);
+  launch_paged(a, counters, window);
 }
 
 // The MFMA launch (attention_mfma.hip): query blocks, optional prefill superblocks int32 [2, NSB]
 // (first query block, count <= 4), optional MX output.
-void launch_mfma(const mp::AttnArgs& a, const at::Tensor& qblocks, const c10::optional<at::Tensor>& superblocks,
-                 void* mx_ax = nullptr, void* mx_as = nullptr) {
+void launch_mfma(mp::AttnArgs a, const at::Tensor& qblocks, const c10::optional<at::Tensor>& superblocks,
+                 int64_t window, void* mx_ax = nullptr, void* mx_as = nullptr) {
   const auto [qb, NB] = check_blocks(qblocks, false, INT64_MAX, "qblocks int32 [2, NB] (first token, token count)");
+  // the window is built for decode blocks (one token per block, NB == T), not for multi-token blocks
+  // or the grouped prefill kernel
+  attn_window(a, window, NB == a.T && !superblocks.has_value(),
+              "attention_mfma with multi-token query blocks or superblocks");
   const int32_t* sb = nullptr;
   int NSB = 0;
   if (superblocks.has_value())
@@ -423,15 +440,17 @@ void attention_mfma(const at::Tensor& q, const at::Tensor& k_cache, const at::Te
                     const at::Tensor& block_tables, const at::Tensor& q_seq, const at::Tensor& q_ctx,
                     const at::Tensor& qblocks, at::Tensor& out, at::Tensor& workspace, int64_t nh, int64_t nkv,
                     double scale, int64_t part_size, int64_t num_parts, int64_t packed,
-                    const c10::optional<at::Tensor>& superblocks) {
+                    const c10::optional<at::Tensor>& superblocks,
+    int64_t window) {
   check_kv_bf16(k_cache, v_cache);
   launch_mfma(attn_args(q, k_cache, v_cache, block_tables, q_seq, q_ctx, out, workspace, nh, nkv, scale, part_size,
                         num_parts, packed),
-              qblocks, superblocks);
+              qblocks, superblocks, window);
 }
 
 // The FA2 prefill launch (attention_fa.hip), on a bf16 or an fp8 (a.ks) cache.
-void launch_fa(const mp::AttnArgs& a, const at::Tensor& fablocks, int64_t waves, int64_t pair) {
+void launch_fa(mp::AttnArgs a, const at::Tensor& fablocks, int64_t waves, int64_t pair, int64_t window) {
+  attn_window(a, window, false, "attention_fa");
   const auto [fb, NB] =
       check_blocks(fablocks, true, INT64_MAX, "fablocks int32 [2, NB] (first token, token count), ops.fa_blocks");
   MP_CHECK(waves == 4 || waves == 8, "waves 4 or 8");
@@ -443,12 +462,13 @@ void launch_fa(const mp::AttnArgs& a, const at::Tensor& fablocks, int64_t waves,
 void attention_fa(const at::Tensor& q, const at::Tensor& k_cache, const at::Tensor& v_cache,
                   const at::Tensor& block_tables, const at::Tensor& q_seq, const at::Tensor& q_ctx,
                   const at::Tensor& fablocks, at::Tensor& out, at::Tensor& workspace, int64_t nh, int64_t nkv,
-                  double scale, int64_t part_size, int64_t num_parts, int64_t waves, int64_t pair) {
+                  double scale, int64_t part_size, int64_t num_parts, int64_t waves, int64_t pair,
+    int64_t window) {
   check_kv_bf16(k_cache, v_cache);
   MP_CHECK(k_cache.size(3) == 128, "attention_fa: head_dim 128");
   launch_fa(attn_args(q, k_cache, v_cache, block_tables, q_seq, q_ctx, out, workspace, nh, nkv, scale, part_size,
                       num_parts, 0),
-            fablocks, waves, pair);
+            fablocks, waves, pair, window);
 }
 
 // Its fp8 cache form (attention_fa.hip F8 form): the same blocks, parts and pairing.
@@ -456,12 +476,13 @@ void attention_fa_f8(const at::Tensor& q, const at::Tensor& k_cache, const at::T
                      const at::Tensor& k_scale, const at::Tensor& v_scale, const at::Tensor& block_tables,
                      const at::Tensor& q_seq, const at::Tensor& q_ctx, const at::Tensor& fablocks, at::Tensor& out,
                      at::Tensor& workspace, int64_t nh, int64_t nkv, double scale, int64_t part_size,
-                     int64_t num_parts, int64_t waves, int64_t pair) {
+                     int64_t num_parts, int64_t waves, int64_t pair,
+    int64_t window) {
   check_kv_f8(k_cache, v_cache, k_scale, v_scale, nkv);
   MP_CHECK(k_cache.size(3) == 128, "attention_fa_f8: head_dim 128");
   launch_fa(attn_args(q, k_cache, v_cache, block_tables, q_seq, q_ctx, out, workspace, nh, nkv, scale, part_size,
                       num_parts, 0, &k_scale, &v_scale),
-            fablocks, waves, pair);
+            fablocks, waves, pair, window);
 }
 
 // GQA decode with RoPE + KV write fused (attention_mfma.hip ROPE path): one token per query block,
@@ -473,7 +494,8 @@ void attention_mfma_rope(const at::Tensor& qkv, at::Tensor& k_cache, at::Tensor&
                          int64_t nh, int64_t nkv, double scale, int64_t part_size, int64_t num_parts, int64_t packed,
                          const c10::optional<at::Tensor>& qkv_part, int64_t part_splits,
                          const c10::optional<at::Tensor>& part_ss, double inv_k, double eps,
-                         const c10::optional<at::Tensor>& mx_ax, const c10::optional<at::Tensor>& mx_as) {
+                         const c10::optional<at::Tensor>& mx_ax, const c10::optional<at::Tensor>& mx_as,
+    int64_t window) {
   check_kv_bf16(k_cache, v_cache);
   const int D = k_cache.size(3), T = qkv.size(0);
   check_rope(qkv, positions, cos, sin, slots, nh, nkv, D);
@@ -494,7 +516,7 @@ void attention_mfma_rope(const at::Tensor& qkv, at::Tensor& k_cache, at::Tensor&
   mp::AttnArgs a = attn_args(qkv, k_cache, v_cache, block_tables, q_seq, q_ctx, out, workspace, nh, nkv, scale,
                              part_size, num_parts, packed);
   fuse_rope(a, positions, cos, sin, slots, qp);
-  launch_mfma(a, qblocks, c10::nullopt, axp, asp);
+  launch_mfma(a, qblocks, c10::nullopt, window, axp, asp);
 }
 
 // The fp8 cache forms of the two above (attention_mfma.hip F8 form): decode blocks only (one token
@@ -510,12 +532,13 @@ void attention_mfma_f8(const at::Tensor& q, const at::Tensor& k_cache, const at:
                        const at::Tensor& k_scale, const at::Tensor& v_scale, const at::Tensor& block_tables,
                        const at::Tensor& q_seq, const at::Tensor& q_ctx, const at::Tensor& qblocks, at::Tensor& out,
                        at::Tensor& workspace, int64_t nh, int64_t nkv, double scale, int64_t part_size,
-                       int64_t num_parts, int64_t packed) {
+                       int64_t num_parts, int64_t packed,
+    int64_t window) {
   check_kv_f8(k_cache, v_cache, k_scale, v_scale, nkv);
   check_mfma_f8(q, qblocks, nh, nkv);
   launch_mfma(attn_args(q, k_cache, v_cache, block_tables, q_seq, q_ctx, out, workspace, nh, nkv, scale, part_size,
                         num_parts, packed, &k_scale, &v_scale),
-              qblocks, c10::nullopt);
+              qblocks, c10::nullopt, window);
 }
 
 void attention_mfma_rope_f8(const at::Tensor& qkv, at::Tensor& k_cache, at::Tensor& v_cache, at::Tensor& k_scale,
@@ -524,7 +547,8 @@ void attention_mfma_rope_f8(const at::Tensor& qkv, at::Tensor& k_cache, at::Tens
                             const at::Tensor& cos, const at::Tensor& sin, const at::Tensor& slots, at::Tensor& out,
                             at::Tensor& workspace, int64_t nh, int64_t nkv, double scale, int64_t part_size,
                             int64_t num_parts, int64_t packed, const c10::optional<at::Tensor>& qkv_part,
-                            int64_t part_splits, const c10::optional<at::Tensor>& part_ss, double inv_k, double eps) {
+                            int64_t part_splits, const c10::optional<at::Tensor>& part_ss, double inv_k, double eps,
+    int64_t window) {
   check_kv_f8(k_cache, v_cache, k_scale, v_scale, nkv);
   check_mfma_f8(qkv, qblocks, nh, nkv);
   check_rope(qkv, positions, cos, sin, slots, nh, nkv, k_cache.size(3));
@@ -532,7 +556,7 @@ void attention_mfma_rope_f8(const at::Tensor& qkv, at::Tensor& k_cache, at::Tens
   mp::AttnArgs a = attn_args(qkv, k_cache, v_cache, block_tables, q_seq, q_ctx, out, workspace, nh, nkv, scale,
                              part_size, num_parts, packed, &k_scale, &v_scale);
   fuse_rope(a, positions, cos, sin, slots, qp);
-  launch_mfma(a, qblocks, c10::nullopt);
+  launch_mfma(a, qblocks, c10::nullopt, window);
 }
 
 void embedding(const at::Tensor& ids, const at::Tensor& table, at::Tensor& out) {
@@ -884,53 +908,53 @@ TORCH_LIBRARY(mpamd, m) {
   m.def(
       "paged_attention(Tensor q, Tensor k_cache, Tensor v_cache, Tensor block_tables, Tensor q_seq, Tensor q_ctx, "
       "Tensor(a!) out, Tensor(b!) workspace, int nh, int nkv, float scale, int part_size, int num_parts, "
-      "int packed, Tensor(c!)? counters=None) -> ()");
+      "int packed, Tensor(c!)? counters=None, int window=0) -> ()");
   m.def(
       "paged_attention_rope(Tensor qkv, Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor block_tables, Tensor q_seq, "
       "Tensor q_ctx, Tensor positions, Tensor cos, Tensor sin, Tensor slots, Tensor(c!) out, Tensor(d!) workspace, "
       "int nh, int nkv, float scale, int part_size, int num_parts, int packed, Tensor(e!)? counters=None, "
-      "Tensor? qkv_part=None, int part_splits=0, Tensor? part_ss=None, float inv_k=0., float eps=0.) -> ()");
+      "Tensor? qkv_part=None, int part_splits=0, Tensor? part_ss=None, float inv_k=0., float eps=0., int window=0) -> ()");
   m.def(
       "rope_kv_write_f8(Tensor(a!) qkv, Tensor positions, Tensor cos, Tensor sin, Tensor(b!) k_cache, "
       "Tensor(c!) v_cache, Tensor(d!) k_scale, Tensor(e!) v_scale, Tensor slots, int nh, int nkv) -> ()");
   m.def(
       "paged_attention_f8(Tensor q, Tensor k_cache, Tensor v_cache, Tensor k_scale, Tensor v_scale, "
       "Tensor block_tables, Tensor q_seq, Tensor q_ctx, Tensor(a!) out, Tensor(b!) workspace, int nh, int nkv, "
-      "float scale, int part_size, int num_parts, int packed, Tensor(c!)? counters=None) -> ()");
+      "float scale, int part_size, int num_parts, int packed, Tensor(c!)? counters=None, int window=0) -> ()");
   m.def(
       "paged_attention_rope_f8(Tensor qkv, Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor(c!) k_scale, "
       "Tensor(d!) v_scale, Tensor block_tables, Tensor q_seq, Tensor q_ctx, Tensor positions, Tensor cos, Tensor sin, "
       "Tensor slots, Tensor(e!) out, Tensor(f!) workspace, int nh, int nkv, float scale, int part_size, "
       "int num_parts, int packed, Tensor(g!)? counters=None, Tensor? qkv_part=None, int part_splits=0, "
-      "Tensor? part_ss=None, float inv_k=0., float eps=0.) -> ()");
+      "Tensor? part_ss=None, float inv_k=0., float eps=0., int window=0) -> ()");
   m.def(
       "attention_mfma(Tensor q, Tensor k_cache, Tensor v_cache, Tensor block_tables, Tensor q_seq, Tensor q_ctx, "
       "Tensor qblocks, Tensor(a!) out, Tensor(b!) workspace, int nh, int nkv, float scale, int part_size, "
-      "int num_parts, int packed, Tensor? superblocks=None) -> ()");
+      "int num_parts, int packed, Tensor? superblocks=None, int window=0) -> ()");
   m.def(
       "attention_fa(Tensor q, Tensor k_cache, Tensor v_cache, Tensor block_tables, Tensor q_seq, Tensor q_ctx, "
       "Tensor fablocks, Tensor(a!) out, Tensor(b!) workspace, int nh, int nkv, float scale, int part_size, "
-      "int num_parts, int waves, int pair=0) -> ()");
+      "int num_parts, int waves, int pair=0, int window=0) -> ()");
   m.def(
       "attention_fa_f8(Tensor q, Tensor k_cache, Tensor v_cache, Tensor k_scale, Tensor v_scale, Tensor block_tables, "
       "Tensor q_seq, Tensor q_ctx, Tensor fablocks, Tensor(a!) out, Tensor(b!) workspace, int nh, int nkv, "
-      "float scale, int part_size, int num_parts, int waves, int pair=0) -> ()");
+      "float scale, int part_size, int num_parts, int waves, int pair=0, int window=0) -> ()");
   m.def(
       "attention_mfma_rope(Tensor qkv, Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor block_tables, Tensor q_seq, "
       "Tensor q_ctx, Tensor qblocks, Tensor positions, Tensor cos, Tensor sin, Tensor slots, Tensor(c!) out, "
       "Tensor(d!) workspace, int nh, int nkv, float scale, int part_size, int num_parts, int packed, "
       "Tensor? qkv_part=None, int part_splits=0, Tensor? part_ss=None, float inv_k=0., float eps=0., "
-      "Tensor(e!)? mx_ax=None, Tensor(f!)? mx_as=None) -> ()");
+      "Tensor(e!)? mx_ax=None, Tensor(f!)? mx_as=None, int window=0) -> ()");
   m.def(
       "attention_mfma_f8(Tensor q, Tensor k_cache, Tensor v_cache, Tensor k_scale, Tensor v_scale, "
       "Tensor block_tables, Tensor q_seq, Tensor q_ctx, Tensor qblocks, Tensor(a!) out, Tensor(b!) workspace, int nh, "
-      "int nkv, float scale, int part_size, int num_parts, int packed) -> ()");
+      "int nkv, float scale, int part_size, int num_parts, int packed, int window=0) -> ()");
   m.def(
       "attention_mfma_rope_f8(Tensor qkv, Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor(c!) k_scale, "
       "Tensor(d!) v_scale, Tensor block_tables, Tensor q_seq, Tensor q_ctx, Tensor qblocks, Tensor positions, "
       "Tensor cos, Tensor sin, Tensor slots, Tensor(e!) out, Tensor(f!) workspace, int nh, int nkv, float scale, "
       "int part_size, int num_parts, int packed, Tensor? qkv_part=None, int part_splits=0, Tensor? part_ss=None, "
-      "float inv_k=0., float eps=0.) -> ()");
+      "float inv_k=0., float eps=0., int window=0) -> ()");
   m.def("embedding(Tensor ids, Tensor table, Tensor(a!) out) -> ()");
   m.def("swiglu(Tensor gu, Tensor(a!) out) -> ()");
   m.def("add(Tensor a, Tensor b, Tensor(a!) y) -> ()");

@@ -46,6 +46,8 @@ struct AttnArgs {
   const float* sin_t;
   const int64_t* slots;            //   [T] cache slot of the new token (< 0: nothing written)
   QkvPart qp;                      // qp.part == nullptr: absent
+  int window;                      // sliding window W: a query of context ctx sees cache positions
+                                   //   [max(0, ctx - W), ctx); 0: no window (decode kernels only)
 };
 
 // log2 of the page size, or -1 when it is no power of two
@@ -57,6 +59,16 @@ inline int attn_page_log2(const AttnArgs& a) {
 
 // the (max, sum) half of the split-K workspace; the partial outputs start at a.workspace
 inline float* attn_ws_ml(const AttnArgs& a) { return a.workspace + (int64_t)a.T * a.nh * a.NP * a.D; }
+
+// first cache position a query of context ctx sees under the window W (W <= 0: none)
+inline
+#if defined(__HIPCC__)
+    __host__ __device__
+#endif
+    int
+    attn_window_lo(int ctx, int W) {
+  return W > 0 && ctx > W ? ctx - W : 0;
+}
 
 // the softmax scale in the exp2 domain
 inline float attn_scale_log2(const AttnArgs& a) { return a.scale * 1.4426950408889634f; }

@@ -130,8 +130,13 @@ def kv_write(k, v, k_cache, v_cache, slots):
     _scatter_cache(v_cache, slots, v.reshape(v.shape[0], nkv, D))
 
 
-def paged_attention(q, k_cache, v_cache, block_tables, q_seq, q_ctx, nh, nkv, scale, out=None):
-    """softmax(q k^T * scale) v over the first q_ctx[t] cached tokens of sequence q_seq[t]."""
+def paged_attention(q, k_cache, v_cache, block_tables, q_seq, q_ctx, nh, nkv, scale, out=None, window=0):
+    """softmax(q k^T * scale) v over the first q_ctx[t] cached tokens of sequence q_seq[t]; with a
+    sliding ``window`` W > 0 over the last W of them only, cache positions ``[max(0, ctx - W), ctx)``
+    (pages wholly below them are not looked up, so their block-table entries may be released)."""
+    window = int(window or 0)
+    if window < 0:
+        raise ValueError(f"window must be >= 0 (0: no sliding window), got {window}")
     T = q.shape[0]
     D = k_cache.shape[-1]
     ps = k_cache.shape[2]
@@ -142,9 +147,11 @@ def paged_attention(q, k_cache, v_cache, block_tables, q_seq, q_ctx, nh, nkv, sc
         n = int(q_ctx[t])
         if n <= 0:
             continue
-        pages = block_tables[int(q_seq[t])][: (n + ps - 1) // ps].long()
-        k = k_cache[pages].permute(1, 0, 2, 3).reshape(nkv, -1, D)[:, :n].float()
-        v = v_cache[pages].permute(1, 0, 2, 3).reshape(nkv, -1, D)[:, :n].float()
+        lo = max(0, n - window) if window else 0
+        p0 = lo // ps  # first page the window reaches into
+        pages = block_tables[int(q_seq[t])][p0: (n + ps - 1) // ps].long()
+        k = k_cache[pages].permute(1, 0, 2, 3).reshape(nkv, -1, D)[:, lo - p0 * ps: n - p0 * ps].float()
+        v = v_cache[pages].permute(1, 0, 2, 3).reshape(nkv, -1, D)[:, lo - p0 * ps: n - p0 * ps].float()
         k = k.repeat_interleave(rep, 0)
         v = v.repeat_interleave(rep, 0)
         s = torch.einsum("hd,hnd->hn", qv[t], k) * scale
@@ -262,10 +269,11 @@ def rope_kv_write_f8(qkv, positions, cos, sin, k_cache: KVF8, v_cache: KVF8, slo
     _scatter_cache_f8(v_cache, slots, v)
 
 
-def paged_attention_f8(q, k_cache: KVF8, v_cache: KVF8, block_tables, q_seq, q_ctx, nh, nkv, scale, out=None):
+def paged_attention_f8(q, k_cache: KVF8, v_cache: KVF8, block_tables, q_seq, q_ctx, nh, nkv, scale, out=None,
+                       window=0):
     """Dequantize, then ``paged_attention``."""
     return paged_attention(q, k_cache.dequant(torch.float32), v_cache.dequant(torch.float32), block_tables, q_seq,
-                           q_ctx, nh, nkv, scale, out=out)
+                           q_ctx, nh, nkv, scale, out=out, window=window)
 
 
 def embedding(ids, table, out=None):

@@ -955,7 +955,7 @@ class PipelineServingEngine:
         for key in (f"{old}:{int(old_handle)}", f"park:{old}:{int(old_handle)}"):
             s = self.ex.sessions.rename(key, self._key(int(handle)))
             if s is not None:
-                s.length = min(s.length, int(length))
+                self.ex.sessions.rewind(s, int(length))
                 break
         cache = self.resume.get("cache")
         rows = (self.replay is not None and cache is not None and 0 < length <= cache.max_len and

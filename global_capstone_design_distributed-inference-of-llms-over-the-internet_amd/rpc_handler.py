@@ -382,7 +382,11 @@ class StageConnectionHandler:
         return Message({"cache_tokens_left": ex.sessions.cache_tokens_left(), "sessions": len(ex.sessions.sessions),
                         "start_block": ex.start, "end_block": ex.end, "final_stage": self.final_stage,
                         "quant_type": getattr(ex, "quant_type", "none"),
-                        "kv_cache_dtype": getattr(ex, "kv_cache_dtype", "bf16"), "phases": self.timer.summary(), **self.stats})
+                        "kv_cache_dtype": getattr(ex, "kv_cache_dtype", "bf16"),
+                        # models with a sliding window: "cap" / "attend" and W (None / 0 otherwise)
+                        "sliding_window": getattr(ex, "sliding_window", None),
+                        "window": int(getattr(ex.cfg, "sliding_window", None) or 0),
+                        "phases": self.timer.summary(), **self.stats})
 
     async def rpc_close_session(self, msg: Message) -> Message:
         sid = msg.metadata.get("session_id")

@@ -20,6 +20,7 @@ NOT causal: src/llama_partition.py:118 -> petals/llama/block.py:136-137; see SUR
 from __future__ import annotations
 
 import dataclasses
+import gc
 import logging
 import math
 import os
@@ -128,19 +129,29 @@ class _Pinned:
             self.events[self.k] = ev
 
 
+# what a stage does with a config's ``sliding_window``: cap sessions at it, or attend through it
+SLIDING_WINDOW_MODES = ("cap", "attend")
+
+
 class StageExecutor:
     def __init__(self, cfg: ModelConfig, weights: StageWeights, device, *, dtype=torch.bfloat16,
                  page_size: int = 64, max_sessions: int = 256, max_seq_len: Optional[int] = None,
                  kv_cache_bytes: Optional[int] = None, kv_fraction: float = 0.9, use_graphs: Optional[bool] = None,
                  graph_max_batch: int = 256, max_tokens_per_step: int = 8192, offload: bool = False,
                  keep_layers_on_gpu: int = 0, tp=None, warmup: Optional[bool] = None,
-                 kv_cache_dtype: str = "bf16"):
+                 kv_cache_dtype: str = "bf16", sliding_window: str = "cap"):
         """``tp``: a ``parallel.tensor_parallel.TPGroup`` when ``weights`` is a tensor-parallel
         shard (``cfg`` is then the shard config); partial sums are all-reduced after the
         o and down projections.  ``kv_cache_dtype="fp8"``: e4m3 pages + e8m0 row scales
         (runtime/kv_cache.py); attention then runs the fp8 forms of the flash-decoding, MFMA GQA decode
-        and FA2 prefill kernels (``_attend``)."""
+        and FA2 prefill kernels (``_attend``).  ``sliding_window`` (configs with ``sliding_window``
+        W, e.g. Mistral): "cap" limits sessions to W tokens, inside which full causal attention is
+        the windowed one; "attend" lets them grow to ``max_seq_len``: every query attends to its last
+        W keys only (``window`` of the decode kernels) and the session's KV pages roll
+        (runtime/session.py).  GPT-2 and configs without a window ignore it."""
         cfg.validate()
+        if sliding_window not in SLIDING_WINDOW_MODES:
+            raise ValueError(f"sliding_window must be one of {SLIDING_WINDOW_MODES}, got {sliding_window!r}")
         if kv_cache_dtype not in KV_DTYPES:
             raise ValueError(f"kv_cache_dtype must be one of {KV_DTYPES}, got {kv_cache_dtype!r}")
         if kv_cache_dtype == "fp8" and cfg.model_type == "gpt2":
@@ -166,7 +177,11 @@ class StageExecutor:
         self.nh, self.nkv, self.D = cfg.num_attention_heads, cfg.num_key_value_heads, cfg.head_dim
         self.scale = 1.0 / math.sqrt(self.D)
         self.max_seq_len = int(max_seq_len or cfg.max_position_embeddings)
-        if cfg.sliding_window and self.max_seq_len > cfg.sliding_window:
+        # the window every attention call gets (0: none): sessions run past it and their pages roll
+        self.window = int(cfg.sliding_window) if (sliding_window == "attend" and cfg.sliding_window and
+                                                   cfg.model_type != "gpt2") else 0
+        self.sliding_window = "attend" if self.window else ("cap" if cfg.sliding_window else None)
+        if cfg.sliding_window and not self.window and self.max_seq_len > cfg.sliding_window:
             # Mistral / Mixtral sliding-window attention: sessions are capped at the window, inside
             # which sliding-window and full causal attention are the same computation
             logger.info(f"max_seq_len capped at sliding_window={cfg.sliding_window}")
@@ -183,7 +198,7 @@ class StageExecutor:
         num_pages = max(1, min(num_pages, max_useful))
         self.cache = PagedKVCache(self.n_layers, num_pages, self.nkv, self.D, page_size, dtype, self.device,
                                   kv_dtype=kv_cache_dtype)
-        self.sessions = SessionManager(self.cache, max_sessions, self.max_seq_len)
+        self.sessions = SessionManager(self.cache, max_sessions, self.max_seq_len, window=self.window)
         self.use_graphs = (self.device.type == "cuda") if use_graphs is None else bool(use_graphs)
         self.use_graphs = self.use_graphs and self.device.type == "cuda" and cfg.model_type != "gpt2" and \
             os.environ.get("MPAMD_GRAPHS", "1") != "0"
@@ -356,7 +371,7 @@ class StageExecutor:
             if reset and reset[i]:
                 self.sessions.reset(sid)
             if starts is not None and starts[i] is not None and starts[i] < s.length:
-                s.length = int(starts[i])
+                self.sessions.rewind(s, int(starts[i]))
             self.sessions.reserve(s, s.length + int(n))
             sess.append(s)
             ntoks[i] = n
@@ -401,6 +416,7 @@ class StageExecutor:
         for s, n in zip(plan.sessions, plan.ntoks):
             s.length += int(n)
             s.step += 1
+            self.sessions.release(s)  # (sliding window: the pages no later query can see)
 
     # ================================================================== execution
     def forward(self, seqs: Sequence[Tuple[str, int]], x: torch.Tensor, **plan_kw) -> torch.Tensor:
@@ -542,26 +558,35 @@ class StageExecutor:
         other prefill blocks (packed output, shapes outside ``fa_ok``) run on the latter as
         per-query causal rows (``qblocks`` is ignored)."""
         table = self.sessions.table_dev
+        # sliding window: the decode kernels take it; the prefill kernels (FA2, grouped MFMA) have no
+        # windowed form, so a prefill step keeps them only while no row is past the window (the same
+        # computation) and otherwise runs the flash-decoding kernel as per-query causal rows
+        win = self.window
+        if win and qblocks is not None and max_ctx > win:
+            return ops.paged_attention(qkv, kc, vc, table, q_seq, q_ctx, self.nh, self.nkv, self.scale, out=out,
+                                       workspace=ws, part_size=ps, num_parts=np_, packed=packed,
+                                       window=win, max_ctx=max_ctx)
         if qblocks is None and self.gqa_decode_mfma_f8 and self.device.type == "cuda":
             ps2 = 128 * math.ceil(ps / 128)
             np2 = max(1, math.ceil(ps * np_ / ps2))
             return ops.attention_mfma_f8(qkv, kc, vc, table, q_seq, q_ctx, self.decode_qblocks(qkv.shape[0]), self.nh,
                                          self.nkv, self.scale, out=out, workspace=ws, part_size=ps2, num_parts=np2,
-                                         packed=packed)
+                                         packed=packed, window=win, max_ctx=max_ctx)
         fb = getattr(self, "_cur_fb", None)
         if self.prefill_fa_f8 and qblocks is not None and fb is not None and not packed:
             return ops.attention_fa_f8(qkv, kc, vc, table, q_seq, q_ctx, fb, self.nh, self.nkv, self.scale, out=out,
                                        workspace=ws, max_ctx=max_ctx, waves=getattr(self, "_cur_fw", 4))
         if self._kv_fp8:
             return ops.paged_attention(qkv, kc, vc, table, q_seq, q_ctx, self.nh, self.nkv, self.scale, out=out,
-                                       workspace=ws, part_size=ps, num_parts=np_, packed=packed)
+                                       workspace=ws, part_size=ps, num_parts=np_, packed=packed,
+                                       window=win, max_ctx=max_ctx)
         if qblocks is None and self.gqa_decode_mfma and self.device.type == "cuda":
             T = qkv.shape[0]
             ps2 = 128 * math.ceil(ps / 128)
             np2 = max(1, math.ceil(ps * np_ / ps2))
             return ops.attention_mfma(qkv, kc, vc, table, q_seq, q_ctx, self.decode_qblocks(T), self.nh, self.nkv,
                                       self.scale, out=out, workspace=ws, part_size=ps2, num_parts=np2,
-                                      packed=packed)
+                                      packed=packed, window=win, max_ctx=max_ctx)
         if qblocks is not None and fb is not None and not packed:
             return ops.attention_fa(qkv, kc, vc, table, q_seq, q_ctx, fb, self.nh, self.nkv, self.scale, out=out,
                                     workspace=ws, max_ctx=max_ctx, waves=getattr(self, "_cur_fw", 4))
@@ -570,7 +595,8 @@ class StageExecutor:
                                       out=out, workspace=ws, max_ctx=max_ctx, packed=packed,
                                       superblocks=getattr(self, "_cur_sb", None))
         return ops.paged_attention(qkv, kc, vc, table, q_seq, q_ctx, self.nh, self.nkv, self.scale, out=out,
-                                   workspace=ws, part_size=ps, num_parts=np_, packed=packed)
+                                   workspace=ws, part_size=ps, num_parts=np_, packed=packed,
+                                   window=win, max_ctx=max_ctx)
 
     def _qkv_fold(self, T: int) -> bool:
         """Decode steps of T rows: qkv as split-K partial slabs folded into the attention kernel's
@@ -601,19 +627,21 @@ class StageExecutor:
             return ops.attention_mfma_rope(qkv, kc, vc, self.sessions.table_dev, q_seq, q_ctx, self.decode_qblocks(T),
                                            positions, self.cos, self.sin, slots, self.nh, self.nkv, self.scale,
                                            out=out, workspace=ws, part_size=ps2, num_parts=np2, packed=packed,
-                                           qkv_part=qkv_part, mx_out=mx)
+                                           qkv_part=qkv_part, mx_out=mx, window=self.window, max_ctx=max_ctx)
         if decode and qblocks is None and self._fuse_rope and self.gqa_decode_mfma_f8 and self.device.type == "cuda":
             ps2 = 128 * math.ceil(ps / 128)
             np2 = max(1, math.ceil(ps * np_ / ps2))
             return ops.attention_mfma_rope_f8(qkv, kc, vc, self.sessions.table_dev, q_seq, q_ctx,
                                               self.decode_qblocks(qkv.shape[0]), positions, self.cos, self.sin, slots,
                                               self.nh, self.nkv, self.scale, out=out, workspace=ws, part_size=ps2,
-                                              num_parts=np2, packed=packed, qkv_part=qkv_part)
+                                              num_parts=np2, packed=packed, qkv_part=qkv_part, window=self.window,
+                                              max_ctx=max_ctx)
         if decode and qblocks is None and self._fuse_rope and not (
                 self.gqa_decode_mfma and not self._kv_fp8 and self.device.type == "cuda"):
             return ops.paged_attention_rope(qkv, kc, vc, self.sessions.table_dev, q_seq, q_ctx, positions, self.cos,
                                             self.sin, slots, self.nh, self.nkv, self.scale, out=out, workspace=ws,
-                                            part_size=ps, num_parts=np_, packed=packed, qkv_part=qkv_part)
+                                            part_size=ps, num_parts=np_, packed=packed, qkv_part=qkv_part,
+                                            window=self.window, max_ctx=max_ctx)
         if qkv_part is not None:
             raise RuntimeError("qkv partial slabs need a fused RoPE decode attention path")
         ops.rope_kv_write(qkv, positions, self.cos, self.sin, kc, vc, slots, self.nh, self.nkv)
@@ -639,7 +667,7 @@ class StageExecutor:
         else:
             h = x
         if attn_part is None:
-            attn_part = ops.attention_partition(T, self.nkv, max_ctx, min_part=self._attn_min_part)
+            attn_part = ops.attention_partition(T, self.nkv, self._attn_span(max_ctx), min_part=self._attn_min_part)
         ps, np_ = attn_part
         ws = e("attn_ws", (max(1, T * self.nh * np_ * (self.D + 2)),), torch.float32)
         res = e("res", (T, H))
@@ -1181,12 +1209,19 @@ class StageExecutor:
         c = max(c, 256)
         return 1 << (c - 1).bit_length()
 
+    def _attn_span(self, ctx: int) -> int:
+        """Tokens per query the attention kernels stream at context ``ctx``: under a sliding window W
+        at most W + 31 (the MFMA kernel starts at the 32-token step that holds the first key)."""
+        return min(int(ctx), self.window + 31) if self.window else int(ctx)
+
     def _graph_key(self, T: int, max_ctx: int, hooked: bool, slot: int = 0, tag: int = 0) -> tuple:
         """(batch bucket, attention part size, parts, qkv fold, hooked, owner tag, input slot).  Slot 0
         (tag 0) is the graph every caller replays; slots 1 / 2 are an owner's two receive graphs
         (``graph_input``)."""
         B = self._bucket(T)
-        ctxb = min(self._ctx_bucket(max_ctx), self._ctx_bucket(self.max_seq_len))
+        # (sliding window: the streamed span is bucketed, not the context - a session far past the
+        # window replays one graph; the kernels compute each row's first key from q_ctx themselves)
+        ctxb = self._attn_span(min(self._ctx_bucket(max_ctx), self._ctx_bucket(self.max_seq_len)))
         part = ops.attention_partition(B, self.nkv, ctxb, min_part=self._attn_min_part)
         return (B, part[0], part[1], self._qkv_fold(B), bool(hooked), int(tag), int(slot))
 
@@ -1355,12 +1390,23 @@ class _DecodeGraph:
                 ex._forward_llama(*args, decode=True)
         torch.cuda.current_stream().wait_stream(s)
         self.graph = torch.cuda.CUDAGraph()
-        # thread-local capture: another thread's stream work (a channel receive posted outside the
-        # executor lock) neither breaks this capture nor fails because of it
-        with torch.cuda.graph(self.graph, pool=pool, capture_error_mode="thread_local"):
-            self.out = ex._forward_llama(*args, decode=True)
-            if hook is not None:  # recorded only: the warm-up runs above never call it
-                hook(self.out)
+        # Python's cyclic collector must not run inside the capture: a dead executor and its graphs
+        # (executor <-> _DecodeGraph reference cycles, freed by the collector only) would be destroyed
+        # on the capturing thread in mid-capture, which the runtime answers with an abort.  Collect
+        # them now (torch.cuda.graph no longer does) and hold the collector off until capture_end.
+        gc.collect()
+        gc_on = gc.isenabled()
+        gc.disable()
+        try:
+            # thread-local capture: another thread's stream work (a channel receive posted outside the
+            # executor lock) neither breaks this capture nor fails because of it
+            with torch.cuda.graph(self.graph, pool=pool, capture_error_mode="thread_local"):
+                self.out = ex._forward_llama(*args, decode=True)
+                if hook is not None:  # recorded only: the warm-up runs above never call it
+                    hook(self.out)
+        finally:
+            if gc_on:
+                gc.enable()
         self.mark_replayed()  # the warm-up runs read ``x``: a receive into it waits for them
 
     def replay(self, plan: Plan, x: torch.Tensor) -> torch.Tensor:

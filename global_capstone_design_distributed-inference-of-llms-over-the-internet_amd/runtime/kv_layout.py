@@ -47,6 +47,9 @@ def export_session_kv(cache, session, layers: Optional[Sequence[int]] = None,
     t = session.length if length is None else int(length)
     if t > session.length:
         raise ValueError(f"session holds {session.length} tokens, asked for {t}")
+    if getattr(session, "first_page", 0):
+        raise ValueError(f"session {session.sid[:8]} has released the pages below its sliding window: a rolled "
+                         "session cannot be exported")
     ps = cache.page_size
     npg = -(-t // ps)
     idx = torch.tensor(session.pages[:npg], dtype=torch.long, device=cache.device)

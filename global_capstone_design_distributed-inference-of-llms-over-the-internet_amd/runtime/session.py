@@ -5,6 +5,12 @@ Reference: the stage handler keeps ``self._kv_cache[session_id]`` forever
 ``max_length``.  Here a session owns a row of a block table and a list of KV pages;
 ``max_length`` is enforced, pages are returned on close, and idle sessions expire after
 a TTL (``evict_expired``) so a crashed client cannot leak HBM.
+
+With a sliding ``window`` W the pages roll: a query at position i sees keys j with 0 <= i - j < W, so
+once a step is committed at length L no later query can see a position below L + 1 - W.  ``release``
+returns every page wholly below that bound to the allocator and sets its block-table entry to -1.
+The table keeps absolute columns; a session's ``pages`` are the held ones, of columns
+``first_page`` onwards - at most ceil(W / page_size) + 1 of them after a commit.
 """
 from __future__ import annotations
 
@@ -25,7 +31,8 @@ class SessionState:
     row: int
     max_length: int
     length: int = 0
-    pages: List[int] = dataclasses.field(default_factory=list)
+    pages: List[int] = dataclasses.field(default_factory=list)  # held pages: table columns first_page ...
+    first_page: int = 0  # > 0 once a sliding window has released the pages below it
     created: float = dataclasses.field(default_factory=time.monotonic)
     last_used: float = dataclasses.field(default_factory=time.monotonic)
     generated: List[int] = dataclasses.field(default_factory=list)
@@ -34,7 +41,11 @@ class SessionState:
 
 class SessionManager:
     def __init__(self, cache: PagedKVCache, max_sessions: int = 256, max_seq_len: int = 4096,
-                 ttl_seconds: float = 600.0):
+                 ttl_seconds: float = 600.0, window: int = 0):
+        """``window``: sliding-window width in tokens (0: none, pages are kept until the session closes)."""
+        if int(window) < 0:
+            raise ValueError(f"window must be >= 0, got {window}")
+        self.window = int(window)
         self.cache = cache
         self.page_size = cache.page_size
         self.max_sessions = max_sessions
@@ -85,6 +96,7 @@ class SessionManager:
                 return
             self.cache.allocator.free(s.pages)
             s.pages = []
+            s.first_page = 0
             s.length = 0
             s.generated = []
             self.table[s.row, :] = -1
@@ -122,12 +134,13 @@ class SessionManager:
             s = self.sessions[src]
             d = self.open(dst, max_length or s.max_length)
             self.reset(dst)
-            if s.pages:
+            if s.pages:  # the held pages only: a rolled source has none below its window
                 new = self.cache.allocator.alloc(len(s.pages))
                 self.cache.copy_pages(s.pages, new)
-                self.table[d.row, : len(new)] = new
+                self.table[d.row, s.first_page: s.first_page + len(new)] = new
                 d.pages = list(new)
                 self._dirty = True
+            d.first_page = s.first_page
             d.length = s.length
             d.generated = list(s.generated)
             d.last_used = time.monotonic()
@@ -159,7 +172,8 @@ class SessionManager:
         """Make sure pages exist for positions [0, total_len)."""
         if total_len > s.max_length:
             raise ValueError(f"session {s.sid[:8]}: length {total_len} exceeds max_length {s.max_length}")
-        need = pages_needed(total_len, self.page_size) - len(s.pages)
+        have = s.first_page + len(s.pages)
+        need = pages_needed(total_len, self.page_size) - have
         if need > 0:
             with self.lock:
                 try:
@@ -167,10 +181,42 @@ class SessionManager:
                 except AllocationFailed:
                     self.evict_expired()
                     new = self.cache.allocator.alloc(need)
-                self.table[s.row, len(s.pages):len(s.pages) + need] = new
+                self.table[s.row, have:have + need] = new
                 s.pages.extend(new)
                 self._dirty = True
         s.last_used = time.monotonic()
+
+    def release(self, s: SessionState) -> int:
+        """Sliding window: after a step is committed at ``s.length``, return the pages whose positions
+        all lie below ``s.length + 1 - window`` (no later query sees them); their table entries
+        become -1.  Returns the number of pages released (0 without a window)."""
+        if not self.window:
+            return 0
+        k = min(max(0, s.length + 1 - self.window) // self.page_size - s.first_page, len(s.pages))
+        if k <= 0:
+            return 0
+        with self.lock:
+            self.cache.allocator.free(s.pages[:k])
+            del s.pages[:k]
+            self.table[s.row, s.first_page:s.first_page + k] = -1
+            s.first_page += k
+            self._dirty = True
+        return k
+
+    def rewind(self, s: SessionState, position: int) -> None:
+        """Continue the session from ``position`` (Petals ``start_from_position``).  Under a sliding
+        window the next query, at ``position``, sees keys from ``max(0, position + 1 - window)``:
+        the page that holds that key must still be held."""
+        position = int(position)
+        if position < 0:
+            raise ValueError(f"session {s.sid[:8]}: cannot rewind to position {position}")
+        if position >= s.length:
+            return
+        if self.window and max(0, position + 1 - self.window) // self.page_size < s.first_page:
+            raise ValueError(f"session {s.sid[:8]}: cannot rewind to position {position}: the sliding window of "
+                             f"{self.window} tokens has released the pages below position "
+                             f"{s.first_page * self.page_size}")
+        s.length = position
 
     def sync_table(self, stream=None) -> torch.Tensor:
         if self._dirty:

@@ -28,6 +28,8 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--fp8", action="store_true")
     ap.add_argument("--kv_cache_dtype", default="bf16", choices=["bf16", "fp8"])
+    ap.add_argument("--sliding_window", default="cap", choices=["cap", "attend"],
+                    help="models with a sliding window: attend = the prompt may pass it (windowed rows)")
     a = ap.parse_args()
 
     from src.models.config import resolve_model
@@ -41,7 +43,8 @@ def main():
     T = a.batch * a.prompt_len
     ex = StageExecutor(cfg, w, dev, max_sessions=a.batch + 4, max_seq_len=a.prompt_len + 64,
                        kv_cache_bytes=16 << 30, max_tokens_per_step=T,
-                       **({"kv_cache_dtype": a.kv_cache_dtype} if a.kv_cache_dtype != "bf16" else {}))
+                       **({"kv_cache_dtype": a.kv_cache_dtype} if a.kv_cache_dtype != "bf16" else {}),
+                       **({"sliding_window": a.sliding_window} if a.sliding_window != "cap" else {}))
     g = torch.Generator().manual_seed(0)
     ids = torch.randint(0, cfg.vocab_size, (T,), generator=g).to(dev)
     seqs = [(f"s{i}", a.prompt_len) for i in range(a.batch)]
@@ -58,7 +61,8 @@ def main():
     proj = L * (H * (cfg.q_dim + 2 * cfg.kv_dim) + cfg.q_dim * H + 3 * H * F)
     attn = L * 2 * a.batch * cfg.num_attention_heads * cfg.head_dim * a.prompt_len * (a.prompt_len + 1)
     flops = 2 * proj * T + attn + 2 * H * cfg.vocab_size * a.batch
-    print(json.dumps({"model": a.model, "kv_cache_dtype": a.kv_cache_dtype, "batch": a.batch, "prompt_len": a.prompt_len, "tokens": T,
+    print(json.dumps({"model": a.model, "kv_cache_dtype": a.kv_cache_dtype, "sliding_window": a.sliding_window,
+                      "window": ex.window, "batch": a.batch, "prompt_len": a.prompt_len, "tokens": T,
                       "cold_s": round(times[0], 4), "warm_s": round(warm, 4),
                       "warm_all_s": [round(t, 5) for t in times[1:]],
                       "warm_tokens_per_s": round(T / warm, 1), "warm_tflops": round(flops / warm / 1e12, 1)}),
