@@ -822,6 +822,77 @@ def _attention_fa(q, k_cache, v_cache, block_tables, q_seq, q_ctx, fablocks, nh,
     return out
 
 
+def attention_fa_window(q, k_cache, v_cache, block_tables, q_seq, q_ctx, fablocks, nh, nkv, scale, window, out=None,
+                        workspace=None, max_ctx=None, waves=None, num_parts=None, pair=None, part_size=None):
+    """``attention_fa`` under a sliding window W = ``window`` > 0 (csrc/attention_fa.hip WIN form): a
+    query of context ctx sees cache positions [max(0, ctx - W), ctx), the decode kernels' rule.  A block
+    streams from the 64-token step that holds its first row's first key, and the parts split that
+    span (at most W + tokens per block + 62), not the context; ``part_size`` (a multiple of 64) with
+    ``num_parts`` sets the slices explicitly and must cover the span.  No block-table entry below the
+    page of a block's first visible key is read (rolling pages)."""
+    _no_kv_f8(k_cache, v_cache, "attention_fa_window")
+    return _attention_fa_window(q, k_cache, v_cache, block_tables, q_seq, q_ctx, fablocks, nh, nkv, scale, window, out,
+                                workspace, max_ctx, waves, num_parts, pair, part_size)
+
+
+def attention_fa_window_f8(q, k_cache, v_cache, block_tables, q_seq, q_ctx, fablocks, nh, nkv, scale, window,
+                           out=None, workspace=None, max_ctx=None, waves=None, num_parts=None, pair=None,
+                           part_size=None):
+    """``attention_fa_window`` on an fp8 KV cache (``KVF8``): only the staging differs, so the output
+    equals ``attention_fa_window`` on the dequantized cache bit for bit."""
+    _need_kv_f8(k_cache, v_cache, "attention_fa_window_f8")
+    return _attention_fa_window(q, k_cache, v_cache, block_tables, q_seq, q_ctx, fablocks, nh, nkv, scale, window, out,
+                                workspace, max_ctx, waves, num_parts, pair, part_size)
+
+
+def fa_window_pad(nh: int, nkv: int, waves: int) -> int:
+    """``pad`` of ``_window_span`` for the windowed FA2 kernel: BT + 62, BT = the most tokens a block
+    holds.  A block of n consecutive tokens with first context c streams from ``base = max(0, c - W) &
+    ~63`` to ``c + n - 1``: at most W + n + 62 tokens."""
+    return max(1, (32 * int(waves)) // max(1, nh // nkv)) + 62
+
+
+def _attention_fa_window(q, k_cache, v_cache, block_tables, q_seq, q_ctx, fablocks, nh, nkv, scale, window, out,
+                         workspace, max_ctx, waves, num_parts, pair, part_size):
+    """``attention_fa_window`` / ``attention_fa_window_f8``: ``_attention_fa``'s partition rule on the
+    streamed span, its pairing rule, and the launch."""
+    window = int(window)
+    if window <= 0:
+        raise ValueError(f"ops.attention_fa_window: window must be > 0, got {window}")
+    waves = int(waves or FA_WAVES)
+    pad = fa_window_pad(nh, nkv, waves)
+    if part_size is not None:
+        if num_parts is None or int(part_size) <= 0 or int(part_size) % 64:
+            raise ValueError("ops.attention_fa_window: part_size is a positive multiple of 64 given with num_parts")
+        _check_window_parts("attention_fa_window", window, max_ctx, part_size, num_parts, pad)
+    if not _native(q):
+        return paged_attention(q, k_cache, v_cache, block_tables, q_seq, q_ctx, nh, nkv, scale, out=out, window=window)
+    T = q.shape[0]
+    D = k_cache.shape[-1]
+    if part_size is None:
+        if max_ctx is None:
+            max_ctx = int(q_ctx.max().item()) if T else 1
+        span = max(_window_span(window, max_ctx, pad), 1)
+        if num_parts is None:
+            nblk = fablocks.shape[1] * (nh // (nh // nkv))
+            want = max(1, math.ceil(512 / max(1, nblk)))
+            num_parts = max(1, min(want, math.ceil(span / 256)))
+        part_size = 64 * math.ceil(math.ceil(span / max(1, int(num_parts))) / 64)
+        num_parts = math.ceil(span / part_size)
+    if out is None:
+        out = torch.empty(T, nh * D, dtype=q.dtype, device=q.device)
+    workspace = _attn_workspace(workspace, T, nh, D, num_parts, q.device)
+    if pair is None:
+        pair = fa_pair(int(fablocks.shape[1]), nh, nkv, num_parts)
+    tail = (block_tables, q_seq, q_ctx, fablocks, out, workspace, int(nh), int(nkv), float(scale), int(part_size),
+            int(num_parts), waves, int(bool(pair) and num_parts == 1), window)
+    if isinstance(k_cache, KVF8):
+        torch.ops.mpamd.attention_fa_window_f8(q, k_cache.codes, v_cache.codes, k_cache.scales, v_cache.scales, *tail)
+    else:
+        torch.ops.mpamd.attention_fa_window(q, k_cache, v_cache, *tail)
+    return out
+
+
 def attention_mfma_rope(qkv, k_cache, v_cache, block_tables, q_seq, q_ctx, qblocks, positions, cos, sin, slots, nh,
                         nkv, scale, out=None, workspace=None, part_size=None, num_parts=None, max_ctx=None,
                         packed=False, qkv_part=None, mx_out=None, window=0):

@@ -30,6 +30,15 @@
 // kvf8_dequant8) right before the LDS store.  The LDS image is the one the bf16 form builds on a bf16
 // cache of the dequantized values, and everything after it is shared, so the output equals the bf16
 // form's on that cache bit for bit.
+//
+// WIN (sliding window W, mp_attention_fa_window): row of context ctx sees [lo, ctx), lo = max(0, ctx - W),
+// the decode kernels' rule.  A block streams [base, grp_ctx), base = the 64-token step that holds the
+// lo of its first row, and slice p of a split launch is [base + p PS, base + (p + 1) PS): pages below
+// base's are never looked up (rolling pages have released them).  The score mask gains tk >= lo, a wave
+// skips the steps wholly below its rows' smallest lo (the lower twin of the causal skip), and the stash
+// zeroes K / V rows below the block's smallest lo as it zeroes rows past the context.  A real row can
+// be fully masked in the block's first steps (its lo can lie whole steps above base): the m == -inf guards
+// that serve padding rows serve it.  WIN is a template parameter: the unwindowed forms compile as before.
 #include <type_traits>
 
 #include "common.h"
@@ -71,14 +80,14 @@ __device__ __forceinline__ unsigned pk_bf16(float a, float b) {
 
 constexpr float FA_RESCALE_THR = 8.f;  // log2 units: P may reach 2^8 before O / l are rescaled (T13)
 
-template <int HB, int NW, bool F8 = false>
+template <int HB, int NW, bool F8 = false, bool WIN = false>
 __global__ __launch_bounds__(NW * 64) void attn_fa_kernel(
     const bf16_t* __restrict__ q, int64_t q_stride, const bf16_t* __restrict__ kc, const bf16_t* __restrict__ vc,
     const int32_t* __restrict__ block_tables, int bt_stride, const int32_t* __restrict__ q_seq,
     const int32_t* __restrict__ q_ctx, const int32_t* __restrict__ fb_tok0, const int32_t* __restrict__ fb_ntok,
     int NBF, bf16_t* __restrict__ out, int64_t out_stride, float* __restrict__ part_o, float* __restrict__ part_ml,
     int nkv, int nh, int page_log2, int PS, int NP, float scale_log2, int pair, const uint8_t* __restrict__ ks,
-    const uint8_t* __restrict__ vs) {
+    const uint8_t* __restrict__ vs, int window) {
   constexpr int D = 128;
   constexpr int STEP = 64;
   constexpr int TILE = STEP * D * 2;            // bytes of one K or V tile (16 KiB)
@@ -118,8 +127,16 @@ __global__ __launch_bounds__(NW * 64) void attn_fa_kernel(
   const int wt_first = (32 * w) / HB, wt_last = min((32 * w + 31) / HB, ntok - 1);
   const bool wave_rows = wt_first < ntok;
   const int wave_ctx = wave_rows ? q_ctx[tok0 + wt_last] : 0;
-  const int start = p * PS, end = min(start + PS, grp_ctx);
+  // WIN: contexts are non-decreasing along the block, so its first row's lo is the smallest; the block
+  // streams [base, grp_ctx) from the 64-token step that holds blk_lo (inside blk_lo's page: pages are
+  // multiples of 64, and no block-table entry below that page is looked up) and slices count from base
+  const int blk_lo = WIN ? attn_window_lo(q_ctx[tok0], window) : 0;
+  const int base = WIN ? (blk_lo & ~(STEP - 1)) : 0;
+  const int start = base + p * PS, end = min(start + PS, grp_ctx);
   const int wave_lim0 = wave_rows ? min(q_ctx[tok0 + wt_first], end) : 0;  // smallest limit of its rows
+  // smallest and largest lo of the wave's rows
+  const int wave_lo0 = WIN && wave_rows ? attn_window_lo(q_ctx[tok0 + wt_first], window) : 0;
+  const int wave_lo1 = WIN && wave_rows ? attn_window_lo(wave_ctx, window) : 0;
 
   const int r = lane & 31, hh = lane >> 5;
   const int my_row = 32 * w + r;
@@ -127,6 +144,7 @@ __global__ __launch_bounds__(NW * 64) void attn_fa_kernel(
   const bool row_ok = my_t < ntok;
   const int my_ctx = row_ok ? q_ctx[tok0 + my_t] : 0;
   const int lim = min(my_ctx, end);
+  const int my_lo = WIN ? attn_window_lo(my_ctx, window) : 0;
 
   u16x8 qf[D / 16];
 #pragma unroll
@@ -176,7 +194,9 @@ __global__ __launch_bounds__(NW * 64) void attn_fa_kernel(
 #pragma unroll
     for (int j = 0; j < CPT; ++j) {
       const int c = tid + NT * j, row = c >> 4, ch = c & 15;
-      const bool past = s0 + row >= end;  // past the context: stale cache bytes never meet a p = 0
+      // past the context: stale cache bytes never meet a p = 0; WIN: nor do the rows below the block's
+      // window (rows from blk_lo up to a row's own lo are other rows' keys and stay: masked by the select)
+      const bool past = s0 + row >= end || (WIN && s0 + row < blk_lo);
       u16x8 kv, vv;                       // (F8: a page tail's 0xFF codes / scales convert to NaN, zeroed here)
       if constexpr (F8) {
         kv = kvf8_dequant8(kreg[j], ke[j]);
@@ -211,7 +231,7 @@ __global__ __launch_bounds__(NW * 64) void attn_fa_kernel(
     const int cur = it & 1;
     const bool more = b0 + STEP < end;
     if (more) fetch(b0 + STEP);
-    if (b0 < wave_ctx) {
+    if (b0 < wave_ctx && (!WIN || b0 + STEP > wave_lo0)) {  // causal skip and its lower twin
       const unsigned char* tb = smem + cur * 2 * TILE;
       // ---- S^T = K . Q^T for the step's 64 tokens: 4 independent accumulation chains
       //      (two 32-token subtiles x two halves of d), summed afterwards ----
@@ -233,13 +253,16 @@ __global__ __launch_bounds__(NW * 64) void attn_fa_kernel(
       for (int sub = 0; sub < 2; ++sub) st[sub] = sa[sub][0] + sa[sub][1];
       // ---- online softmax of row r over this lane's 32 tokens (raw scores; the scale is
       //      folded into the exponent's FMA) ----
-      if (b0 + STEP > wave_lim0) {  // diagonal / last step: causal and context mask
+      // diagonal / last step: causal and context mask; WIN: also a step that starts below some row's lo.
+      // A select, never a product: a NaN score below the window is replaced
+      if (b0 + STEP > wave_lim0 || (WIN && b0 < wave_lo1)) {
 #pragma unroll
         for (int sub = 0; sub < 2; ++sub)
 #pragma unroll
           for (int j = 0; j < 16; ++j) {
             const int tk = b0 + 32 * sub + 4 * hh + (j & 3) + 8 * (j >> 2);
-            st[sub][j] = tk < lim ? st[sub][j] : -INFINITY;
+            const bool seen = WIN ? (tk < lim && tk >= my_lo) : tk < lim;
+            st[sub][j] = seen ? st[sub][j] : -INFINITY;
           }
       }
       float lm = -INFINITY;
@@ -339,12 +362,10 @@ __global__ void paged_attn_reduce_kernel(const float* __restrict__ part_o, const
 // / heads_per_block consecutive tokens of ONE sequence, ops.fa_blocks).  D = 128, page_size a
 // multiple of 64, heads_per_block = nh / nkv in {1, 2, 4, 8}; row-major output [T, nh * D].
 // a.ks != nullptr: the fp8 cache's code pages and row scales (kv_f8.h), the kernel's F8 form.
-extern "C" int mp_attention_fa(const mp::AttnArgs* args, const int32_t* fb_tok0, const int32_t* fb_ntok, int NBF,
-                               int nw, int pair, hipStream_t stream) {
-  (void)hipGetLastError();  // an earlier non-mpamd HIP call's stale error is not this launch's
+// win: the kernel's WIN form under a.window > 0 (the two C entries below check the window themselves).
+static int fa_launch(const mp::AttnArgs& a, const int32_t* fb_tok0, const int32_t* fb_ntok, int NBF, int nw, int pair,
+                     bool win, hipStream_t stream) {
   using namespace mp;
-  const AttnArgs& a = *args;
-  if (a.window != 0) return -11;  // no sliding-window form
   if (NBF == 0 || a.T == 0) return 0;
   if (a.D != 128 || a.nh % a.nkv != 0 || a.PS % 64 != 0 || a.NP < 1 || a.page_size % 64 != 0) return -1;
   const int page_log2 = attn_page_log2(a);
@@ -354,29 +375,47 @@ extern "C" int mp_attention_fa(const mp::AttnArgs* args, const int32_t* fb_tok0,
   const int hb = a.nh / a.nkv;
   pair = pair ? 1 : 0;
   const int nbp = pair ? (NBF + 1) / 2 : NBF;
-#define MP_FA(HB_, NW_, F8_)                                                                                       \
-  hipLaunchKernelGGL((attn_fa_kernel<HB_, NW_, F8_>), dim3(nbp * (a.nh / HB_), a.NP), dim3(NW_ * 64), 0, stream,   \
-                     (const bf16_t*)a.q, a.q_stride, (const bf16_t*)a.kc, (const bf16_t*)a.vc, a.bt, a.bt_stride,   \
-                     a.q_seq, a.q_ctx, fb_tok0, fb_ntok, NBF, (bf16_t*)a.out, (int64_t)a.nh * a.D, a.workspace,     \
-                     attn_ws_ml(a), a.nkv, a.nh, page_log2, a.PS, a.NP, attn_scale_log2(a), pair,                   \
-                     (const uint8_t*)a.ks, (const uint8_t*)a.vs)
-#define MP_FA_NW(HB_)                                             \
-  if (f8) {                                                       \
-    if (nw == 8) MP_FA(HB_, 8, true); else MP_FA(HB_, 4, true);   \
-  } else {                                                        \
-    if (nw == 8) MP_FA(HB_, 8, false); else MP_FA(HB_, 4, false); \
-  }
+#define MP_FA(HB_, NW_, F8_, WIN_)                                                                                  \
+  hipLaunchKernelGGL((attn_fa_kernel<HB_, NW_, F8_, WIN_>), dim3(nbp * (a.nh / HB_), a.NP), dim3(NW_ * 64), 0,      \
+                     stream, (const bf16_t*)a.q, a.q_stride, (const bf16_t*)a.kc, (const bf16_t*)a.vc, a.bt,        \
+                     a.bt_stride, a.q_seq, a.q_ctx, fb_tok0, fb_ntok, NBF, (bf16_t*)a.out, (int64_t)a.nh * a.D,     \
+                     a.workspace, attn_ws_ml(a), a.nkv, a.nh, page_log2, a.PS, a.NP, attn_scale_log2(a), pair,      \
+                     (const uint8_t*)a.ks, (const uint8_t*)a.vs, a.window)
+#define MP_FA_F8(HB_, NW_, WIN_) \
+  if (f8) MP_FA(HB_, NW_, true, WIN_); else MP_FA(HB_, NW_, false, WIN_)
+#define MP_FA_NW(HB_, WIN_) \
+  if (nw == 8) { MP_FA_F8(HB_, 8, WIN_); } else { MP_FA_F8(HB_, 4, WIN_); }
+#define MP_FA_WIN(HB_) \
+  if (win) { MP_FA_NW(HB_, true); } else { MP_FA_NW(HB_, false); }
   switch (hb) {
-    case 1: MP_FA_NW(1); break;
-    case 2: MP_FA_NW(2); break;
-    case 4: MP_FA_NW(4); break;
-    case 8: MP_FA_NW(8); break;
+    case 1: MP_FA_WIN(1); break;
+    case 2: MP_FA_WIN(2); break;
+    case 4: MP_FA_WIN(4); break;
+    case 8: MP_FA_WIN(8); break;
     default: return -3;
   }
+#undef MP_FA_WIN
 #undef MP_FA_NW
+#undef MP_FA_F8
 #undef MP_FA
   if (a.NP > 1)
     hipLaunchKernelGGL(paged_attn_reduce_kernel, dim3(a.T * a.nh), dim3(a.D), 0, stream, a.workspace, attn_ws_ml(a),
                        (bf16_t*)a.out, a.NP, a.D, a.nh, 0);
   return (int)hipGetLastError();
+}
+
+extern "C" int mp_attention_fa(const mp::AttnArgs* args, const int32_t* fb_tok0, const int32_t* fb_ntok, int NBF,
+                               int nw, int pair, hipStream_t stream) {
+  (void)hipGetLastError();  // an earlier non-mpamd HIP call's stale error is not this launch's
+  if (args->window != 0) return -11;  // the windowed form is mp_attention_fa_window
+  return fa_launch(*args, fb_tok0, fb_ntok, NBF, nw, pair, false, stream);
+}
+
+// The sliding-window form (the kernel's WIN form): a.window = W > 0.  a.PS x a.NP must cover the span a
+// block streams, at most W + (tokens per block) + 62 (ops.attention_fa_window checks it).
+extern "C" int mp_attention_fa_window(const mp::AttnArgs* args, const int32_t* fb_tok0, const int32_t* fb_ntok,
+                                      int NBF, int nw, int pair, hipStream_t stream) {
+  (void)hipGetLastError();
+  if (args->window <= 0) return -11;
+  return fa_launch(*args, fb_tok0, fb_ntok, NBF, nw, pair, true, stream);
 }

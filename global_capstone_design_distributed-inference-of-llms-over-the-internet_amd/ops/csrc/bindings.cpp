@@ -448,12 +448,21 @@ void attention_mfma(const at::Tensor& q, const at::Tensor& k_cache, const at::Te
               qblocks, superblocks, window);
 }
 
-// The FA2 prefill launch (attention_fa.hip), on a bf16 or an fp8 (a.ks) cache.
-void launch_fa(mp::AttnArgs a, const at::Tensor& fablocks, int64_t waves, int64_t pair, int64_t window) {
-  attn_window(a, window, false, "attention_fa");
+// The FA2 prefill launch (attention_fa.hip), on a bf16 or an fp8 (a.ks) cache.  windowed: the
+// sliding-window form (attention_fa_window / attention_fa_window_f8), which needs a window > 0; the
+// plain ops keep refusing one.
+void launch_fa(mp::AttnArgs a, const at::Tensor& fablocks, int64_t waves, int64_t pair, int64_t window,
+               bool windowed = false) {
+  attn_window(a, window, windowed, "attention_fa");
+  MP_CHECK(!windowed || window > 0, "attention_fa_window: window must be > 0");
   const auto [fb, NB] =
       check_blocks(fablocks, true, INT64_MAX, "fablocks int32 [2, NB] (first token, token count), ops.fa_blocks");
   MP_CHECK(waves == 4 || waves == 8, "waves 4 or 8");
+  if (windowed) {
+    check_launch(mp_attention_fa_window(&a, fb, fb + NB, NB, (int)waves, (int)pair, cur_stream()),
+                 a.ks != nullptr ? "attention_fa_window_f8" : "attention_fa_window");
+    return;
+  }
   check_launch(mp_attention_fa(&a, fb, fb + NB, NB, (int)waves, (int)pair, cur_stream()),
                a.ks != nullptr ? "attention_fa_f8" : "attention_fa");
 }
@@ -483,6 +492,32 @@ void attention_fa_f8(const at::Tensor& q, const at::Tensor& k_cache, const at::T
   launch_fa(attn_args(q, k_cache, v_cache, block_tables, q_seq, q_ctx, out, workspace, nh, nkv, scale, part_size,
                       num_parts, 0, &k_scale, &v_scale),
             fablocks, waves, pair, window);
+}
+
+// The sliding-window forms of the two above (attention_fa.hip WIN form): window W > 0, a query of
+// context ctx sees [max(0, ctx - W), ctx); part_size x num_parts covers the span a block streams.
+void attention_fa_window(const at::Tensor& q, const at::Tensor& k_cache, const at::Tensor& v_cache,
+                         const at::Tensor& block_tables, const at::Tensor& q_seq, const at::Tensor& q_ctx,
+                         const at::Tensor& fablocks, at::Tensor& out, at::Tensor& workspace, int64_t nh, int64_t nkv,
+                         double scale, int64_t part_size, int64_t num_parts, int64_t waves, int64_t pair,
+                         int64_t window) {
+  check_kv_bf16(k_cache, v_cache);
+  MP_CHECK(k_cache.size(3) == 128, "attention_fa_window: head_dim 128");
+  launch_fa(attn_args(q, k_cache, v_cache, block_tables, q_seq, q_ctx, out, workspace, nh, nkv, scale, part_size,
+                      num_parts, 0),
+            fablocks, waves, pair, window, true);
+}
+
+void attention_fa_window_f8(const at::Tensor& q, const at::Tensor& k_cache, const at::Tensor& v_cache,
+                            const at::Tensor& k_scale, const at::Tensor& v_scale, const at::Tensor& block_tables,
+                            const at::Tensor& q_seq, const at::Tensor& q_ctx, const at::Tensor& fablocks,
+                            at::Tensor& out, at::Tensor& workspace, int64_t nh, int64_t nkv, double scale,
+                            int64_t part_size, int64_t num_parts, int64_t waves, int64_t pair, int64_t window) {
+  check_kv_f8(k_cache, v_cache, k_scale, v_scale, nkv);
+  MP_CHECK(k_cache.size(3) == 128, "attention_fa_window_f8: head_dim 128");
+  launch_fa(attn_args(q, k_cache, v_cache, block_tables, q_seq, q_ctx, out, workspace, nh, nkv, scale, part_size,
+                      num_parts, 0, &k_scale, &v_scale),
+            fablocks, waves, pair, window, true);
 }
 
 // GQA decode with RoPE + KV write fused (attention_mfma.hip ROPE path): one token per query block,
@@ -940,6 +975,14 @@ TORCH_LIBRARY(mpamd, m) {
       "Tensor q_seq, Tensor q_ctx, Tensor fablocks, Tensor(a!) out, Tensor(b!) workspace, int nh, int nkv, "
       "float scale, int part_size, int num_parts, int waves, int pair=0, int window=0) -> ()");
   m.def(
+      "attention_fa_window(Tensor q, Tensor k_cache, Tensor v_cache, Tensor block_tables, Tensor q_seq, Tensor q_ctx, "
+      "Tensor fablocks, Tensor(a!) out, Tensor(b!) workspace, int nh, int nkv, float scale, int part_size, "
+      "int num_parts, int waves, int pair, int window) -> ()");
+  m.def(
+      "attention_fa_window_f8(Tensor q, Tensor k_cache, Tensor v_cache, Tensor k_scale, Tensor v_scale, "
+      "Tensor block_tables, Tensor q_seq, Tensor q_ctx, Tensor fablocks, Tensor(a!) out, Tensor(b!) workspace, int nh, "
+      "int nkv, float scale, int part_size, int num_parts, int waves, int pair, int window) -> ()");
+  m.def(
       "attention_mfma_rope(Tensor qkv, Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor block_tables, Tensor q_seq, "
       "Tensor q_ctx, Tensor qblocks, Tensor positions, Tensor cos, Tensor sin, Tensor slots, Tensor(c!) out, "
       "Tensor(d!) workspace, int nh, int nkv, float scale, int part_size, int num_parts, int packed, "
@@ -1002,6 +1045,8 @@ TORCH_LIBRARY_IMPL(mpamd, CUDA, m) {
   m.impl("attention_mfma", &attention_mfma);
   m.impl("attention_fa", &attention_fa);
   m.impl("attention_fa_f8", &attention_fa_f8);
+  m.impl("attention_fa_window", &attention_fa_window);
+  m.impl("attention_fa_window_f8", &attention_fa_window_f8);
   m.impl("attention_mfma_rope", &attention_mfma_rope);
   m.impl("attention_mfma_f8", &attention_mfma_f8);
   m.impl("attention_mfma_rope_f8", &attention_mfma_rope_f8);

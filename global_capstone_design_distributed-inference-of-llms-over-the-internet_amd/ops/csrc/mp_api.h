@@ -47,7 +47,7 @@ struct AttnArgs {
   const int64_t* slots;            //   [T] cache slot of the new token (< 0: nothing written)
   QkvPart qp;                      // qp.part == nullptr: absent
   int window;                      // sliding window W: a query of context ctx sees cache positions
-                                   //   [max(0, ctx - W), ctx); 0: no window (decode kernels only)
+                                   //   [max(0, ctx - W), ctx); 0: no window (decode kernels, mp_attention_fa_window)
 };
 
 // log2 of the page size, or -1 when it is no power of two
@@ -99,6 +99,8 @@ int mp_attention_mfma(const mp::AttnArgs* a, const int32_t* qb_tok0, const int32
                       hipStream_t stream);
 int mp_attention_fa(const mp::AttnArgs* a, const int32_t* fb_tok0, const int32_t* fb_ntok, int NBF, int nw, int pair,
                     hipStream_t stream);
+int mp_attention_fa_window(const mp::AttnArgs* a, const int32_t* fb_tok0, const int32_t* fb_ntok, int NBF, int nw,
+                           int pair, hipStream_t stream);  // a->window > 0: the kernel's sliding-window form
 // elementwise.hip
 int mp_embedding(const int64_t* ids, const void* table, void* out, int T, int H, int64_t vocab, hipStream_t stream);
 int mp_swiglu(const void* gu, void* out, int64_t T, int F, hipStream_t stream);

@@ -147,7 +147,7 @@ class StageExecutor:
         and FA2 prefill kernels (``_attend``).  ``sliding_window`` (configs with ``sliding_window``
         W, e.g. Mistral): "cap" limits sessions to W tokens, inside which full causal attention is
         the windowed one; "attend" lets them grow to ``max_seq_len``: every query attends to its last
-        W keys only (``window`` of the decode kernels) and the session's KV pages roll
+        W keys only (``window`` of the decode and FA2 prefill kernels) and the session's KV pages roll
         (runtime/session.py).  GPT-2 and configs without a window ignore it."""
         cfg.validate()
         if sliding_window not in SLIDING_WINDOW_MODES:
@@ -254,6 +254,9 @@ class StageExecutor:
         # ... and on an fp8 KV cache the kernel's fp8 form; MPAMD_KV_FP8_FA=0 keeps those steps on the
         # flash-decoding kernel (per-query causal rows)
         self.prefill_fa_f8 = self._attn_fa and self._kv_fp8 and os.environ.get("MPAMD_KV_FP8_FA", "1") != "0"
+        # sliding window ("attend"): row-major prefill steps past the window on the FA2 kernel's windowed
+        # form (bf16 and fp8 caches); MPAMD_WINDOW_FA=0 puts them back on the flash-decoding rows
+        self.window_fa = bool(self.window) and self._attn_fa and os.environ.get("MPAMD_WINDOW_FA", "1") != "0"
         self._cur_fb = None
         self._cur_fw = 4
         self._n_cu = torch.cuda.get_device_properties(self.device).multi_processor_count \
@@ -556,13 +559,21 @@ class StageExecutor:
         else the flash-decoding kernel.  An fp8 KV cache has the fp8 forms of the MFMA GQA decode
         kernel, of the FA2 prefill kernel (row-major output) and of the flash-decoding kernel; its
         other prefill blocks (packed output, shapes outside ``fa_ok``) run on the latter as
-        per-query causal rows (``qblocks`` is ignored)."""
+        per-query causal rows (``qblocks`` is ignored).  Under a sliding window a prefill step with a
+        row past the window runs the FA2 kernel's windowed form where FA2 covers it, else those rows."""
         table = self.sessions.table_dev
-        # sliding window: the decode kernels take it; the prefill kernels (FA2, grouped MFMA) have no
-        # windowed form, so a prefill step keeps them only while no row is past the window (the same
-        # computation) and otherwise runs the flash-decoding kernel as per-query causal rows
+        # sliding window: the decode kernels take it, and so does the FA2 prefill kernel's windowed form
+        # (row-major steps it covers: window_fa).  The grouped MFMA kernel has none: a prefill step keeps
+        # the unwindowed kernels only while no row is past the window (the same computation) and
+        # otherwise runs the windowed FA2 form, or the flash-decoding kernel as per-query causal rows
         win = self.window
         if win and qblocks is not None and max_ctx > win:
+            fb = getattr(self, "_cur_fb", None)
+            if self.window_fa and fb is not None and not packed and \
+                    (self.prefill_fa_f8 if self._kv_fp8 else self._attn_fa):
+                op = ops.attention_fa_window_f8 if self._kv_fp8 else ops.attention_fa_window
+                return op(qkv, kc, vc, table, q_seq, q_ctx, fb, self.nh, self.nkv, self.scale, win, out=out,
+                          workspace=ws, max_ctx=max_ctx, waves=getattr(self, "_cur_fw", 4))
             return ops.paged_attention(qkv, kc, vc, table, q_seq, q_ctx, self.nh, self.nkv, self.scale, out=out,
                                        workspace=ws, part_size=ps, num_parts=np_, packed=packed,
                                        window=win, max_ctx=max_ctx)
