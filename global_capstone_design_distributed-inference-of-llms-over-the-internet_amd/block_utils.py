@@ -54,6 +54,15 @@ def get_block_size(cfg: ModelConfig, location: str = "memory", dtype=torch.bfloa
     H = cfg.hidden_size
     norms = 2 * H * elt
     matrices = cfg.layer_param_bytes(1.0) - 2 * H  # parameter count of the projection matrices
+    if cfg.is_moe:
+        if quant_type not in _CHANNEL_SCALES:
+            raise ValueError(f"quant_type={quant_type} is not supported for MoE (Mixtral) models")
+        # fp8 experts: every projection at 1 B, the router (E x H) stays 16-bit, one fp32 scale per
+        # output channel of qkv, o and each expert's gate_up / down (StageWeights.quantize_fp8)
+        E = cfg.num_local_experts
+        router = E * H
+        scales = (cfg.q_dim + 2 * cfg.kv_dim + H + E * (2 * cfg.intermediate_size + H)) * 4
+        return int((matrices - router) * q + router * elt + norms + scales)
     scales = (cfg.q_dim + 2 * cfg.kv_dim + H + 2 * cfg.intermediate_size + H) * 4  # per-channel fp32
     return int(matrices * q + norms + (scales if quant_type in _CHANNEL_SCALES else 0))
 

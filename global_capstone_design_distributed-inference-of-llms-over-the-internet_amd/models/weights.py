@@ -110,20 +110,28 @@ class LlamaLayer:
     def w4(self) -> bool:
         return self.qkv_w4 is not None
 
-    def dense(self, name: str, dtype=torch.bfloat16) -> torch.Tensor:
+    def dense(self, name: str, dtype=torch.bfloat16, expert: Optional[int] = None) -> torch.Tensor:
         """Row-major weight ``name`` (dequantized on the fly when only an fp8 or MXFP4 copy is
         kept; a W8A16 / W4A16 layer's qkv / gate_up then carry the folded norm weights, see
-        ``folded``)."""
+        ``folded``).  ``expert`` (MoE gate_up / down): that expert's matrix alone - the prefill
+        path dequantizes one expert at a time; without it a stacked fp8 weight is dequantized
+        whole ([E, N, K]: tests and oracles only)."""
         from .. import ops
 
         if getattr(self, name + "_w4") is not None:  # (also when a 16-bit copy was kept: it is unfolded)
             return ops.unpack_weight_w4(getattr(self, name + "_w4"), getattr(self, name + "_s4"), dtype)
         w = getattr(self, name)
         if w is not None:
-            return w
+            return w if expert is None else w[expert]
         if getattr(self, name + "_w8") is not None:
-            return ops.unpack_weight_w8(getattr(self, name + "_w8"), getattr(self, name + "_ws"), dtype)
-        return ops.unpack_weight_fp8(getattr(self, name + "_q"), getattr(self, name + "_s"), dtype)
+            q, sc, unpack = getattr(self, name + "_w8"), getattr(self, name + "_ws"), ops.unpack_weight_w8
+        else:
+            q, sc, unpack = getattr(self, name + "_q"), getattr(self, name + "_s"), ops.unpack_weight_fp8
+        if q.dim() == 4:
+            return unpack(q, sc, dtype)
+        if expert is not None:
+            return unpack(q[expert], sc[expert], dtype)
+        return torch.stack([unpack(q[e], sc[e], dtype) for e in range(q.shape[0])])
 
 
 @dataclasses.dataclass
@@ -183,6 +191,11 @@ class StageWeights:
         from .. import ops
 
         for lay in self.layers:
+            if isinstance(lay, LlamaLayer) and lay.moe and lay.router_p is None and lay.qkv is None and \
+                    lay.router.shape[1] % 32 == 0:
+                # quantized MoE layer (no 16-bit projections to pack): the decode router GEMM only
+                E, H = lay.router.shape
+                lay.router_p = ops.pack_weight(torch.cat([lay.router, lay.router.new_zeros((-E) % 16, H)]))
             if isinstance(lay, LlamaLayer) and lay.qkv_p is None and lay.qkv is not None:
                 if fold_norms and not lay.moe:
                     lay.qkv_p = ops.pack_weight((lay.qkv.float() * lay.input_norm.float()[None, :])
@@ -223,16 +236,24 @@ class StageWeights:
         ``drop_dense`` frees the bf16 copies (the prefill path then dequantizes one layer at a
         time), halving resident weight bytes: Llama-3-70B fits ONE MI355X (~70 GB) with room
         for a large KV cache.  Embeddings, norms and lm_head stay bf16.
+
+        MoE (Mixtral) layers: gate_up [E, 2F, H] / down [E, H, F] are quantized expert by expert
+        and stacked (gate_up_q [E, 2F/16, H/64, 64, 16], gate_up_s [E, 2F], ...); the router stays
+        16-bit.
         """
         from .. import ops
 
-        if self.cfg.is_moe:
-            raise ValueError("fp8 W8A8 weights are not supported for MoE (Mixtral) models")
         for lay in self.layers:
             if not isinstance(lay, LlamaLayer) or lay.fp8:
                 continue
             for name in LlamaLayer.PROJ:
-                q, sc = ops.pack_weight_fp8(getattr(lay, name))
+                w = getattr(lay, name)
+                if w.dim() == 3:  # stacked experts
+                    qs = [ops.pack_weight_fp8(w[e]) for e in range(w.shape[0])]
+                    q, sc = torch.stack([a for a, _ in qs]), torch.stack([b for _, b in qs])
+                    del qs
+                else:
+                    q, sc = ops.pack_weight_fp8(w)
                 setattr(lay, name + "_q", q)
                 setattr(lay, name + "_s", sc)
                 if drop_dense:
@@ -244,23 +265,30 @@ class StageWeights:
         copies.  ``fold_norms``: qkv / gate_up are dequantized, multiplied by the input /
         post-attention RMSNorm weight along K and re-quantized (W' = W diag(g), per-output-channel
         scales), as the bf16 fused-norm path folds them into its packed weights; ``folded`` is set
-        and every path over these weights normalises with a unit RMSNorm weight."""
+        and every path over these weights normalises with a unit RMSNorm weight.
+
+        MoE layers are converted WITHOUT folding (``folded`` stays False, no second quantization):
+        they run the norm kernels with their real weights, and the expert stacks become
+        gate_up_w8 [E, 2F/16, H/32, 64, 8] + gate_up_ws [E, 2F] (ops.w8_from_fp8 per expert)."""
         from .. import ops
 
         for lay in self.layers:
             if not isinstance(lay, LlamaLayer) or lay.w8 or lay.qkv_q is None:
                 continue
+            fold = bool(fold_norms) and not lay.moe
             for name, g in (("qkv", lay.input_norm), ("o", None), ("gate_up", lay.post_norm), ("down", None)):
                 q, sc = getattr(lay, name + "_q"), getattr(lay, name + "_s")
-                if fold_norms and g is not None:
+                if fold and g is not None:
                     w = ops.unpack_weight_fp8(q, sc, torch.float32) * g.float()[None, :]
                     q, sc = ops.pack_weight_fp8(w)
                     del w
-                setattr(lay, name + "_w8", ops.w8_from_fp8(q))
+                w8 = ops.w8_from_fp8(q) if q.dim() == 4 else torch.stack([ops.w8_from_fp8(q[e])
+                                                                          for e in range(q.shape[0])])
+                setattr(lay, name + "_w8", w8)
                 setattr(lay, name + "_ws", sc)
                 setattr(lay, name + "_q", None)
                 setattr(lay, name + "_s", None)
-            lay.folded = bool(fold_norms)
+            lay.folded = fold
 
     def quantize_mxfp4(self, drop_dense: bool = True) -> None:
         """OCP MXFP4 weights (4.25 bits per weight) for every projection: the W4A16 decode path.
@@ -503,8 +531,10 @@ def load_stage_weights(cfg: ModelConfig, path: str, start: int, end: int, *, has
                        device, dtype=torch.bfloat16, quant_type: Optional[str] = None) -> StageWeights:
     """``quant_type`` ("fp8" / "mxfp4"): each block is quantized as soon as it is read."""
     quant = resolve_quant(quant_type)
-    if quant is not None and (cfg.model_type == "gpt2" or cfg.is_moe):
-        raise ValueError(f"quant_type={quant} is built for dense Llama-family models only")
+    if quant is not None and cfg.model_type == "gpt2":
+        raise ValueError(f"quant_type={quant} is built for Llama-family models only")
+    if quant == "mxfp4" and cfg.is_moe:
+        raise ValueError("MXFP4 weights are not supported for MoE (Mixtral) models")
     ck = _Checkpoint(path)
     dev = torch.device(device)
 
@@ -541,6 +571,8 @@ def load_stage_weights(cfg: ModelConfig, path: str, start: int, end: int, *, has
             dn = torch.stack([t(f"{m}experts.{j}.w2.weight") for j in range(E)])
             layers.append(LlamaLayer(t(p + "input_layernorm.weight"), qkv, t(p + "self_attn.o_proj.weight"),
                                      t(p + "post_attention_layernorm.weight"), gu, dn, router=t(m + "gate.weight")))
+            if quant is not None:
+                _quantize_block(cfg, i, layers[-1], quant)
             continue
         gu = interleave_gate_up(t(p + "mlp.gate_proj.weight"), t(p + "mlp.up_proj.weight")).contiguous()
         layers.append(LlamaLayer(t(p + "input_layernorm.weight"), qkv, t(p + "self_attn.o_proj.weight"),

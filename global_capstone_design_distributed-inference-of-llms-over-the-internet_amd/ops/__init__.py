@@ -1587,6 +1587,84 @@ def linear_w8(x, w8, w_scale, a_rows: int, out=None, epilogue: int = 0, residual
 
 
 # ---------------------------------------------------------------------------------------
+# Grouped W8A16 GEMMs of a sparse-MoE MLP (csrc/gemm_moe.hip): every expert of a layer in two
+# launches.  Weights: the W8A16 layout stacked per expert, uint8 [E, N/16, K/32, 64, 8] + fp32 [E, N];
+# ``cnt`` int32 [E]: tokens routed to each expert (0: the expert is skipped on the device - neither
+# its weights nor its activation slab are read); ``wd`` fp32 [M, E]: the dense routing matrix
+# (ops.moe.dense_weights).  Between the two launches the SwiGLU outputs travel as E consecutive
+# packed activations of ``packed_numel(M, F)`` elements.
+_MOE_OK = {}
+
+
+def moe_w8_ok(M: int, E: int, H: int, F: int) -> bool:
+    """Whether both grouped kernels cover the shape (M <= 64 rows; a dry dispatch, as ``w4_gemm_ok``)."""
+    key = (int(M), int(E), int(H), int(F))
+    if key not in _MOE_OK:
+        _MOE_OK[key] = bool(native_available() and torch.ops.mpamd.moe_w8_ok(*key))
+    return _MOE_OK[key]
+
+
+def _moe_dims(w8: torch.Tensor, w_scale: torch.Tensor, cnt: torch.Tensor, M: int):
+    """(E, N, K) of stacked expert weights, with the checks both grouped ops share."""
+    if w8.dim() != 5 or tuple(w8.shape[3:]) != (64, 8) or w8.dtype != torch.uint8:
+        raise ValueError("w8 must be stacked fp8 expert weights uint8 [E, N/16, K/32, 64, 8]")
+    E, N, K = w8.shape[0], 16 * w8.shape[1], 32 * w8.shape[2]
+    if tuple(w_scale.shape) != (E, N) or w_scale.dtype != torch.float32:
+        raise ValueError(f"w_scale must be fp32 [E, N] = [{E}, {N}]")
+    if cnt.numel() != E or cnt.dtype != torch.int32:
+        raise ValueError(f"cnt must be int32 [{E}] routed-token counts")
+    if not 0 <= M <= 64:
+        raise ValueError(f"the grouped MoE GEMMs take 0..64 rows, got {M}")
+    return E, N, K
+
+
+def moe_gate_up_w8(x, w8, w_scale, cnt, a_rows: int, out=None):
+    """act[e] = SwiGLU(x @ gate_up[e]^T) for every routed expert, one launch: ``x`` packed bf16
+    (``a_rows`` rows), output E packed slabs (an unrouted expert's slab is left untouched).  A routed
+    slab holds the bits of ``linear_w8(x, w8[e], w_scale[e], a_rows, epilogue=1, out_packed=True)`` on
+    the ring form."""
+    M = int(a_rows)
+    E, N, K = _moe_dims(w8, w_scale, cnt, M)
+    F_ = N // 2
+    slab = packed_numel(M, F_)
+    if out is None:
+        out = torch.zeros(E * slab, dtype=x.dtype, device=x.device)
+    if not _native(x):
+        xr = ref.unpack_act(x, M, K)
+        for e, c in enumerate(cnt.tolist()):
+            if c <= 0:
+                continue
+            y = (xr.float() @ unpack_weight_w8(w8[e], w_scale[e], torch.float32).t()).to(x.dtype)
+            ref.pack_act(ref.swiglu(y), out=out[e * slab:(e + 1) * slab])  # SwiGLU output rounded to bf16
+        return out
+    torch.ops.mpamd.moe_gate_up_w8(x, w8, w_scale, cnt, out, M)
+    return out
+
+
+def moe_down_w8(act, w8, w_scale, cnt, wd, a_rows: int, out=None):
+    """y [M, H] = bf16(sum over routed experts e of wd[:, e] * (act[e] @ down[e]^T)), one launch:
+    channel scales and routing weights applied in fp32, ONE bf16 rounding of the combined sum."""
+    M = int(a_rows)
+    E, N, K = _moe_dims(w8, w_scale, cnt, M)
+    if tuple(wd.shape) != (M, E) or wd.dtype != torch.float32:
+        raise ValueError(f"wd must be the fp32 [{M}, {E}] dense routing matrix")
+    if out is None:
+        out = torch.empty(M, N, dtype=act.dtype, device=act.device)
+    if not _native(act):
+        slab = packed_numel(M, K)
+        tot = torch.zeros(M, N, dtype=torch.float32)
+        for e, c in enumerate(cnt.tolist()):
+            if c <= 0:
+                continue
+            a = ref.unpack_act(act[e * slab:(e + 1) * slab], M, K)
+            tot += wd[:, e:e + 1] * (a.float() @ unpack_weight_w8(w8[e], w_scale[e], torch.float32).t())
+        out.copy_(tot.to(out.dtype))
+        return out
+    torch.ops.mpamd.moe_down_w8(act, w8, w_scale, cnt, wd, out, M)
+    return out
+
+
+# ---------------------------------------------------------------------------------------
 # W4A16 decode GEMM (csrc/gemm_w4.hip mp_gemm_w4): OCP MXFP4 weights - e2m1 codes, one e8m0 scale
 # per 32 weights along K, 4.25 bits per weight - dequantized in registers into the bf16 MFMA
 # (v_cvt_scalef32_pk_bf16_fp4), bf16 activations.  Weight layout, in the bf16 fragment order:

@@ -745,6 +745,75 @@ void gemm_w8(const at::Tensor& x, const at::Tensor& wq, const at::Tensor& wsc, a
   check_launch(rc, "gemm_w8");
 }
 
+// Stacked fp8 expert weights of the grouped MoE GEMMs (gemm_moe.hip): uint8 [E, N/16, K/32, 64, 8] +
+// per-expert column scales fp32 [E, N] -> (E, N, K)
+static std::tuple<int, int, int> check_moe_weight(const at::Tensor& w8, const at::Tensor& wsc) {
+  MP_CHECK(w8.is_cuda() && w8.scalar_type() == at::kByte && w8.dim() == 5 && w8.size(3) == 64 && w8.size(4) == 8 &&
+               w8.is_contiguous(),
+           "w8 must be stacked fp8 expert weights uint8 [E, N/16, K/32, 64, 8] (ops.w8_from_fp8 per expert)");
+  const int E = w8.size(0), N = 16 * w8.size(1), K = 32 * w8.size(2);
+  MP_CHECK(wsc.is_cuda() && wsc.scalar_type() == at::kFloat && wsc.is_contiguous() && wsc.dim() == 2 &&
+               wsc.size(0) == E && wsc.size(1) == N && wsc.device() == w8.device(),
+           "wsc: fp32 [E, N] column scales");
+  return {E, N, K};
+}
+
+// routed-token counts of the grouped MoE GEMMs
+static void check_moe_cnt(const at::Tensor& cnt, int E, const at::Tensor& like) {
+  MP_CHECK(cnt.is_cuda() && cnt.scalar_type() == at::kInt && cnt.is_contiguous() && cnt.numel() == E &&
+               cnt.device() == like.device(),
+           "cnt: int32 [E] routed-token counts on the weights' device");
+}
+
+// the E packed SwiGLU activations between the two grouped launches
+static void check_moe_act(const at::Tensor& act, int M, int E, int F, const at::Tensor& like) {
+  check_bf16_cuda(act, "act");
+  MP_CHECK(act.is_contiguous() && act.numel() >= E * packed_numel(M, F) && act.device() == like.device() &&
+               reinterpret_cast<uintptr_t>(act.data_ptr()) % 16 == 0,
+           "act: E packed activations of packed_numel(M, F) bf16 elements each");
+}
+
+// Grouped gate/up + SwiGLU of all experts (gemm_moe.hip mp_moe_gate_up_w8): packed bf16 x (M rows)
+void moe_gate_up_w8(const at::Tensor& x, const at::Tensor& w8, const at::Tensor& wsc, const at::Tensor& cnt,
+                    at::Tensor& act, int64_t M_) {
+  check_bf16_cuda(x, "x");
+  const auto [E, N, K] = check_moe_weight(w8, wsc);
+  const int M = (int)M_;
+  MP_CHECK(M >= 0 && M <= 64, "moe_gate_up_w8: 0 <= M <= 64");
+  MP_CHECK(N % 32 == 0, "moe_gate_up_w8: SwiGLU needs N % 32 == 0");
+  MP_CHECK(x.is_contiguous() && x.numel() >= packed_numel(M, K) && x.device() == w8.device(), "packed x too small");
+  check_moe_cnt(cnt, E, w8);
+  check_moe_act(act, M, E, N / 2, w8);
+  const int rc = mp_moe_gate_up_w8(x.data_ptr(), w8.data_ptr(), wsc.data_ptr<float>(), cnt.data_ptr<int32_t>(),
+                                   act.data_ptr(), M, E, K, N / 2, cur_stream());
+  TORCH_CHECK(rc != 1, "mpamd: moe_gate_up_w8: no grouped kernel covers M=", M, " E=", E, " H=", K, " F=", N / 2);
+  check_launch(rc, "moe_gate_up_w8");
+}
+
+// Grouped down + combine (gemm_moe.hip mp_moe_down_w8): y bf16 [M, H] = sum_e wd[:, e] * (act[e] . down[e]^T)
+void moe_down_w8(const at::Tensor& act, const at::Tensor& w8, const at::Tensor& wsc, const at::Tensor& cnt,
+                 const at::Tensor& wd, at::Tensor& y, int64_t M_) {
+  const auto [E, N, K] = check_moe_weight(w8, wsc);
+  const int M = (int)M_;
+  MP_CHECK(M >= 0 && M <= 64, "moe_down_w8: 0 <= M <= 64");
+  check_moe_cnt(cnt, E, w8);
+  check_moe_act(act, M, E, K, w8);
+  MP_CHECK(wd.is_cuda() && wd.scalar_type() == at::kFloat && wd.is_contiguous() && wd.dim() == 2 && wd.size(0) == M &&
+               wd.size(1) == E && wd.device() == w8.device(),
+           "wd: fp32 [M, E] dense routing weights");
+  check_bf16_cuda(y, "y");
+  check_rows(y, "y");
+  MP_CHECK(y.size(0) == M && y.size(1) == N && y.device() == w8.device(), "y shape");
+  const int rc = mp_moe_down_w8(act.data_ptr(), w8.data_ptr(), wsc.data_ptr<float>(), cnt.data_ptr<int32_t>(),
+                                wd.data_ptr<float>(), y.data_ptr(), y.stride(0), M, E, N, K, cur_stream());
+  TORCH_CHECK(rc != 1, "mpamd: moe_down_w8: no grouped kernel covers M=", M, " E=", E, " H=", N, " F=", K);
+  check_launch(rc, "moe_down_w8");
+}
+
+bool moe_w8_ok(int64_t M, int64_t E, int64_t H, int64_t F) {
+  return mp_moe_w8_ok((int)M, (int)E, (int)H, (int)F) != 0;
+}
+
 // MXFP4 weight operands (gemm_w4.hip): codes uint8 [N/16, K/128, 64, 16] + e8m0 scales uint8 [N/16, K/128, 16, 4]
 static void check_w4(const at::Tensor& w4, const at::Tensor& s4) {
   MP_CHECK(w4.is_cuda() && w4.scalar_type() == at::kByte && w4.dim() == 4 && w4.size(2) == 64 && w4.size(3) == 16 &&
@@ -1019,6 +1088,9 @@ TORCH_LIBRARY(mpamd, m) {
       "float eps=0.) -> ()");
   m.def("gemm_w4_ok(int M, int N, int K, int epilogue) -> bool", &gemm_w4_ok);
   m.def("dequant_w4(Tensor w4, Tensor s4) -> Tensor");
+  m.def("moe_gate_up_w8(Tensor x, Tensor w8, Tensor wsc, Tensor cnt, Tensor(a!) act, int M) -> ()");
+  m.def("moe_down_w8(Tensor act, Tensor w8, Tensor wsc, Tensor cnt, Tensor wd, Tensor(a!) y, int M) -> ()");
+  m.def("moe_w8_ok(int M, int E, int H, int F) -> bool", &moe_w8_ok);
   m.def("pack_act(Tensor x, Tensor(a!) ap) -> ()");
   m.def("pack_weight(Tensor w) -> Tensor");
   m.def("quant_act_fp8(Tensor ap, Tensor(a!) a8, Tensor(b!) scale, int M, int K) -> ()");
@@ -1059,6 +1131,8 @@ TORCH_LIBRARY_IMPL(mpamd, CUDA, m) {
   m.impl("gemm_w8", &gemm_w8);
   m.impl("gemm_w4", &gemm_w4);
   m.impl("dequant_w4", &dequant_w4);
+  m.impl("moe_gate_up_w8", &moe_gate_up_w8);
+  m.impl("moe_down_w8", &moe_down_w8);
   m.impl("pack_weight", &pack_weight);
   m.impl("pack_act", &pack_act);
   m.impl("quant_act_fp8", &quant_act_fp8);

@@ -140,6 +140,12 @@ int mp_quant_mx(const void* ap, void* ax, void* as, int M, int K, hipStream_t st
 int mp_gemm_mx(const void* ax, const void* as, const void* wq, const float* wsc, void* y, int64_t y_stride,
                const void* res, int64_t res_stride, int M, int N, int K, int epilogue, int flags, void* ws, void* ap,
                void* ss_out, void* ss_zero, const void* ss_in, float inv_k, float eps, hipStream_t stream);
+// gemm_moe.hip: the grouped W8A16 GEMMs of a sparse-MoE MLP (all experts of a layer in two launches)
+int mp_moe_gate_up_w8(const void* x, const void* w8, const float* wsc, const int32_t* cnt, void* act, int M, int E,
+                      int H, int F, hipStream_t stream);
+int mp_moe_down_w8(const void* act, const void* w8, const float* wsc, const int32_t* cnt, const float* wd, void* y,
+                   int64_t y_stride, int M, int E, int H, int F, hipStream_t stream);
+int mp_moe_w8_ok(int M, int E, int H, int F);
 // fp8.hip
 void mp_fp8_set_kernel(int kind);
 int mp_quant_act_fp8(const void* ap, void* a8, float* scale, float* part, int M, int K, hipStream_t stream);

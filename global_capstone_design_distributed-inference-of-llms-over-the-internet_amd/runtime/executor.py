@@ -286,6 +286,28 @@ class StageExecutor:
         self._mx = bool(self._w8 and fp8_mode == "mx")
         if self._w8:
             weights.prepare_w8a16(fold_norms=True)
+        # fp8 MoE (Mixtral) weights: W8A16 WITHOUT the fused-norm path (norm kernels with the real
+        # weights, the router in bf16).  Steps of <= 64 rows run qkv / o on ops.linear_w8 and all
+        # experts in two grouped launches (ops.moe_gate_up_w8 / moe_down_w8: unrouted experts skipped
+        # on the device); MPAMD_MOE_GROUPED=0 - or a shape the grouped kernels do not cover - runs them
+        # expert by expert through ops.linear_w8 + addcmul_ instead.  Larger steps and prefill take the
+        # expert-grouped schedule and dequantize one expert's projection at a time, so this stage's
+        # graphs stop at 64 rows.  CPU executors dequantize everywhere.
+        self._moe_w8 = False
+        if cfg.is_moe and weights.fp8:
+            if self._tp is not None:
+                raise ValueError("fp8 MoE (Mixtral) weights are not supported under tensor parallelism")
+            if self.device.type == "cuda":
+                if fp8_mode != "w8a16":
+                    raise ValueError(f"MPAMD_FP8_MODE={fp8_mode} is not built for MoE (Mixtral) models: fp8 experts "
+                                     f"run W8A16 only")
+                self._moe_w8 = (all(d % 256 == 0 for d in (cfg.hidden_size, cfg.q_dim, cfg.intermediate_size)) and
+                                (cfg.q_dim + 2 * cfg.kv_dim) % 32 == 0 and ops.gemm_policy() != "hipblaslt")
+                if self._moe_w8:
+                    weights.prepare_w8a16(fold_norms=False)
+                    self._w8 = True  # the W8A16 layout and kernels (never the fused-norm path: _fused stays off)
+                    self.graph_max_batch = min(self.graph_max_batch, 64)
+        self._moe_grouped = os.environ.get("MPAMD_MOE_GROUPED", "1") != "0"
         # MXFP4 weights (StageWeights.quantize_mxfp4: norm weights folded in before the one
         # quantization): <= 64-row decode steps run the fused-norm path on ops.linear_w4, everything
         # else dequantizes one projection at a time (LlamaLayer.dense) and normalises with unit weights
@@ -328,7 +350,9 @@ class StageExecutor:
                     if weights.lm_head_p is not None:
                         shapes.append((16 * weights.lm_head_p.shape[0], H, 0))
                     ops.autotune_gemm(shapes, self.device)
-                    if self._w8 and weights.layers:
+                    if self._moe_w8 and weights.layers:  # qkv / o only: the experts run the grouped kernels
+                        ops.autotune_w8([(cfg.q_dim + 2 * cfg.kv_dim, H, 0), (H, cfg.q_dim, 0)], self.device)
+                    elif self._w8 and weights.layers:
                         ops.autotune_w8([(cfg.q_dim + 2 * cfg.kv_dim, H, 0), (H, cfg.q_dim, 3), (2 * F, H, 1),
                                          (H, F, 3)], self.device)
                     if self._w4:
@@ -336,7 +360,7 @@ class StageExecutor:
                     elif self._fused and weights.layers and self._fuse_rope:
                         # qkv as split-K partials summed in the attention kernel, per row bucket
                         ops.autotune_qkv_fold(cfg.q_dim + 2 * cfg.kv_dim, H, self.device, fp8=bool(self._w8))
-                    elif weights.fp8 and weights.layers:
+                    elif weights.fp8 and weights.layers and not cfg.is_moe:
                         ops.autotune_fp8([(cfg.q_dim + 2 * cfg.kv_dim, H, 0), (H, cfg.q_dim, 0), (2 * F, H, 1),
                                           (H, F, 0)], self.device)
         self._streamer, self._n_stream = None, self.n_layers
@@ -773,6 +797,25 @@ class StageExecutor:
                 gemm(xr, L, "gate_up", out=act, epilogue=1, out_packed=True, ss_in=ss_post, eps=eps)
                 gemm(act, L, "down", out=res, epilogue=3, residual=res, ap_out=xr, ss_out=ss_in, ss_zero=ss_post)
             mlp = None
+        elif prompt is None and self._moe_w8 and 0 < T <= 64:
+            # fp8 MoE decode path: packed activations, norm kernels with the real weights, qkv / o on
+            # the W8A16 GEMM, the experts in two grouped launches (_moe_mlp_w8)
+            pk = ops.packed_numel
+            xn = e("xn_p", (pk(T, H),))
+            attn = e("attn_p", (pk(T, cfg.q_dim),))
+            act = e("moe_act_p", (cfg.num_local_experts * pk(T, cfg.intermediate_size),))
+            for li, L in enumerate(w.layers):
+                if li == 0:
+                    ops.rmsnorm(h, L.input_norm, eps, out=xn, residual=res, mode=2, packed=True)
+                else:
+                    ops.rmsnorm(mlp, L.input_norm, eps, out=xn, residual=res, mode=1, packed=True)
+                ops.linear_w8(xn, L.qkv_w8, L.qkv_ws, T, out=qkv)
+                kc, vc = self.cache.layer(li)
+                self._rope_attend(qkv, positions, slots, kc, vc, q_seq, q_ctx, attn, ws, ps, np_, True, qblocks,
+                                  max_ctx, decode)
+                ops.linear_w8(attn, L.o_w8, L.o_ws, T, out=o)
+                ops.rmsnorm(o, L.post_norm, eps, out=xn, residual=res, mode=1, packed=True)
+                self._moe_mlp_w8(L, xn, T, mlp, act, e)
         elif prompt is None and self._packed_ok(T):
             # decode path: activations feeding a GEMM stay in the packed MFMA-fragment layout
             pk = ops.packed_numel
@@ -826,11 +869,13 @@ class StageExecutor:
                     ops.rmsnorm(h, g_in, eps, out=xn, residual=res, mode=2)
                 else:
                     ops.rmsnorm(mlp, g_in, eps, out=xn, residual=res, mode=1)
-                ops.linear(xn, L.dense("qkv"), out=qkv, wp=qkv_p)
+                # (fp8 MoE layers dequantize into the executor's dtype: an fp32 CPU stage stays fp32)
+                wdt = dt if L.moe else torch.bfloat16
+                ops.linear(xn, L.dense("qkv", wdt), out=qkv, wp=qkv_p)
                 kc, vc = self.cache.layer(li)
                 self._rope_attend(qkv, positions, slots, kc, vc, q_seq, q_ctx, attn, ws, ps, np_, False, qblocks,
                                   max_ctx, decode)
-                ops.linear(attn, L.dense("o"), out=o, wp=L.o_p)
+                ops.linear(attn, L.dense("o", wdt), out=o, wp=L.o_p)
                 self._ar(o)
                 ops.rmsnorm(o, g_post, eps, out=xn, residual=res, mode=1)
                 if L.moe:
@@ -1031,6 +1076,34 @@ class StageExecutor:
             u = self._ones = torch.ones(self.cfg.hidden_size, dtype=self.dtype, device=self.device)
         return u
 
+    def _moe_mlp_w8(self, L, xn, T, mlp, act, e) -> None:
+        """Sparse-MoE MLP of a <= 64-row step over fp8 experts into ``mlp``: the bf16 router, the
+        routing math (ops/moe.py), then two grouped launches for all experts - gate/up + SwiGLU into
+        E packed slabs of ``act``, down + combine (channel scales and routing weights in fp32, one
+        bf16 rounding).  Experts no row is routed to are skipped on the device by ``cnt``: no host
+        sync, the step stays graph-capturable.  MPAMD_MOE_GROUPED=0 (and shapes the grouped kernels
+        do not cover): every expert through ops.linear_w8 + addcmul_, nothing skipped."""
+        cfg = self.cfg
+        E, k, H, F = cfg.num_local_experts, cfg.num_experts_per_tok, cfg.hidden_size, cfg.intermediate_size
+        logits = ops.linear(xn, None, out=e("moe_logits", (T, 16 * L.router_p.shape[0])), wp=L.router_p,
+                            a_rows=T)[:, :E]
+        w, idx = moe.route(logits, k)
+        wd = moe.dense_weights(w, idx, E, out=e("moe_w", (T, E), torch.float32))
+        if self._moe_grouped and ops.moe_w8_ok(T, E, H, F):
+            cnt = (wd > 0).sum(0, dtype=torch.int32)
+            ops.moe_gate_up_w8(xn, L.gate_up_w8, L.gate_up_ws, cnt, T, out=act)
+            ops.moe_down_w8(act, L.down_w8, L.down_ws, cnt, wd, T, out=mlp)
+            return
+        acc = e("moe_acc", (T, H), torch.float32)
+        acc.zero_()
+        y = e("moe_y", (T, H))
+        a1 = act[: ops.packed_numel(T, F)]
+        for j in range(E):
+            ops.linear_w8(xn, L.gate_up_w8[j], L.gate_up_ws[j], T, out=a1, epilogue=1, out_packed=True)
+            ops.linear_w8(a1, L.down_w8[j], L.down_ws[j], T, out=y)
+            acc.addcmul_(y, wd[:, j:j + 1])
+        mlp.copy_(acc)
+
     def _moe_mlp(self, L, xn, T, mlp, act, e, packed: bool) -> None:
         """Mixtral sparse-MoE MLP into ``mlp`` (ops/moe.py has the routing math and the
         decode-vs-prefill strategy).  Decode steps run every expert on the whole batch with a
@@ -1047,6 +1120,11 @@ class StageExecutor:
         acc.zero_()
         gp = (lambda j: L.gate_up_p[j]) if L.gate_up_p is not None else (lambda j: None)  # noqa: E731
         dp = (lambda j: L.down_p[j]) if L.down_p is not None else (lambda j: None)  # noqa: E731
+        # fp8 experts (no 16-bit copy kept): dequantize ONE expert's projection at a time
+        gw = (lambda j: L.gate_up[j]) if L.gate_up is not None else \
+            (lambda j: L.dense("gate_up", self.dtype, expert=j))  # noqa: E731
+        dw = (lambda j: L.down[j]) if L.down is not None else \
+            (lambda j: L.dense("down", self.dtype, expert=j))  # noqa: E731
         capturing = self.device.type == "cuda" and torch.cuda.is_current_stream_capturing()
         if packed or T <= 64 or capturing:
             wd = moe.dense_weights(w, idx, E, out=e("moe_w", (T, E), torch.float32))
@@ -1061,11 +1139,11 @@ class StageExecutor:
             for j in range(E):
                 if packed:
                     g = cnt[j:j + 1] if gated else None
-                    ops.linear(xn, L.gate_up[j], out=act, epilogue=1, wp=gp(j), a_rows=T, out_packed=True, gate=g)
-                    ops.linear(act, L.down[j], out=y, wp=dp(j), a_rows=T, gate=g)
+                    ops.linear(xn, gw(j), out=act, epilogue=1, wp=gp(j), a_rows=T, out_packed=True, gate=g)
+                    ops.linear(act, dw(j), out=y, wp=dp(j), a_rows=T, gate=g)
                 else:
-                    ops.linear(xn, L.gate_up[j], out=act, epilogue=1, wp=gp(j))
-                    ops.linear(act, L.down[j], out=y, wp=dp(j))
+                    ops.linear(xn, gw(j), out=act, epilogue=1, wp=gp(j))
+                    ops.linear(act, dw(j), out=y, wp=dp(j))
                 acc.addcmul_(y, wd[:, j:j + 1])
         else:
             # prefill: group the T*k (token, expert) pairs by expert (one host sync per layer)
@@ -1080,8 +1158,8 @@ class StageExecutor:
                     continue
                 rows = tok[off:off + c]
                 xe = xn.index_select(0, rows)
-                a = ops.linear(xe, L.gate_up[j], epilogue=1, wp=gp(j))
-                ye = ops.linear(a, L.down[j], wp=dp(j))
+                a = ops.linear(xe, gw(j), epilogue=1, wp=gp(j))  # (experts without rows: skipped above,
+                ye = ops.linear(a, dw(j), wp=dp(j))              # before anything is dequantized)
                 acc.index_add_(0, rows, ye.float() * wsel[off:off + c].unsqueeze(1))
                 off += c
         mlp.copy_(acc)
@@ -1144,7 +1222,7 @@ class StageExecutor:
 
     def _fp8_ok(self, M: int) -> bool:
         """fp8 W8A8 decode path: GPU, fp8 weights, fp8 GEMM shape constraints."""
-        if self.device.type != "cuda" or not 0 < M <= 64 or not self.w.fp8 or self._w8:
+        if self.device.type != "cuda" or not 0 < M <= 64 or not self.w.fp8 or self._w8 or self.cfg.is_moe:
             return False
         cfg = self.cfg
         return all(d % 256 == 0 for d in (cfg.hidden_size, cfg.q_dim, cfg.intermediate_size)) and \
