@@ -61,6 +61,8 @@ inline void check_gemm_out(const at::Tensor& y, int64_t M, int64_t N, int64_t ep
   const int64_t ncols = epilogue == 1 ? N / 2 : N;
   if (opk) {
     MP_CHECK(epilogue == 1 && y.is_contiguous() && y.numel() >= packed_numel(M, ncols), "packed y");
+    // 32-column groups, as opt_packed: an odd count of gate/up pairs would store past packed_numel(M, ncols)
+    MP_CHECK(ncols % 32 == 0, "packed y: the packed output needs N / 2 % 32 == 0");
   } else {
     check_rows(y, "y");
     MP_CHECK(y.size(0) == M && y.size(1) == ncols, "y shape");
@@ -81,6 +83,9 @@ inline std::pair<const void*, int64_t> opt_rows(const c10::optional<at::Tensor>&
 inline void* opt_packed(const c10::optional<at::Tensor>& ap, int64_t M, int64_t N) {
   if (!ap.has_value()) return nullptr;
   check_bf16_cuda(*ap, "ap");
+  // the packed layout lives in 32-column groups: with an odd column-tile count the last tile's copy
+  // would land up to half a group past packed_numel(M, N)
+  MP_CHECK(N % 32 == 0, "ap: the packed copy needs N % 32 == 0");
   MP_CHECK(ap->is_contiguous() && ap->numel() >= packed_numel(M, N), "ap: packed [ceil(M/16)*16*N]");
   return ap->data_ptr();
 }
