@@ -144,7 +144,6 @@ _LDS_CFG = {"lds22": (2, 2), "lds24": (2, 4), "lds42": (4, 2)}
 ROT_FLAG = 1024
 
 
-
 def _base(name: str) -> str:
     return name[:-2] if name.endswith("+r") else name
 
@@ -452,7 +451,6 @@ def autotune_gemm(shapes, device, ms=(4, 16, 32, 48, 64), iters: int = 24, round
     return dict(_SK_CHOICE)
 
 
-
 # ---------------------------------------------------------------------------------------
 def packed_numel(M: int, K: int) -> int:
     """Elements of a packed decode activation (rows padded to a multiple of 16)."""
@@ -550,18 +548,23 @@ def _need_kv_f8(k_cache, v_cache, what: str) -> None:
         raise TypeError(f"ops.{what} takes fp8 KV caches (ops.KVF8); bf16 caches run on ops.{what[:-3]}")
 
 
+def _kv_pages(k_cache, v_cache):
+    """(k pages, v pages, scale keyword arguments) of a ``torch.ops.mpamd`` call: an fp8 cache's
+    (``KVF8``) codes with ``k_scale`` / ``v_scale``, bf16 pages as they come."""
+    if isinstance(k_cache, KVF8):
+        return k_cache.codes, v_cache.codes, {"k_scale": k_cache.scales, "v_scale": v_cache.scales}
+    return k_cache, v_cache, {}
+
+
 def rope_kv_write(qkv, positions, cos, sin, k_cache, v_cache, slots, nh, nkv):
     """RoPE of q (in place) and the new tokens' k / v into their page slots; an fp8 cache (``KVF8``)
     gets k (rotated, rounded to bf16) and v quantized per head (``quant_kv_fp8``)."""
-    if _kv_f8(k_cache, v_cache):
-        if not _native(qkv):
-            return ref.rope_kv_write_f8(qkv, positions, cos, sin, k_cache, v_cache, slots, nh, nkv)
-        torch.ops.mpamd.rope_kv_write_f8(qkv, positions, cos, sin, k_cache.codes, v_cache.codes, k_cache.scales,
-                                         v_cache.scales, slots, int(nh), int(nkv))
-        return
+    f8 = _kv_f8(k_cache, v_cache)
     if not _native(qkv):
-        return ref.rope_kv_write(qkv, positions, cos, sin, k_cache, v_cache, slots, nh, nkv)
-    torch.ops.mpamd.rope_kv_write(qkv, positions, cos, sin, k_cache, v_cache, slots, int(nh), int(nkv))
+        return (ref.rope_kv_write_f8 if f8 else ref.rope_kv_write)(qkv, positions, cos, sin, k_cache, v_cache, slots,
+                                                                  nh, nkv)
+    kc, vc, scales = _kv_pages(k_cache, v_cache)
+    torch.ops.mpamd.rope_kv_write(qkv, positions, cos, sin, kc, vc, slots, int(nh), int(nkv), **scales)
 
 
 def kv_write(k, v, k_cache, v_cache, slots):
@@ -660,6 +663,30 @@ def query_superblocks(ntoks, nrep: int, group: int = 8):
     return np.array([first, cnt], dtype=np.int32).reshape(2, -1)
 
 
+def _attn_launch(what: str, q, k_cache, q_ctx, nh, window, pad: int, partition, part_size, num_parts, max_ctx, out,
+                 workspace, packed=False, grow_workspace=True):
+    """What every attention wrapper settles before its launch -> (part_size, num_parts, out, workspace).
+    Without a ``part_size`` the slices are ``partition(span)`` of the tokens a query streams
+    (``_window_span`` with the kernel's ``pad``; ``max_ctx`` is read from ``q_ctx`` when unknown);
+    explicit slices must cover a window's span (``_check_window_parts``, as ``ops.<what>``).
+    ``grow_workspace``: a caller's workspace too small for the parts is replaced; the flash-decoding
+    ops allocate only when given none."""
+    T, D = q.shape[0], k_cache.shape[-1]
+    if part_size is None:
+        if max_ctx is None:
+            max_ctx = int(q_ctx.max().item()) if T else 1
+        part_size, num_parts = partition(_window_span(window, max_ctx, pad))
+    else:
+        _check_window_parts(what, window, max_ctx, part_size, num_parts, pad)
+    if out is None:
+        out = _gemm_out(T, nh * D, packed, q.dtype, q.device)
+    if grow_workspace:
+        workspace = _attn_workspace(workspace, T, nh, D, num_parts, q.device)
+    elif workspace is None:
+        workspace = attention_workspace(T, nh, D, num_parts, q.device)
+    return part_size, num_parts, out, workspace
+
+
 def attention_mfma(q, k_cache, v_cache, block_tables, q_seq, q_ctx, qblocks, nh, nkv, scale, out=None,
                    workspace=None, part_size=None, num_parts=None, max_ctx=None, packed=False, superblocks=None,
                    window=0):
@@ -669,25 +696,8 @@ def attention_mfma(q, k_cache, v_cache, block_tables, q_seq, q_ctx, qblocks, nh,
     selects the grouped prefill kernel (up to 4 blocks of a sequence per workgroup).  ``window``
     (sliding window, ``paged_attention``): decode blocks only - one token per block, no superblocks."""
     _no_kv_f8(k_cache, v_cache, "attention_mfma")
-    if not _native(q):
-        return paged_attention(q, k_cache, v_cache, block_tables, q_seq, q_ctx, nh, nkv, scale, out=out,
-                               packed=packed, window=window)
-    T = q.shape[0]
-    D = k_cache.shape[-1]
-    if part_size is None:
-        if max_ctx is None:
-            max_ctx = int(q_ctx.max().item()) if T else 1
-        nblk = superblocks.shape[1] if superblocks is not None else qblocks.shape[1]
-        part_size, num_parts = _mfma_partition(nblk, nh, nkv, _window_span(window, max_ctx, 31))
-    else:
-        _check_window_parts("attention_mfma", window, max_ctx, part_size, num_parts, 31)
-    if out is None:
-        out = _gemm_out(T, nh * D, packed, q.dtype, q.device)
-    workspace = _attn_workspace(workspace, T, nh, D, num_parts, q.device)
-    torch.ops.mpamd.attention_mfma(q, k_cache, v_cache, block_tables, q_seq, q_ctx, qblocks, out, workspace, nh, nkv,
-                                   float(scale), int(part_size), int(num_parts), int(bool(packed)), superblocks,
-                                   **_window_kw(window))
-    return out
+    return _attention_mfma("attention_mfma", q, k_cache, v_cache, block_tables, q_seq, q_ctx, qblocks, nh, nkv, scale,
+                           out, workspace, part_size, num_parts, max_ctx, packed, window, superblocks=superblocks)
 
 
 def _mfma_partition(nblocks: int, nh: int, nkv: int, max_ctx: int) -> Tuple[int, int]:
@@ -707,23 +717,43 @@ def attention_mfma_f8(q, k_cache, v_cache, block_tables, q_seq, q_ctx, qblocks, 
     heads.  The kernel converts the codes exactly and then does the bf16 kernel's arithmetic, so the
     output equals ``attention_mfma`` on the dequantized cache bit for bit."""
     _need_kv_f8(k_cache, v_cache, "attention_mfma_f8")
+    return _attention_mfma("attention_mfma_f8", q, k_cache, v_cache, block_tables, q_seq, q_ctx, qblocks, nh, nkv,
+                           scale, out, workspace, part_size, num_parts, max_ctx, packed, window)
+
+
+def _attention_mfma(what, q, k_cache, v_cache, block_tables, q_seq, q_ctx, qblocks, nh, nkv, scale, out, workspace,
+                    part_size, num_parts, max_ctx, packed, window, superblocks=None, rope=(), qkv_part=None,
+                    mx_out=None):
+    """The four ``attention_mfma*`` ops, on the cache as it comes.  ``rope`` = (positions, cos, sin,
+    slots): the fused RoPE decode form, where ``q`` is the unrotated qkv projection."""
+    if qkv_part is not None and not _native(q):
+        q = reduce_qkv_part(qkv_part, q.dtype)
+        qkv_part = None
     if not _native(q):
+        if rope:
+            positions, cos, sin, slots = rope
+            q = q.clone()
+            (ref.rope_kv_write_f8 if isinstance(k_cache, KVF8) else ref.rope_kv_write)(
+                q, positions, cos, sin, k_cache, v_cache, slots, nh, nkv)
         return paged_attention(q, k_cache, v_cache, block_tables, q_seq, q_ctx, nh, nkv, scale, out=out,
                                packed=packed, window=window)
-    T = q.shape[0]
-    D = k_cache.shape[-1]
-    if part_size is None:
-        if max_ctx is None:
-            max_ctx = int(q_ctx.max().item()) if T else 1
-        part_size, num_parts = _mfma_partition(qblocks.shape[1], nh, nkv, _window_span(window, max_ctx, 31))
+    if rope:  # one part unless the caller sets the slices
+        partition = lambda span: (128 * math.ceil(max(span, 1) / 128), 1)  # noqa: E731
     else:
-        _check_window_parts("attention_mfma_f8", window, max_ctx, part_size, num_parts, 31)
-    if out is None:
-        out = _gemm_out(T, nh * D, packed, q.dtype, q.device)
-    workspace = _attn_workspace(workspace, T, nh, D, num_parts, q.device)
-    torch.ops.mpamd.attention_mfma_f8(q, k_cache.codes, v_cache.codes, k_cache.scales, v_cache.scales, block_tables,
-                                      q_seq, q_ctx, qblocks, out, workspace, int(nh), int(nkv), float(scale),
-                                      int(part_size), int(num_parts), int(bool(packed)), **_window_kw(window))
+        nblk = superblocks.shape[1] if superblocks is not None else qblocks.shape[1]
+        partition = lambda span: _mfma_partition(nblk, nh, nkv, span)  # noqa: E731
+    part_size, num_parts, out, workspace = _attn_launch(what, q, k_cache, q_ctx, nh, window, 31, partition, part_size,
+                                                        num_parts, max_ctx, out, workspace, packed)
+    kc, vc, scales = _kv_pages(k_cache, v_cache)
+    tail = (out, workspace, int(nh), int(nkv), float(scale), int(part_size), int(num_parts), int(bool(packed)))
+    if rope:
+        torch.ops.mpamd.attention_mfma_rope(q, kc, vc, block_tables, q_seq, q_ctx, qblocks, *rope, *tail,
+                                            *_qkv_part_args(qkv_part),
+                                            *(mx_out if mx_out is not None else (None, None)),
+                                            **_window_kw(window), **scales)
+    else:
+        torch.ops.mpamd.attention_mfma(q, kc, vc, block_tables, q_seq, q_ctx, qblocks, *tail, superblocks,
+                                       **_window_kw(window), **scales)
     return out
 
 
@@ -774,7 +804,8 @@ def attention_fa(q, k_cache, v_cache, block_tables, q_seq, q_ctx, fablocks, nh, 
     """Causal prefill attention, FA2 form on 32x32x16 MFMA with the transposed LDS reads of V
     (csrc/attention_fa.hip).  Same semantics as ``paged_attention``; row-major output only.
     ``fablocks`` from ``fa_blocks`` (device int32 [2, NB]).  The context is split over parts
-    only when the grid would leave CUs idle.  The kernel has no sliding-window form: ``window`` > 0 raises."""
+    only when the grid would leave CUs idle.  This op keeps ``window`` at 0 (``window`` > 0 raises):
+    the kernel's sliding-window form is ``attention_fa_window``."""
     _no_kv_f8(k_cache, v_cache, "attention_fa")
     return _attention_fa(q, k_cache, v_cache, block_tables, q_seq, q_ctx, fablocks, nh, nkv, scale, out, workspace,
                          max_ctx, waves, num_parts, pair, window)
@@ -791,37 +822,6 @@ def attention_fa_f8(q, k_cache, v_cache, block_tables, q_seq, q_ctx, fablocks, n
                          max_ctx, waves, num_parts, pair, window)
 
 
-def _attention_fa(q, k_cache, v_cache, block_tables, q_seq, q_ctx, fablocks, nh, nkv, scale, out, workspace, max_ctx,
-                  waves, num_parts, pair, window=0):
-    """``attention_fa`` / ``attention_fa_f8``: the partition and pairing rules and the launch."""
-    if not _native(q):
-        return paged_attention(q, k_cache, v_cache, block_tables, q_seq, q_ctx, nh, nkv, scale, out=out, window=window)
-    T = q.shape[0]
-    D = k_cache.shape[-1]
-    waves = int(waves or FA_WAVES)
-    if max_ctx is None:
-        max_ctx = int(q_ctx.max().item()) if T else 1
-    if num_parts is None:
-        nblk = fablocks.shape[1] * (nh // (nh // nkv))
-        want = max(1, math.ceil(512 / max(1, nblk)))
-        num_parts = max(1, min(want, math.ceil(max_ctx / 256)))
-    part_size = 64 * math.ceil(math.ceil(max(max_ctx, 1) / num_parts) / 64)
-    num_parts = math.ceil(max(max_ctx, 1) / part_size)
-    if out is None:
-        out = torch.empty(T, nh * D, dtype=q.dtype, device=q.device)
-    workspace = _attn_workspace(workspace, T, nh, D, num_parts, q.device)
-    if pair is None:
-        pair = fa_pair(int(fablocks.shape[1]), nh, nkv, num_parts)
-    tail = (block_tables, q_seq, q_ctx, fablocks, out, workspace, int(nh), int(nkv), float(scale), int(part_size),
-            int(num_parts), waves, int(bool(pair) and num_parts == 1))
-    if isinstance(k_cache, KVF8):
-        torch.ops.mpamd.attention_fa_f8(q, k_cache.codes, v_cache.codes, k_cache.scales, v_cache.scales, *tail,
-                                        **_window_kw(window))
-    else:
-        torch.ops.mpamd.attention_fa(q, k_cache, v_cache, *tail, **_window_kw(window))
-    return out
-
-
 def attention_fa_window(q, k_cache, v_cache, block_tables, q_seq, q_ctx, fablocks, nh, nkv, scale, window, out=None,
                         workspace=None, max_ctx=None, waves=None, num_parts=None, pair=None, part_size=None):
     """``attention_fa`` under a sliding window W = ``window`` > 0 (csrc/attention_fa.hip WIN form): a
@@ -831,8 +831,8 @@ def attention_fa_window(q, k_cache, v_cache, block_tables, q_seq, q_ctx, fablock
     ``num_parts`` sets the slices explicitly and must cover the span.  No block-table entry below the
     page of a block's first visible key is read (rolling pages)."""
     _no_kv_f8(k_cache, v_cache, "attention_fa_window")
-    return _attention_fa_window(q, k_cache, v_cache, block_tables, q_seq, q_ctx, fablocks, nh, nkv, scale, window, out,
-                                workspace, max_ctx, waves, num_parts, pair, part_size)
+    return _attention_fa(q, k_cache, v_cache, block_tables, q_seq, q_ctx, fablocks, nh, nkv, scale, out, workspace,
+                         max_ctx, waves, num_parts, pair, window, windowed=True, part_size=part_size)
 
 
 def attention_fa_window_f8(q, k_cache, v_cache, block_tables, q_seq, q_ctx, fablocks, nh, nkv, scale, window,
@@ -841,8 +841,8 @@ def attention_fa_window_f8(q, k_cache, v_cache, block_tables, q_seq, q_ctx, fabl
     """``attention_fa_window`` on an fp8 KV cache (``KVF8``): only the staging differs, so the output
     equals ``attention_fa_window`` on the dequantized cache bit for bit."""
     _need_kv_f8(k_cache, v_cache, "attention_fa_window_f8")
-    return _attention_fa_window(q, k_cache, v_cache, block_tables, q_seq, q_ctx, fablocks, nh, nkv, scale, window, out,
-                                workspace, max_ctx, waves, num_parts, pair, part_size)
+    return _attention_fa(q, k_cache, v_cache, block_tables, q_seq, q_ctx, fablocks, nh, nkv, scale, out, workspace,
+                         max_ctx, waves, num_parts, pair, window, windowed=True, part_size=part_size)
 
 
 def fa_window_pad(nh: int, nkv: int, waves: int) -> int:
@@ -852,44 +852,50 @@ def fa_window_pad(nh: int, nkv: int, waves: int) -> int:
     return max(1, (32 * int(waves)) // max(1, nh // nkv)) + 62
 
 
-def _attention_fa_window(q, k_cache, v_cache, block_tables, q_seq, q_ctx, fablocks, nh, nkv, scale, window, out,
-                         workspace, max_ctx, waves, num_parts, pair, part_size):
-    """``attention_fa_window`` / ``attention_fa_window_f8``: ``_attention_fa``'s partition rule on the
-    streamed span, its pairing rule, and the launch."""
-    window = int(window)
-    if window <= 0:
-        raise ValueError(f"ops.attention_fa_window: window must be > 0, got {window}")
+def _fa_partition(nblocks: int, nh: int, nkv: int, span: int, num_parts=None) -> Tuple[int, int]:
+    """(part_size, num_parts) of the FA2 ops over ``span`` streamed tokens: parts (the caller's count,
+    else enough for about 512 workgroups, none under 256 tokens) of a multiple of 64 tokens."""
+    span = max(span, 1)
+    if num_parts is None:
+        nblk = nblocks * (nh // (nh // nkv))
+        want = max(1, math.ceil(512 / max(1, nblk)))
+        num_parts = max(1, min(want, math.ceil(span / 256)))
+    part_size = 64 * math.ceil(math.ceil(span / max(1, int(num_parts))) / 64)
+    return part_size, math.ceil(span / part_size)
+
+
+def _attention_fa(q, k_cache, v_cache, block_tables, q_seq, q_ctx, fablocks, nh, nkv, scale, out, workspace, max_ctx,
+                  waves, num_parts, pair, window=0, windowed=False, part_size=None):
+    """The four ``attention_fa*`` ops, on the cache as it comes: the partition rule (``windowed``: on
+    the streamed span, or the caller's ``part_size``; the plain ops always derive theirs), the pairing
+    rule and the launch."""
     waves = int(waves or FA_WAVES)
-    pad = fa_window_pad(nh, nkv, waves)
-    if part_size is not None:
-        if num_parts is None or int(part_size) <= 0 or int(part_size) % 64:
-            raise ValueError("ops.attention_fa_window: part_size is a positive multiple of 64 given with num_parts")
-        _check_window_parts("attention_fa_window", window, max_ctx, part_size, num_parts, pad)
+    pad = 0
+    if windowed:
+        window = int(window)
+        if window <= 0:
+            raise ValueError(f"ops.attention_fa_window: window must be > 0, got {window}")
+        pad = fa_window_pad(nh, nkv, waves)
+        if part_size is not None:  # (refused before the fallback too)
+            if num_parts is None or int(part_size) <= 0 or int(part_size) % 64:
+                raise ValueError("ops.attention_fa_window: part_size is a positive multiple of 64 given with num_parts")
+            _check_window_parts("attention_fa_window", window, max_ctx, part_size, num_parts, pad)
     if not _native(q):
         return paged_attention(q, k_cache, v_cache, block_tables, q_seq, q_ctx, nh, nkv, scale, out=out, window=window)
-    T = q.shape[0]
-    D = k_cache.shape[-1]
-    if part_size is None:
-        if max_ctx is None:
-            max_ctx = int(q_ctx.max().item()) if T else 1
-        span = max(_window_span(window, max_ctx, pad), 1)
-        if num_parts is None:
-            nblk = fablocks.shape[1] * (nh // (nh // nkv))
-            want = max(1, math.ceil(512 / max(1, nblk)))
-            num_parts = max(1, min(want, math.ceil(span / 256)))
-        part_size = 64 * math.ceil(math.ceil(span / max(1, int(num_parts))) / 64)
-        num_parts = math.ceil(span / part_size)
-    if out is None:
-        out = torch.empty(T, nh * D, dtype=q.dtype, device=q.device)
-    workspace = _attn_workspace(workspace, T, nh, D, num_parts, q.device)
+    nblocks = int(fablocks.shape[1])
+    # (a window on the plain ops is the binding's to refuse: their slices split the context)
+    part_size, num_parts, out, workspace = _attn_launch(
+        "attention_fa_window", q, k_cache, q_ctx, nh, window if windowed else 0, pad,
+        lambda span: _fa_partition(nblocks, nh, nkv, span, num_parts), part_size, num_parts, max_ctx, out, workspace)
     if pair is None:
-        pair = fa_pair(int(fablocks.shape[1]), nh, nkv, num_parts)
-    tail = (block_tables, q_seq, q_ctx, fablocks, out, workspace, int(nh), int(nkv), float(scale), int(part_size),
-            int(num_parts), waves, int(bool(pair) and num_parts == 1), window)
-    if isinstance(k_cache, KVF8):
-        torch.ops.mpamd.attention_fa_window_f8(q, k_cache.codes, v_cache.codes, k_cache.scales, v_cache.scales, *tail)
+        pair = fa_pair(nblocks, nh, nkv, num_parts)
+    kc, vc, scales = _kv_pages(k_cache, v_cache)
+    args = (q, kc, vc, block_tables, q_seq, q_ctx, fablocks, out, workspace, int(nh), int(nkv), float(scale),
+            int(part_size), int(num_parts), waves, int(bool(pair) and num_parts == 1))
+    if windowed:
+        torch.ops.mpamd.attention_fa_window(*args, window, **scales)
     else:
-        torch.ops.mpamd.attention_fa_window(q, k_cache, v_cache, *tail)
+        torch.ops.mpamd.attention_fa(*args, **_window_kw(window), **scales)
     return out
 
 
@@ -904,31 +910,9 @@ def attention_mfma_rope(qkv, k_cache, v_cache, block_tables, q_seq, q_ctx, qbloc
     activation (``quant_mx`` layout) there instead of ``out`` - the o projection's input, quantized
     in the attention epilogue."""
     _no_kv_f8(k_cache, v_cache, "attention_mfma_rope")
-    if qkv_part is not None and not _native(qkv):
-        qkv = reduce_qkv_part(qkv_part, qkv.dtype)
-        qkv_part = None
-    if not _native(qkv):
-        q = qkv.clone()
-        ref.rope_kv_write(q, positions, cos, sin, k_cache, v_cache, slots, nh, nkv)
-        return paged_attention(q, k_cache, v_cache, block_tables, q_seq, q_ctx, nh, nkv, scale, out=out,
-                               packed=packed, window=window)
-    T = qkv.shape[0]
-    D = k_cache.shape[-1]
-    if part_size is None:
-        if max_ctx is None:
-            max_ctx = int(q_ctx.max().item()) if T else 1
-        part_size = 128 * math.ceil(max(_window_span(window, max_ctx, 31), 1) / 128)
-        num_parts = 1
-    else:
-        _check_window_parts("attention_mfma_rope", window, max_ctx, part_size, num_parts, 31)
-    if out is None:
-        out = _gemm_out(T, nh * D, packed, qkv.dtype, qkv.device)
-    workspace = _attn_workspace(workspace, T, nh, D, num_parts, qkv.device)
-    torch.ops.mpamd.attention_mfma_rope(qkv, k_cache, v_cache, block_tables, q_seq, q_ctx, qblocks, positions, cos,
-                                        sin, slots, out, workspace, nh, nkv, float(scale), int(part_size),
-                                        int(num_parts), int(bool(packed)), *_qkv_part_args(qkv_part),
-                                        *(mx_out if mx_out is not None else (None, None)), **_window_kw(window))
-    return out
+    return _attention_mfma("attention_mfma_rope", qkv, k_cache, v_cache, block_tables, q_seq, q_ctx, qblocks, nh, nkv,
+                           scale, out, workspace, part_size, num_parts, max_ctx, packed, window,
+                           rope=(positions, cos, sin, slots), qkv_part=qkv_part, mx_out=mx_out)
 
 
 def attention_mfma_rope_f8(qkv, k_cache, v_cache, block_tables, q_seq, q_ctx, qblocks, positions, cos, sin, slots,
@@ -939,32 +923,9 @@ def attention_mfma_rope_f8(qkv, k_cache, v_cache, block_tables, q_seq, q_ctx, qb
     dequantized values - what every later step reads.  GQA groups of 4, 8 or a multiple of 16 heads;
     no MX output."""
     _need_kv_f8(k_cache, v_cache, "attention_mfma_rope_f8")
-    if qkv_part is not None and not _native(qkv):
-        qkv = reduce_qkv_part(qkv_part, qkv.dtype)
-        qkv_part = None
-    if not _native(qkv):
-        q = qkv.clone()
-        ref.rope_kv_write_f8(q, positions, cos, sin, k_cache, v_cache, slots, nh, nkv)
-        return paged_attention(q, k_cache, v_cache, block_tables, q_seq, q_ctx, nh, nkv, scale, out=out,
-                               packed=packed, window=window)
-    T = qkv.shape[0]
-    D = k_cache.shape[-1]
-    if part_size is None:
-        if max_ctx is None:
-            max_ctx = int(q_ctx.max().item()) if T else 1
-        part_size = 128 * math.ceil(max(_window_span(window, max_ctx, 31), 1) / 128)
-        num_parts = 1
-    else:
-        _check_window_parts("attention_mfma_rope_f8", window, max_ctx, part_size, num_parts, 31)
-    if out is None:
-        out = _gemm_out(T, nh * D, packed, qkv.dtype, qkv.device)
-    workspace = _attn_workspace(workspace, T, nh, D, num_parts, qkv.device)
-    torch.ops.mpamd.attention_mfma_rope_f8(qkv, k_cache.codes, v_cache.codes, k_cache.scales, v_cache.scales,
-                                           block_tables, q_seq, q_ctx, qblocks, positions, cos, sin, slots, out,
-                                           workspace, int(nh), int(nkv), float(scale), int(part_size),
-                                           int(num_parts), int(bool(packed)), *_qkv_part_args(qkv_part),
-                                           **_window_kw(window))
-    return out
+    return _attention_mfma("attention_mfma_rope_f8", qkv, k_cache, v_cache, block_tables, q_seq, q_ctx, qblocks, nh,
+                           nkv, scale, out, workspace, part_size, num_parts, max_ctx, packed, window,
+                           rope=(positions, cos, sin, slots), qkv_part=qkv_part)
 
 
 _ATTN_CNT = {}
@@ -1017,27 +978,26 @@ def paged_attention(q, k_cache, v_cache, block_tables, q_seq, q_ctx, nh, nkv, sc
             q, k_cache, v_cache, block_tables, q_seq, q_ctx, nh, nkv, scale, out=None if packed else out,
             window=window)
         return ref.pack_act(y, out=out) if packed else y
+    return _flash_decoding("paged_attention", q, k_cache, v_cache, block_tables, q_seq, q_ctx, nh, nkv, scale, out,
+                           workspace, part_size, num_parts, max_ctx, packed, window)
+
+
+def _flash_decoding(what, q, k_cache, v_cache, block_tables, q_seq, q_ctx, nh, nkv, scale, out, workspace, part_size,
+                    num_parts, max_ctx, packed, window, rope=(), qkv_part=None):
+    """The launch of ``paged_attention`` and, with ``rope`` = (positions, cos, sin, slots) and ``q`` the
+    unrotated qkv projection, of ``paged_attention_rope``, on the cache as it comes."""
     T = q.shape[0]
-    D = k_cache.shape[-1]
-    if part_size is None:
-        if max_ctx is None:
-            max_ctx = int(q_ctx.max().item()) if T else 1
-        part_size, num_parts = attention_partition(T, nkv, _window_span(window, max_ctx))
+    part_size, num_parts, out, workspace = _attn_launch(
+        what, q, k_cache, q_ctx, nh, window, 0, lambda span: attention_partition(T, nkv, span), part_size, num_parts,
+        max_ctx, out, workspace, packed, grow_workspace=False)
+    kc, vc, scales = _kv_pages(k_cache, v_cache)
+    tail = (out, workspace, int(nh), int(nkv), float(scale), int(part_size), int(num_parts), int(bool(packed)),
+            _attn_cnt(q.device))
+    if rope:
+        torch.ops.mpamd.paged_attention_rope(q, kc, vc, block_tables, q_seq, q_ctx, *rope, *tail,
+                                             *_qkv_part_args(qkv_part), **_window_kw(window), **scales)
     else:
-        _check_window_parts("paged_attention", window, max_ctx, part_size, num_parts)
-    if out is None:
-        out = _gemm_out(T, nh * D, packed, q.dtype, q.device)
-    if workspace is None:
-        workspace = attention_workspace(T, nh, D, num_parts, q.device)
-    if f8:
-        torch.ops.mpamd.paged_attention_f8(q, k_cache.codes, v_cache.codes, k_cache.scales, v_cache.scales,
-                                           block_tables, q_seq, q_ctx, out, workspace, int(nh), int(nkv),
-                                           float(scale), int(part_size), int(num_parts), int(bool(packed)),
-                                           _attn_cnt(q.device), **_window_kw(window))
-        return out
-    torch.ops.mpamd.paged_attention(q, k_cache, v_cache, block_tables, q_seq, q_ctx, out, workspace, int(nh), int(nkv),
-                                    float(scale), int(part_size), int(num_parts), int(bool(packed)), _attn_cnt(q.device),
-                                    **_window_kw(window))
+        torch.ops.mpamd.paged_attention(q, kc, vc, block_tables, q_seq, q_ctx, *tail, **_window_kw(window), **scales)
     return out
 
 
@@ -1082,30 +1042,9 @@ def paged_attention_rope(qkv, k_cache, v_cache, block_tables, q_seq, q_ctx, posi
         return paged_attention(q, k_cache, v_cache, block_tables, q_seq, q_ctx, nh, nkv, scale, out=out,
                                workspace=workspace, part_size=part_size, num_parts=num_parts, max_ctx=max_ctx,
                                packed=packed, window=window)
-    T = qkv.shape[0]
-    D = k_cache.shape[-1]
-    if part_size is None:
-        if max_ctx is None:
-            max_ctx = int(q_ctx.max().item()) if T else 1
-        part_size, num_parts = attention_partition(T, nkv, _window_span(window, max_ctx))
-    else:
-        _check_window_parts("paged_attention_rope", window, max_ctx, part_size, num_parts)
-    if out is None:
-        out = _gemm_out(T, nh * D, packed, qkv.dtype, qkv.device)
-    if workspace is None:
-        workspace = attention_workspace(T, nh, D, num_parts, qkv.device)
-    if f8:
-        torch.ops.mpamd.paged_attention_rope_f8(qkv, k_cache.codes, v_cache.codes, k_cache.scales, v_cache.scales,
-                                                block_tables, q_seq, q_ctx, positions, cos, sin, slots, out,
-                                                workspace, int(nh), int(nkv), float(scale), int(part_size),
-                                                int(num_parts), int(bool(packed)), _attn_cnt(qkv.device),
-                                                *_qkv_part_args(qkv_part), **_window_kw(window))
-        return out
-    torch.ops.mpamd.paged_attention_rope(qkv, k_cache, v_cache, block_tables, q_seq, q_ctx, positions, cos, sin,
-                                         slots, out, workspace, int(nh), int(nkv), float(scale), int(part_size),
-                                         int(num_parts), int(bool(packed)), _attn_cnt(qkv.device),
-                                         *_qkv_part_args(qkv_part), **_window_kw(window))
-    return out
+    return _flash_decoding("paged_attention_rope", qkv, k_cache, v_cache, block_tables, q_seq, q_ctx, nh, nkv, scale,
+                           out, workspace, part_size, num_parts, max_ctx, packed, window,
+                           rope=(positions, cos, sin, slots), qkv_part=qkv_part)
 
 
 def embedding(ids, table, out=None):

@@ -31,7 +31,7 @@
 // cache of the dequantized values, and everything after it is shared, so the output equals the bf16
 // form's on that cache bit for bit.
 //
-// WIN (sliding window W, mp_attention_fa_window): row of context ctx sees [lo, ctx), lo = max(0, ctx - W),
+// WIN (sliding window W, mp_attention_fa's windowed form): row of context ctx sees [lo, ctx), lo = max(0, ctx - W),
 // the decode kernels' rule.  A block streams [base, grp_ctx), base = the 64-token step that holds the
 // lo of its first row, and slice p of a split launch is [base + p PS, base + (p + 1) PS): pages below
 // base's are never looked up (rolling pages have released them).  The score mask gains tk >= lo, a wave
@@ -41,7 +41,7 @@
 // that serve padding rows serve it.  WIN is a template parameter: the unwindowed forms compile as before.
 #include <type_traits>
 
-#include "common.h"
+#include "attn_common.h"
 #include "kv_f8.h"
 
 namespace mp {
@@ -353,19 +353,23 @@ __global__ __launch_bounds__(NW * 64) void attn_fa_kernel(
   }  // pass
 }
 
-__global__ void paged_attn_reduce_kernel(const float* __restrict__ part_o, const float* __restrict__ part_ml,
-                                         bf16_t* __restrict__ out, int NP, int D, int nh, int packed_mt);
-
 }  // namespace mp
 
 // Prefill blocks: fb_tok0[i] / fb_ntok[i] = first flat token / token count of block i (<= 32 x NW
 // / heads_per_block consecutive tokens of ONE sequence, ops.fa_blocks).  D = 128, page_size a
 // multiple of 64, heads_per_block = nh / nkv in {1, 2, 4, 8}; row-major output [T, nh * D].
 // a.ks != nullptr: the fp8 cache's code pages and row scales (kv_f8.h), the kernel's F8 form.
-// win: the kernel's WIN form under a.window > 0 (the two C entries below check the window themselves).
-static int fa_launch(const mp::AttnArgs& a, const int32_t* fb_tok0, const int32_t* fb_ntok, int NBF, int nw, int pair,
-                     bool win, hipStream_t stream) {
+// windowed: the sliding-window form (the kernel's WIN form), a.window = W > 0; a.PS x a.NP must cover the
+// span a block streams, at most W + (tokens per block) + 62 (ops.attention_fa_window checks it).  The
+// plain form refuses a window instead of attending to the whole context.
+extern "C" int mp_attention_fa(const mp::AttnArgs* args, const int32_t* fb_tok0, const int32_t* fb_ntok, int NBF,
+                               int nw, int pair, int windowed, hipStream_t stream) {
+  (void)hipGetLastError();  // an earlier non-mpamd HIP call's stale error is not this launch's
   using namespace mp;
+  const AttnArgs& a = *args;
+  const bool win = windowed != 0;
+  if (!win && a.window != 0) return -11;
+  if (win && a.window <= 0) return -11;
   if (NBF == 0 || a.T == 0) return 0;
   if (a.D != 128 || a.nh % a.nkv != 0 || a.PS % 64 != 0 || a.NP < 1 || a.page_size % 64 != 0) return -1;
   const int page_log2 = attn_page_log2(a);
@@ -402,20 +406,4 @@ static int fa_launch(const mp::AttnArgs& a, const int32_t* fb_tok0, const int32_
     hipLaunchKernelGGL(paged_attn_reduce_kernel, dim3(a.T * a.nh), dim3(a.D), 0, stream, a.workspace, attn_ws_ml(a),
                        (bf16_t*)a.out, a.NP, a.D, a.nh, 0);
   return (int)hipGetLastError();
-}
-
-extern "C" int mp_attention_fa(const mp::AttnArgs* args, const int32_t* fb_tok0, const int32_t* fb_ntok, int NBF,
-                               int nw, int pair, hipStream_t stream) {
-  (void)hipGetLastError();  // an earlier non-mpamd HIP call's stale error is not this launch's
-  if (args->window != 0) return -11;  // the windowed form is mp_attention_fa_window
-  return fa_launch(*args, fb_tok0, fb_ntok, NBF, nw, pair, false, stream);
-}
-
-// The sliding-window form (the kernel's WIN form): a.window = W > 0.  a.PS x a.NP must cover the span a
-// block streams, at most W + (tokens per block) + 62 (ops.attention_fa_window checks it).
-extern "C" int mp_attention_fa_window(const mp::AttnArgs* args, const int32_t* fb_tok0, const int32_t* fb_ntok,
-                                      int NBF, int nw, int pair, hipStream_t stream) {
-  (void)hipGetLastError();
-  if (args->window <= 0) return -11;
-  return fa_launch(*args, fb_tok0, fb_ntok, NBF, nw, pair, true, stream);
 }

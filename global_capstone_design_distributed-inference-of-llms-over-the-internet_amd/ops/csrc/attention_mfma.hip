@@ -34,7 +34,7 @@
 // (K/V loads keep the default cache policy here: non-temporal loads, a win for the MHA decode
 // kernel in attention.hip, measured 12-14 % SLOWER on this kernel at 64 / 256 sessions, cold
 // caches - profiles/r3_i/attn_nt.jsonl vs attn_def.jsonl.)
-#include "common.h"
+#include "attn_common.h"
 #include "kv_f8.h"
 #include "mx_common.h"
 #include <type_traits>
@@ -688,14 +688,16 @@ __global__ __launch_bounds__(NWG * 64) void attn_mfma_grp_kernel(
   }
 }
 
-template <int D, int HB>
+// F8: the fp8 cache form - decode blocks only (one token per block), so no superblocks (the grouped
+// kernel has no fp8 form; mp_attention_mfma refuses them); HB 4 / 8 / 16.
+template <int D, int HB, bool F8>
 static void launch_attn_mfma(const AttnArgs& a, int page_log2, const RopeFuseM& rf, const int32_t* qb_tok0,
                              const int32_t* qb_ntok, int NB, const int32_t* sb_first, const int32_t* sb_n, int NSB,
                              hipStream_t stream) {
   const bf16_t *q = (const bf16_t*)a.q, *kc = (const bf16_t*)a.kc, *vc = (const bf16_t*)a.vc;
   float* ws_ml = attn_ws_ml(a);
   const float scale_log2 = attn_scale_log2(a);
-  if (sb_first != nullptr && NSB > 0 && rf.pos == nullptr) {
+  if (!F8 && sb_first != nullptr && NSB > 0 && rf.pos == nullptr) {
     hipLaunchKernelGGL((attn_mfma_grp_kernel<D, HB, 8>), dim3(NSB, a.nh / HB, a.NP), dim3(512), 0, stream, q,
                        a.q_stride, kc, vc, a.bt, a.bt_stride, a.q_seq, a.q_ctx, qb_tok0, qb_ntok, sb_first, sb_n,
                        (bf16_t*)a.out, a.workspace, ws_ml, a.nkv, a.nh, page_log2, a.PS, a.NP, scale_log2,
@@ -707,28 +709,10 @@ static void launch_attn_mfma(const AttnArgs& a, int page_log2, const RopeFuseM& 
                        a.bt_stride, a.q_seq, a.q_ctx, qb_tok0, qb_ntok, (bf16_t*)a.out, a.workspace, ws_ml, a.nkv,
                        a.nh, page_log2, a.PS, a.NP, scale_log2, a.packed_mt, rf, a.window);
   };
-  if (rf.pos && rf.qp.part) go(attn_mfma_kernel<D, HB, true, true>);
-  else if (rf.pos) go(attn_mfma_kernel<D, HB, true, false>);
-  else go(attn_mfma_kernel<D, HB, false, false>);
+  if (rf.pos && rf.qp.part) go(attn_mfma_kernel<D, HB, true, true, F8>);
+  else if (rf.pos) go(attn_mfma_kernel<D, HB, true, false, F8>);
+  else go(attn_mfma_kernel<D, HB, false, false, F8>);
 }
-
-// The fp8 cache form: decode blocks only (one token per block), so no superblocks; HB 4 / 8 / 16.
-template <int D, int HB>
-static void launch_attn_mfma_f8(const AttnArgs& a, int page_log2, const RopeFuseM& rf, const int32_t* qb_tok0,
-                                const int32_t* qb_ntok, int NB, hipStream_t stream) {
-  auto go = [&](auto kern) {
-    hipLaunchKernelGGL(kern, dim3(NB, a.nh / HB, a.NP), dim3(256), 0, stream, (const bf16_t*)a.q, a.q_stride,
-                       (const bf16_t*)a.kc, (const bf16_t*)a.vc, a.bt, a.bt_stride, a.q_seq, a.q_ctx, qb_tok0, qb_ntok,
-                       (bf16_t*)a.out, a.workspace, attn_ws_ml(a), a.nkv, a.nh, page_log2, a.PS, a.NP,
-                       attn_scale_log2(a), a.packed_mt, rf, a.window);
-  };
-  if (rf.pos && rf.qp.part) go(attn_mfma_kernel<D, HB, true, true, true>);
-  else if (rf.pos) go(attn_mfma_kernel<D, HB, true, false, true>);
-  else go(attn_mfma_kernel<D, HB, false, false, true>);
-}
-
-__global__ void paged_attn_reduce_kernel(const float* __restrict__ part_o, const float* __restrict__ part_ml,
-                                         bf16_t* __restrict__ out, int NP, int D, int nh, int packed_mt);
 
 }  // namespace mp
 
@@ -771,37 +755,22 @@ extern "C" int mp_attention_mfma(const mp::AttnArgs* args, const int32_t* qb_tok
   // several workgroups that re-read the same K / V measured 1.6-2.7x slower, profiles/r4k)
   const int hb = nrep >= 16 ? 16 : nrep;
   if (nrep % hb) return -3;
-  if (f8) {
-    if (hb != 4 && hb != 8 && hb != 16) return -10;
-#define MP_AM_F8_CASE(DD, HH)                                                            \
-  if (a.D == DD && hb == HH) {                                                           \
-    launch_attn_mfma_f8<DD, HH>(a, page_log2, rf, qb_tok0, qb_ntok, NB, stream);         \
-    goto launched;                                                                       \
-  }
-    MP_AM_F8_CASE(128, 4)
-    MP_AM_F8_CASE(128, 8)
-    MP_AM_F8_CASE(128, 16)
-    MP_AM_F8_CASE(64, 4)
-    MP_AM_F8_CASE(64, 8)
-    MP_AM_F8_CASE(64, 16)
-#undef MP_AM_F8_CASE
-    return -4;
-  }
-#define MP_AM_CASE(DD, HH)                                                                                  \
-  if (a.D == DD && hb == HH) {                                                                              \
-    launch_attn_mfma<DD, HH>(a, page_log2, rf, qb_tok0, qb_ntok, NB, sb_first, sb_n, NSB, stream);          \
+  if (f8 && hb != 4 && hb != 8 && hb != 16) return -10;
+#define MP_AM_CASE(DD, HH, F8)                                                                              \
+  if (a.D == DD && hb == HH && f8 == F8) {                                                                  \
+    launch_attn_mfma<DD, HH, F8>(a, page_log2, rf, qb_tok0, qb_ntok, NB, sb_first, sb_n, NSB, stream);      \
     goto launched;                                                                                          \
   }
-  MP_AM_CASE(128, 1)
-  MP_AM_CASE(128, 2)
-  MP_AM_CASE(128, 4)
-  MP_AM_CASE(128, 8)
-  MP_AM_CASE(128, 16)
-  MP_AM_CASE(64, 1)
-  MP_AM_CASE(64, 2)
-  MP_AM_CASE(64, 4)
-  MP_AM_CASE(64, 8)
-  MP_AM_CASE(64, 16)
+  MP_AM_CASE(128, 1, false)  // (heads per block 1 and 2 have no fp8 form: -10 above)
+  MP_AM_CASE(128, 2, false)
+  MP_AM_CASE(128, 4, false) MP_AM_CASE(128, 4, true)
+  MP_AM_CASE(128, 8, false) MP_AM_CASE(128, 8, true)
+  MP_AM_CASE(128, 16, false) MP_AM_CASE(128, 16, true)
+  MP_AM_CASE(64, 1, false)
+  MP_AM_CASE(64, 2, false)
+  MP_AM_CASE(64, 4, false) MP_AM_CASE(64, 4, true)
+  MP_AM_CASE(64, 8, false) MP_AM_CASE(64, 8, true)
+  MP_AM_CASE(64, 16, false) MP_AM_CASE(64, 16, true)
 #undef MP_AM_CASE
   return -4;
 launched:

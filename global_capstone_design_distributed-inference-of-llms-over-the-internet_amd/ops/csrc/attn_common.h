@@ -1,5 +1,6 @@
 // Device helpers of the decode attention kernels (attention.hip): DPP lane sums over a token's lane
-// group, packed bf16 dot products, the fused RoPE of one 8-element chunk.
+// group, packed bf16 dot products, the fused RoPE of one 8-element chunk; and the split-K combine
+// kernel every attention launcher ends in.
 #pragma once
 #include "common.h"
 
@@ -41,5 +42,9 @@ __device__ __forceinline__ u16x8 rope8(u16x8 me, u16x8 ot, f32x4 ca, f32x4 cb, f
   }
   return r;
 }
+
+// Combine split-K partials (defined in attention.hip; launched by all three attention launchers when NP > 1)
+__global__ void paged_attn_reduce_kernel(const float* __restrict__ part_o, const float* __restrict__ part_ml,
+                                         bf16_t* __restrict__ out, int NP, int D, int nh, int packed_mt);
 
 }  // namespace mp

@@ -199,36 +199,57 @@ inline void check_kv_f8(const at::Tensor& k_cache, const at::Tensor& v_cache, co
                reinterpret_cast<uintptr_t>(v_cache.data_ptr()) % 8 == 0, "fp8 KV codes must be 8-B aligned");
 }
 
+using OptTensor = c10::optional<at::Tensor>;
+
+// The cache type of an op, told by its trailing k_scale / v_scale: both given - an fp8 cache, neither -
+// a bf16 cache.
+inline bool kv_is_f8(const OptTensor& k_scale, const OptTensor& v_scale) {
+  MP_CHECK(k_scale.has_value() == v_scale.has_value(),
+           "fp8 KV cache: k_scale and v_scale are given together (neither: a bf16 cache)");
+  return k_scale.has_value();
+}
+
+// The cache pair of an attention op, by its type (true: fp8).  Code pages without scales fail the
+// bf16 rules and bf16 pages with scales the fp8 rules.
+inline bool check_kv(const at::Tensor& k_cache, const at::Tensor& v_cache, const OptTensor& k_scale,
+                     const OptTensor& v_scale, int64_t nkv) {
+  const bool f8 = kv_is_f8(k_scale, v_scale);
+  if (f8) check_kv_f8(k_cache, v_cache, *k_scale, *v_scale, nkv);
+  else check_kv_bf16(k_cache, v_cache);
+  return f8;
+}
+
+// RoPE of q in place + the new tokens' k / v into their cache slots; with scales, quantized into an fp8 cache
 void rope_kv_write(at::Tensor& qkv, const at::Tensor& positions, const at::Tensor& cos, const at::Tensor& sin,
-                   at::Tensor& k_cache, at::Tensor& v_cache, const at::Tensor& slots, int64_t nh, int64_t nkv) {
+                   at::Tensor& k_cache, at::Tensor& v_cache, const at::Tensor& slots, int64_t nh, int64_t nkv,
+                   const OptTensor& k_scale, const OptTensor& v_scale) {
   check_bf16_cuda(qkv, "qkv");
   check_rows(qkv, "qkv");
-  check_bf16_cuda(k_cache, "k_cache");
-  check_bf16_cuda(v_cache, "v_cache");
-  MP_CHECK(k_cache.dim() == 4 && k_cache.is_contiguous() && v_cache.is_contiguous(), "cache [pages, nkv, page, D]");
-  MP_CHECK(k_cache.sizes() == v_cache.sizes(), "k/v cache shapes differ");
-  MP_CHECK(k_cache.size(1) == nkv, "cache kv heads");
+  const bool f8 = kv_is_f8(k_scale, v_scale);
+  if (f8) {
+    check_kv_f8(k_cache, v_cache, *k_scale, *v_scale, nkv);
+  } else {
+    check_bf16_cuda(k_cache, "k_cache");
+    check_bf16_cuda(v_cache, "v_cache");
+    MP_CHECK(k_cache.dim() == 4 && k_cache.is_contiguous() && v_cache.is_contiguous(), "cache [pages, nkv, page, D]");
+    MP_CHECK(k_cache.sizes() == v_cache.sizes(), "k/v cache shapes differ");
+    MP_CHECK(k_cache.size(1) == nkv, "cache kv heads");
+  }
   const int D = k_cache.size(3);
   check_rope(qkv, positions, cos, sin, slots, nh, nkv, D);
+  if (f8) {
+    check_launch(mp_rope_kv_write_f8(qkv.data_ptr(), qkv.stride(0), positions.data_ptr<int64_t>(),
+                                     cos.data_ptr<float>(), sin.data_ptr<float>(), k_cache.data_ptr(),
+                                     v_cache.data_ptr(), k_scale->data_ptr(), v_scale->data_ptr(),
+                                     slots.data_ptr<int64_t>(), qkv.size(0), nh, nkv, D, k_cache.size(2),
+                                     cur_stream()),
+                 "rope_kv_write_f8");
+    return;
+  }
   check_launch(mp_rope_kv_write(qkv.data_ptr(), qkv.stride(0), positions.data_ptr<int64_t>(), cos.data_ptr<float>(),
                                 sin.data_ptr<float>(), k_cache.data_ptr(), v_cache.data_ptr(),
                                 slots.data_ptr<int64_t>(), qkv.size(0), nh, nkv, D, k_cache.size(2), cur_stream()),
                "rope_kv_write");
-}
-
-void rope_kv_write_f8(at::Tensor& qkv, const at::Tensor& positions, const at::Tensor& cos, const at::Tensor& sin,
-                      at::Tensor& k_cache, at::Tensor& v_cache, at::Tensor& k_scale, at::Tensor& v_scale,
-                      const at::Tensor& slots, int64_t nh, int64_t nkv) {
-  check_bf16_cuda(qkv, "qkv");
-  check_rows(qkv, "qkv");
-  check_kv_f8(k_cache, v_cache, k_scale, v_scale, nkv);
-  const int D = k_cache.size(3);
-  check_rope(qkv, positions, cos, sin, slots, nh, nkv, D);
-  check_launch(mp_rope_kv_write_f8(qkv.data_ptr(), qkv.stride(0), positions.data_ptr<int64_t>(), cos.data_ptr<float>(),
-                                   sin.data_ptr<float>(), k_cache.data_ptr(), v_cache.data_ptr(), k_scale.data_ptr(),
-                                   v_scale.data_ptr(), slots.data_ptr<int64_t>(), qkv.size(0), nh, nkv, D,
-                                   k_cache.size(2), cur_stream()),
-               "rope_kv_write_f8");
 }
 
 void kv_write(const at::Tensor& k, const at::Tensor& v, at::Tensor& k_cache, at::Tensor& v_cache,
@@ -247,13 +268,12 @@ void kv_write(const at::Tensor& k, const at::Tensor& v, at::Tensor& k_cache, at:
 }
 
 // The operands every attention op shares -> the launcher's arguments (mp_api.h), the fused-RoPE group
-// and the qkv partials left empty.  The caller has checked the cache pair (check_kv_bf16 / check_kv_f8);
-// k_scale / v_scale: the fp8 cache's scales.  packed: the output in the packed activation layout.
+// and the qkv partials left empty.  The caller has checked the cache pair (check_kv); k_scale / v_scale:
+// the fp8 cache's scales.  packed: the output in the packed activation layout.
 mp::AttnArgs attn_args(const at::Tensor& q, const at::Tensor& k_cache, const at::Tensor& v_cache,
-                       const at::Tensor& block_tables, const at::Tensor& q_seq, const at::Tensor& q_ctx,
-                       at::Tensor& out, at::Tensor& workspace, int64_t nh, int64_t nkv, double scale,
-                       int64_t part_size, int64_t num_parts, int64_t packed, const at::Tensor* k_scale = nullptr,
-                       const at::Tensor* v_scale = nullptr) {
+                       const OptTensor& k_scale, const OptTensor& v_scale, const at::Tensor& block_tables,
+                       const at::Tensor& q_seq, const at::Tensor& q_ctx, at::Tensor& out, at::Tensor& workspace,
+                       int64_t nh, int64_t nkv, double scale, int64_t part_size, int64_t num_parts, int64_t packed) {
   check_bf16_cuda(q, "q");
   check_rows(q, "q");
   check_bf16_cuda(out, "out");
@@ -278,7 +298,7 @@ mp::AttnArgs attn_args(const at::Tensor& q, const at::Tensor& k_cache, const at:
   a.q_stride = q.stride(0);
   a.kc = k_cache.data_ptr();
   a.vc = v_cache.data_ptr();
-  if (k_scale != nullptr) {
+  if (k_scale.has_value()) {
     a.ks = k_scale->data_ptr();
     a.vs = v_scale->data_ptr();
   }
@@ -359,74 +379,44 @@ void launch_paged(mp::AttnArgs a, const c10::optional<at::Tensor>& counters, int
                a.ks != nullptr ? "paged_attention_f8" : "paged_attention");
 }
 
+// Flash-decoding paged attention; with k_scale / v_scale on an fp8 KV cache (attention.hip F8 form).
 void paged_attention(const at::Tensor& q, const at::Tensor& k_cache, const at::Tensor& v_cache,
                      const at::Tensor& block_tables, const at::Tensor& q_seq, const at::Tensor& q_ctx,
                      at::Tensor& out, at::Tensor& workspace, int64_t nh, int64_t nkv, double scale, int64_t part_size,
-                     int64_t num_parts, int64_t packed, const c10::optional<at::Tensor>& counters,
-    int64_t window) {
-  check_kv_bf16(k_cache, v_cache);
-  launch_paged(attn_args(q, k_cache, v_cache, block_tables, q_seq, q_ctx, out, workspace, nh, nkv, scale, part_size,
-                         num_parts, packed),
-               counters, window);
-}
-
-// The flash-decoding kernel on an fp8 KV cache (attention.hip F8 form).
-void paged_attention_f8(const at::Tensor& q, const at::Tensor& k_cache, const at::Tensor& v_cache,
-                        const at::Tensor& k_scale, const at::Tensor& v_scale, const at::Tensor& block_tables,
-                        const at::Tensor& q_seq, const at::Tensor& q_ctx, at::Tensor& out, at::Tensor& workspace,
-                        int64_t nh, int64_t nkv, double scale, int64_t part_size, int64_t num_parts, int64_t packed,
-                        const c10::optional<at::Tensor>& counters,
-    int64_t window) {
-  check_kv_f8(k_cache, v_cache, k_scale, v_scale, nkv);
-  launch_paged(attn_args(q, k_cache, v_cache, block_tables, q_seq, q_ctx, out, workspace, nh, nkv, scale, part_size,
-                         num_parts, packed, &k_scale, &v_scale),
+                     int64_t num_parts, int64_t packed, const OptTensor& counters, int64_t window,
+                     const OptTensor& k_scale, const OptTensor& v_scale) {
+  check_kv(k_cache, v_cache, k_scale, v_scale, nkv);
+  launch_paged(attn_args(q, k_cache, v_cache, k_scale, v_scale, block_tables, q_seq, q_ctx, out, workspace, nh, nkv,
+                         scale, part_size, num_parts, packed),
                counters, window);
 }
 
 // Decode attention with RoPE + KV write fused in (attention.hip ROPE path): q is the unrotated
-// fused qkv row; k_cache / v_cache receive the new token at slots[t].
+// fused qkv row; k_cache / v_cache receive the new token at slots[t].  On an fp8 cache: RoPE, the new
+// token's quantization + page write and attention in one launch.
 void paged_attention_rope(const at::Tensor& qkv, at::Tensor& k_cache, at::Tensor& v_cache,
                           const at::Tensor& block_tables, const at::Tensor& q_seq, const at::Tensor& q_ctx,
                           const at::Tensor& positions, const at::Tensor& cos, const at::Tensor& sin,
                           const at::Tensor& slots, at::Tensor& out, at::Tensor& workspace, int64_t nh, int64_t nkv,
                           double scale, int64_t part_size, int64_t num_parts, int64_t packed,
-                          const c10::optional<at::Tensor>& counters, const c10::optional<at::Tensor>& qkv_part,
-                          int64_t part_splits, const c10::optional<at::Tensor>& part_ss, double inv_k, double eps,
-    int64_t window) {
-  check_kv_bf16(k_cache, v_cache);
+                          const OptTensor& counters, const OptTensor& qkv_part, int64_t part_splits,
+                          const OptTensor& part_ss, double inv_k, double eps, int64_t window,
+                          const OptTensor& k_scale, const OptTensor& v_scale) {
+  check_kv(k_cache, v_cache, k_scale, v_scale, nkv);
   const int D = k_cache.size(3);
   check_rope(qkv, positions, cos, sin, slots, nh, nkv, D);
   MP_CHECK(D % 16 == 0, "head dim");
   const mp::QkvPart qp = qkv_part_args(qkv_part, part_splits, part_ss, inv_k, eps, qkv.size(0), qkv.size(1));
-  mp::AttnArgs a = attn_args(qkv, k_cache, v_cache, block_tables, q_seq, q_ctx, out, workspace, nh, nkv, scale,
-                             part_size, num_parts, packed);
-  fuse_rope(a, positions, cos, sin, slots, qp);
-  launch_paged(a, counters, window);
-}
-
-// Its fp8 cache form: RoPE, the new token's quantization + page write and attention in one launch.
-void paged_attention_rope_f8(const at::Tensor& qkv, at::Tensor& k_cache, at::Tensor& v_cache, at::Tensor& k_scale,
-                             at::Tensor& v_scale, const at::Tensor& block_tables, const at::Tensor& q_seq,
-                             const at::Tensor& q_ctx, const at::Tensor& positions, const at::Tensor& cos,
-                             const at::Tensor& sin, const at::Tensor& slots, at::Tensor& out, at::Tensor& workspace,
-                             int64_t nh, int64_t nkv, double scale, int64_t part_size, int64_t num_parts,
-                             int64_t packed, const c10::optional<at::Tensor>& counters,
-                             const c10::optional<at::Tensor>& qkv_part, int64_t part_splits,
-                             const c10::optional<at::Tensor>& part_ss, double inv_k, double eps,
-    int64_t window) {
-  check_kv_f8(k_cache, v_cache, k_scale, v_scale, nkv);
-  check_rope(qkv, positions, cos, sin, slots, nh, nkv, k_cache.size(3));
-  const mp::QkvPart qp = qkv_part_args(qkv_part, part_splits, part_ss, inv_k, eps, qkv.size(0), qkv.size(1));
-  mp::AttnArgs a = attn_args(qkv, k_cache, v_cache, block_tables, q_seq, q_ctx, out, workspace, nh, nkv, scale,
-                             part_size, num_parts, packed, &k_scale, &v_scale);
+  mp::AttnArgs a = attn_args(qkv, k_cache, v_cache, k_scale, v_scale, block_tables, q_seq, q_ctx, out, workspace, nh,
+                             nkv, scale, part_size, num_parts, packed);
   fuse_rope(a, positions, cos, sin, slots, qp);
   launch_paged(a, counters, window);
 }
 
 // The MFMA launch (attention_mfma.hip): query blocks, optional prefill superblocks int32 [2, NSB]
 // (first query block, count <= 4), optional MX output.
-void launch_mfma(mp::AttnArgs a, const at::Tensor& qblocks, const c10::optional<at::Tensor>& superblocks,
-                 int64_t window, void* mx_ax = nullptr, void* mx_as = nullptr) {
+void launch_mfma(mp::AttnArgs a, const at::Tensor& qblocks, const OptTensor& superblocks, int64_t window,
+                 void* mx_ax = nullptr, void* mx_as = nullptr) {
   const auto [qb, NB] = check_blocks(qblocks, false, INT64_MAX, "qblocks int32 [2, NB] (first token, token count)");
   // the window is built for decode blocks (one token per block, NB == T), not for multi-token blocks
   // or the grouped prefill kernel
@@ -441,88 +431,68 @@ void launch_mfma(mp::AttnArgs a, const at::Tensor& qblocks, const c10::optional<
                "attention_mfma");
 }
 
+// The MFMA ops on an fp8 cache (attention_mfma.hip F8 form): decode blocks only (one token per query
+// block), the whole GQA group in the MFMA rows - no superblocks, no MX output.
+inline void check_mfma_f8(const at::Tensor& q, const at::Tensor& qblocks, int64_t nh, int64_t nkv, bool superblocks,
+                          bool mx_out) {
+  MP_CHECK(!superblocks, "attention_mfma on an fp8 KV cache has no grouped prefill form: superblocks must be None");
+  MP_CHECK(!mx_out, "attention_mfma on an fp8 KV cache has no MX output: mx_ax must be None");
+  MP_CHECK(nkv > 0 && nh % nkv == 0 && (nh / nkv == 4 || nh / nkv == 8 || (nh / nkv >= 16 && (nh / nkv) % 16 == 0)),
+           "attention_mfma on an fp8 KV cache supports GQA group sizes nh / nkv of 4, 8 and multiples of 16");
+  MP_CHECK(qblocks.dim() == 2 && qblocks.size(1) == q.size(0),
+           "attention_mfma on an fp8 KV cache needs one query token per block (decode)");
+}
+
 void attention_mfma(const at::Tensor& q, const at::Tensor& k_cache, const at::Tensor& v_cache,
                     const at::Tensor& block_tables, const at::Tensor& q_seq, const at::Tensor& q_ctx,
                     const at::Tensor& qblocks, at::Tensor& out, at::Tensor& workspace, int64_t nh, int64_t nkv,
-                    double scale, int64_t part_size, int64_t num_parts, int64_t packed,
-                    const c10::optional<at::Tensor>& superblocks,
-    int64_t window) {
-  check_kv_bf16(k_cache, v_cache);
-  launch_mfma(attn_args(q, k_cache, v_cache, block_tables, q_seq, q_ctx, out, workspace, nh, nkv, scale, part_size,
-                        num_parts, packed),
+                    double scale, int64_t part_size, int64_t num_parts, int64_t packed, const OptTensor& superblocks,
+                    int64_t window, const OptTensor& k_scale, const OptTensor& v_scale) {
+  if (check_kv(k_cache, v_cache, k_scale, v_scale, nkv))
+    check_mfma_f8(q, qblocks, nh, nkv, superblocks.has_value(), false);
+  launch_mfma(attn_args(q, k_cache, v_cache, k_scale, v_scale, block_tables, q_seq, q_ctx, out, workspace, nh, nkv,
+                        scale, part_size, num_parts, packed),
               qblocks, superblocks, window);
 }
 
-// The FA2 prefill launch (attention_fa.hip), on a bf16 or an fp8 (a.ks) cache.  windowed: the
-// sliding-window form (attention_fa_window / attention_fa_window_f8), which needs a window > 0; the
-// plain ops keep refusing one.
-void launch_fa(mp::AttnArgs a, const at::Tensor& fablocks, int64_t waves, int64_t pair, int64_t window,
-               bool windowed = false) {
+// Causal prefill attention, 32x32x16 MFMA FA2 form (attention_fa.hip): row-major output, on a bf16 or an
+// fp8 cache.  windowed: the sliding-window form (WIN form), which needs a window W > 0 - a query of
+// context ctx sees [max(0, ctx - W), ctx), and part_size x num_parts covers the span a block streams;
+// the plain op keeps refusing a window.
+void launch_fa(bool windowed, const at::Tensor& q, const at::Tensor& k_cache, const at::Tensor& v_cache,
+               const at::Tensor& block_tables, const at::Tensor& q_seq, const at::Tensor& q_ctx,
+               const at::Tensor& fablocks, at::Tensor& out, at::Tensor& workspace, int64_t nh, int64_t nkv,
+               double scale, int64_t part_size, int64_t num_parts, int64_t waves, int64_t pair, int64_t window,
+               const OptTensor& k_scale, const OptTensor& v_scale) {
+  const bool f8 = check_kv(k_cache, v_cache, k_scale, v_scale, nkv);
+  const std::string name = std::string(windowed ? "attention_fa_window" : "attention_fa") + (f8 ? "_f8" : "");
+  MP_CHECK(k_cache.size(3) == 128, name + ": head_dim 128");
+  mp::AttnArgs a = attn_args(q, k_cache, v_cache, k_scale, v_scale, block_tables, q_seq, q_ctx, out, workspace, nh,
+                             nkv, scale, part_size, num_parts, 0);
   attn_window(a, window, windowed, "attention_fa");
   MP_CHECK(!windowed || window > 0, "attention_fa_window: window must be > 0");
   const auto [fb, NB] =
       check_blocks(fablocks, true, INT64_MAX, "fablocks int32 [2, NB] (first token, token count), ops.fa_blocks");
   MP_CHECK(waves == 4 || waves == 8, "waves 4 or 8");
-  if (windowed) {
-    check_launch(mp_attention_fa_window(&a, fb, fb + NB, NB, (int)waves, (int)pair, cur_stream()),
-                 a.ks != nullptr ? "attention_fa_window_f8" : "attention_fa_window");
-    return;
-  }
-  check_launch(mp_attention_fa(&a, fb, fb + NB, NB, (int)waves, (int)pair, cur_stream()),
-               a.ks != nullptr ? "attention_fa_f8" : "attention_fa");
+  check_launch(mp_attention_fa(&a, fb, fb + NB, NB, (int)waves, (int)pair, windowed, cur_stream()), name.c_str());
 }
 
-// Causal prefill attention, 32x32x16 MFMA FA2 form (attention_fa.hip): row-major output.
 void attention_fa(const at::Tensor& q, const at::Tensor& k_cache, const at::Tensor& v_cache,
                   const at::Tensor& block_tables, const at::Tensor& q_seq, const at::Tensor& q_ctx,
                   const at::Tensor& fablocks, at::Tensor& out, at::Tensor& workspace, int64_t nh, int64_t nkv,
-                  double scale, int64_t part_size, int64_t num_parts, int64_t waves, int64_t pair,
-    int64_t window) {
-  check_kv_bf16(k_cache, v_cache);
-  MP_CHECK(k_cache.size(3) == 128, "attention_fa: head_dim 128");
-  launch_fa(attn_args(q, k_cache, v_cache, block_tables, q_seq, q_ctx, out, workspace, nh, nkv, scale, part_size,
-                      num_parts, 0),
-            fablocks, waves, pair, window);
+                  double scale, int64_t part_size, int64_t num_parts, int64_t waves, int64_t pair, int64_t window,
+                  const OptTensor& k_scale, const OptTensor& v_scale) {
+  launch_fa(false, q, k_cache, v_cache, block_tables, q_seq, q_ctx, fablocks, out, workspace, nh, nkv, scale,
+            part_size, num_parts, waves, pair, window, k_scale, v_scale);
 }
 
-// Its fp8 cache form (attention_fa.hip F8 form): the same blocks, parts and pairing.
-void attention_fa_f8(const at::Tensor& q, const at::Tensor& k_cache, const at::Tensor& v_cache,
-                     const at::Tensor& k_scale, const at::Tensor& v_scale, const at::Tensor& block_tables,
-                     const at::Tensor& q_seq, const at::Tensor& q_ctx, const at::Tensor& fablocks, at::Tensor& out,
-                     at::Tensor& workspace, int64_t nh, int64_t nkv, double scale, int64_t part_size,
-                     int64_t num_parts, int64_t waves, int64_t pair,
-    int64_t window) {
-  check_kv_f8(k_cache, v_cache, k_scale, v_scale, nkv);
-  MP_CHECK(k_cache.size(3) == 128, "attention_fa_f8: head_dim 128");
-  launch_fa(attn_args(q, k_cache, v_cache, block_tables, q_seq, q_ctx, out, workspace, nh, nkv, scale, part_size,
-                      num_parts, 0, &k_scale, &v_scale),
-            fablocks, waves, pair, window);
-}
-
-// The sliding-window forms of the two above (attention_fa.hip WIN form): window W > 0, a query of
-// context ctx sees [max(0, ctx - W), ctx); part_size x num_parts covers the span a block streams.
 void attention_fa_window(const at::Tensor& q, const at::Tensor& k_cache, const at::Tensor& v_cache,
                          const at::Tensor& block_tables, const at::Tensor& q_seq, const at::Tensor& q_ctx,
                          const at::Tensor& fablocks, at::Tensor& out, at::Tensor& workspace, int64_t nh, int64_t nkv,
                          double scale, int64_t part_size, int64_t num_parts, int64_t waves, int64_t pair,
-                         int64_t window) {
-  check_kv_bf16(k_cache, v_cache);
-  MP_CHECK(k_cache.size(3) == 128, "attention_fa_window: head_dim 128");
-  launch_fa(attn_args(q, k_cache, v_cache, block_tables, q_seq, q_ctx, out, workspace, nh, nkv, scale, part_size,
-                      num_parts, 0),
-            fablocks, waves, pair, window, true);
-}
-
-void attention_fa_window_f8(const at::Tensor& q, const at::Tensor& k_cache, const at::Tensor& v_cache,
-                            const at::Tensor& k_scale, const at::Tensor& v_scale, const at::Tensor& block_tables,
-                            const at::Tensor& q_seq, const at::Tensor& q_ctx, const at::Tensor& fablocks,
-                            at::Tensor& out, at::Tensor& workspace, int64_t nh, int64_t nkv, double scale,
-                            int64_t part_size, int64_t num_parts, int64_t waves, int64_t pair, int64_t window) {
-  check_kv_f8(k_cache, v_cache, k_scale, v_scale, nkv);
-  MP_CHECK(k_cache.size(3) == 128, "attention_fa_window_f8: head_dim 128");
-  launch_fa(attn_args(q, k_cache, v_cache, block_tables, q_seq, q_ctx, out, workspace, nh, nkv, scale, part_size,
-                      num_parts, 0, &k_scale, &v_scale),
-            fablocks, waves, pair, window, true);
+                         int64_t window, const OptTensor& k_scale, const OptTensor& v_scale) {
+  launch_fa(true, q, k_cache, v_cache, block_tables, q_seq, q_ctx, fablocks, out, workspace, nh, nkv, scale,
+            part_size, num_parts, waves, pair, window, k_scale, v_scale);
 }
 
 // GQA decode with RoPE + KV write fused (attention_mfma.hip ROPE path): one token per query block,
@@ -532,11 +502,11 @@ void attention_mfma_rope(const at::Tensor& qkv, at::Tensor& k_cache, at::Tensor&
                          const at::Tensor& qblocks, const at::Tensor& positions, const at::Tensor& cos,
                          const at::Tensor& sin, const at::Tensor& slots, at::Tensor& out, at::Tensor& workspace,
                          int64_t nh, int64_t nkv, double scale, int64_t part_size, int64_t num_parts, int64_t packed,
-                         const c10::optional<at::Tensor>& qkv_part, int64_t part_splits,
-                         const c10::optional<at::Tensor>& part_ss, double inv_k, double eps,
-                         const c10::optional<at::Tensor>& mx_ax, const c10::optional<at::Tensor>& mx_as,
-    int64_t window) {
-  check_kv_bf16(k_cache, v_cache);
+                         const OptTensor& qkv_part, int64_t part_splits, const OptTensor& part_ss, double inv_k,
+                         double eps, const OptTensor& mx_ax, const OptTensor& mx_as, int64_t window,
+                         const OptTensor& k_scale, const OptTensor& v_scale) {
+  if (check_kv(k_cache, v_cache, k_scale, v_scale, nkv))
+    check_mfma_f8(qkv, qblocks, nh, nkv, false, mx_ax.has_value());
   const int D = k_cache.size(3), T = qkv.size(0);
   check_rope(qkv, positions, cos, sin, slots, nh, nkv, D);
   MP_CHECK(qblocks.size(1) == T, "fused RoPE needs one query token per block (decode)");
@@ -553,50 +523,10 @@ void attention_mfma_rope(const at::Tensor& qkv, at::Tensor& k_cache, at::Tensor&
     axp = mx_ax->data_ptr();
     asp = mx_as->data_ptr();
   }
-  mp::AttnArgs a = attn_args(qkv, k_cache, v_cache, block_tables, q_seq, q_ctx, out, workspace, nh, nkv, scale,
-                             part_size, num_parts, packed);
+  mp::AttnArgs a = attn_args(qkv, k_cache, v_cache, k_scale, v_scale, block_tables, q_seq, q_ctx, out, workspace, nh,
+                             nkv, scale, part_size, num_parts, packed);
   fuse_rope(a, positions, cos, sin, slots, qp);
   launch_mfma(a, qblocks, c10::nullopt, window, axp, asp);
-}
-
-// The fp8 cache forms of the two above (attention_mfma.hip F8 form): decode blocks only (one token
-// per query block), the whole GQA group in the MFMA rows - no superblocks, no MX output.
-inline void check_mfma_f8(const at::Tensor& q, const at::Tensor& qblocks, int64_t nh, int64_t nkv) {
-  MP_CHECK(nkv > 0 && nh % nkv == 0 && (nh / nkv == 4 || nh / nkv == 8 || (nh / nkv >= 16 && (nh / nkv) % 16 == 0)),
-           "attention_mfma on an fp8 KV cache supports GQA group sizes nh / nkv of 4, 8 and multiples of 16");
-  MP_CHECK(qblocks.dim() == 2 && qblocks.size(1) == q.size(0),
-           "attention_mfma on an fp8 KV cache needs one query token per block (decode)");
-}
-
-void attention_mfma_f8(const at::Tensor& q, const at::Tensor& k_cache, const at::Tensor& v_cache,
-                       const at::Tensor& k_scale, const at::Tensor& v_scale, const at::Tensor& block_tables,
-                       const at::Tensor& q_seq, const at::Tensor& q_ctx, const at::Tensor& qblocks, at::Tensor& out,
-                       at::Tensor& workspace, int64_t nh, int64_t nkv, double scale, int64_t part_size,
-                       int64_t num_parts, int64_t packed,
-    int64_t window) {
-  check_kv_f8(k_cache, v_cache, k_scale, v_scale, nkv);
-  check_mfma_f8(q, qblocks, nh, nkv);
-  launch_mfma(attn_args(q, k_cache, v_cache, block_tables, q_seq, q_ctx, out, workspace, nh, nkv, scale, part_size,
-                        num_parts, packed, &k_scale, &v_scale),
-              qblocks, c10::nullopt, window);
-}
-
-void attention_mfma_rope_f8(const at::Tensor& qkv, at::Tensor& k_cache, at::Tensor& v_cache, at::Tensor& k_scale,
-                            at::Tensor& v_scale, const at::Tensor& block_tables, const at::Tensor& q_seq,
-                            const at::Tensor& q_ctx, const at::Tensor& qblocks, const at::Tensor& positions,
-                            const at::Tensor& cos, const at::Tensor& sin, const at::Tensor& slots, at::Tensor& out,
-                            at::Tensor& workspace, int64_t nh, int64_t nkv, double scale, int64_t part_size,
-                            int64_t num_parts, int64_t packed, const c10::optional<at::Tensor>& qkv_part,
-                            int64_t part_splits, const c10::optional<at::Tensor>& part_ss, double inv_k, double eps,
-    int64_t window) {
-  check_kv_f8(k_cache, v_cache, k_scale, v_scale, nkv);
-  check_mfma_f8(qkv, qblocks, nh, nkv);
-  check_rope(qkv, positions, cos, sin, slots, nh, nkv, k_cache.size(3));
-  const mp::QkvPart qp = qkv_part_args(qkv_part, part_splits, part_ss, inv_k, eps, qkv.size(0), qkv.size(1));
-  mp::AttnArgs a = attn_args(qkv, k_cache, v_cache, block_tables, q_seq, q_ctx, out, workspace, nh, nkv, scale,
-                             part_size, num_parts, packed, &k_scale, &v_scale);
-  fuse_rope(a, positions, cos, sin, slots, qp);
-  launch_mfma(a, qblocks, c10::nullopt, window);
 }
 
 void embedding(const at::Tensor& ids, const at::Tensor& table, at::Tensor& out) {
@@ -1010,68 +940,42 @@ TORCH_LIBRARY(mpamd, m) {
   m.def(
       "rmsnorm(Tensor x, Tensor(a!) residual, Tensor w, Tensor(b!) y, float eps, int mode, Tensor? rows, "
       "int packed, Tensor(c!)? ss=None, Tensor(d!)? a8=None, Tensor(e!)? a8_scale=None, Tensor? gather=None) -> ()");
+  // the KV-write and attention ops end in k_scale / v_scale: both given on an fp8 KV cache (k_cache / v_cache
+  // then hold its uint8 codes), neither on a bf16 cache
   m.def(
       "rope_kv_write(Tensor(a!) qkv, Tensor positions, Tensor cos, Tensor sin, Tensor(b!) k_cache, "
-      "Tensor(c!) v_cache, Tensor slots, int nh, int nkv) -> ()");
+      "Tensor(c!) v_cache, Tensor slots, int nh, int nkv, Tensor(d!)? k_scale=None, Tensor(e!)? v_scale=None) -> ()");
   m.def("kv_write(Tensor k, Tensor v, Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor slots) -> ()");
   m.def(
       "paged_attention(Tensor q, Tensor k_cache, Tensor v_cache, Tensor block_tables, Tensor q_seq, Tensor q_ctx, "
       "Tensor(a!) out, Tensor(b!) workspace, int nh, int nkv, float scale, int part_size, int num_parts, "
-      "int packed, Tensor(c!)? counters=None, int window=0) -> ()");
+      "int packed, Tensor(c!)? counters=None, int window=0, Tensor? k_scale=None, Tensor? v_scale=None) -> ()");
   m.def(
       "paged_attention_rope(Tensor qkv, Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor block_tables, Tensor q_seq, "
       "Tensor q_ctx, Tensor positions, Tensor cos, Tensor sin, Tensor slots, Tensor(c!) out, Tensor(d!) workspace, "
       "int nh, int nkv, float scale, int part_size, int num_parts, int packed, Tensor(e!)? counters=None, "
-      "Tensor? qkv_part=None, int part_splits=0, Tensor? part_ss=None, float inv_k=0., float eps=0., int window=0) -> ()");
-  m.def(
-      "rope_kv_write_f8(Tensor(a!) qkv, Tensor positions, Tensor cos, Tensor sin, Tensor(b!) k_cache, "
-      "Tensor(c!) v_cache, Tensor(d!) k_scale, Tensor(e!) v_scale, Tensor slots, int nh, int nkv) -> ()");
-  m.def(
-      "paged_attention_f8(Tensor q, Tensor k_cache, Tensor v_cache, Tensor k_scale, Tensor v_scale, "
-      "Tensor block_tables, Tensor q_seq, Tensor q_ctx, Tensor(a!) out, Tensor(b!) workspace, int nh, int nkv, "
-      "float scale, int part_size, int num_parts, int packed, Tensor(c!)? counters=None, int window=0) -> ()");
-  m.def(
-      "paged_attention_rope_f8(Tensor qkv, Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor(c!) k_scale, "
-      "Tensor(d!) v_scale, Tensor block_tables, Tensor q_seq, Tensor q_ctx, Tensor positions, Tensor cos, Tensor sin, "
-      "Tensor slots, Tensor(e!) out, Tensor(f!) workspace, int nh, int nkv, float scale, int part_size, "
-      "int num_parts, int packed, Tensor(g!)? counters=None, Tensor? qkv_part=None, int part_splits=0, "
-      "Tensor? part_ss=None, float inv_k=0., float eps=0., int window=0) -> ()");
+      "Tensor? qkv_part=None, int part_splits=0, Tensor? part_ss=None, float inv_k=0., float eps=0., int window=0, "
+      "Tensor(f!)? k_scale=None, Tensor(g!)? v_scale=None) -> ()");
   m.def(
       "attention_mfma(Tensor q, Tensor k_cache, Tensor v_cache, Tensor block_tables, Tensor q_seq, Tensor q_ctx, "
       "Tensor qblocks, Tensor(a!) out, Tensor(b!) workspace, int nh, int nkv, float scale, int part_size, "
-      "int num_parts, int packed, Tensor? superblocks=None, int window=0) -> ()");
+      "int num_parts, int packed, Tensor? superblocks=None, int window=0, Tensor? k_scale=None, "
+      "Tensor? v_scale=None) -> ()");
   m.def(
       "attention_fa(Tensor q, Tensor k_cache, Tensor v_cache, Tensor block_tables, Tensor q_seq, Tensor q_ctx, "
       "Tensor fablocks, Tensor(a!) out, Tensor(b!) workspace, int nh, int nkv, float scale, int part_size, "
-      "int num_parts, int waves, int pair=0, int window=0) -> ()");
-  m.def(
-      "attention_fa_f8(Tensor q, Tensor k_cache, Tensor v_cache, Tensor k_scale, Tensor v_scale, Tensor block_tables, "
-      "Tensor q_seq, Tensor q_ctx, Tensor fablocks, Tensor(a!) out, Tensor(b!) workspace, int nh, int nkv, "
-      "float scale, int part_size, int num_parts, int waves, int pair=0, int window=0) -> ()");
+      "int num_parts, int waves, int pair=0, int window=0, Tensor? k_scale=None, Tensor? v_scale=None) -> ()");
   m.def(
       "attention_fa_window(Tensor q, Tensor k_cache, Tensor v_cache, Tensor block_tables, Tensor q_seq, Tensor q_ctx, "
       "Tensor fablocks, Tensor(a!) out, Tensor(b!) workspace, int nh, int nkv, float scale, int part_size, "
-      "int num_parts, int waves, int pair, int window) -> ()");
-  m.def(
-      "attention_fa_window_f8(Tensor q, Tensor k_cache, Tensor v_cache, Tensor k_scale, Tensor v_scale, "
-      "Tensor block_tables, Tensor q_seq, Tensor q_ctx, Tensor fablocks, Tensor(a!) out, Tensor(b!) workspace, int nh, "
-      "int nkv, float scale, int part_size, int num_parts, int waves, int pair, int window) -> ()");
+      "int num_parts, int waves, int pair, int window, Tensor? k_scale=None, Tensor? v_scale=None) -> ()");
   m.def(
       "attention_mfma_rope(Tensor qkv, Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor block_tables, Tensor q_seq, "
       "Tensor q_ctx, Tensor qblocks, Tensor positions, Tensor cos, Tensor sin, Tensor slots, Tensor(c!) out, "
       "Tensor(d!) workspace, int nh, int nkv, float scale, int part_size, int num_parts, int packed, "
       "Tensor? qkv_part=None, int part_splits=0, Tensor? part_ss=None, float inv_k=0., float eps=0., "
-      "Tensor(e!)? mx_ax=None, Tensor(f!)? mx_as=None, int window=0) -> ()");
-  m.def(
-      "attention_mfma_f8(Tensor q, Tensor k_cache, Tensor v_cache, Tensor k_scale, Tensor v_scale, "
-      "Tensor block_tables, Tensor q_seq, Tensor q_ctx, Tensor qblocks, Tensor(a!) out, Tensor(b!) workspace, int nh, "
-      "int nkv, float scale, int part_size, int num_parts, int packed, int window=0) -> ()");
-  m.def(
-      "attention_mfma_rope_f8(Tensor qkv, Tensor(a!) k_cache, Tensor(b!) v_cache, Tensor(c!) k_scale, "
-      "Tensor(d!) v_scale, Tensor block_tables, Tensor q_seq, Tensor q_ctx, Tensor qblocks, Tensor positions, "
-      "Tensor cos, Tensor sin, Tensor slots, Tensor(e!) out, Tensor(f!) workspace, int nh, int nkv, float scale, "
-      "int part_size, int num_parts, int packed, Tensor? qkv_part=None, int part_splits=0, Tensor? part_ss=None, "
-      "float inv_k=0., float eps=0., int window=0) -> ()");
+      "Tensor(e!)? mx_ax=None, Tensor(f!)? mx_as=None, int window=0, Tensor(g!)? k_scale=None, "
+      "Tensor(h!)? v_scale=None) -> ()");
   m.def("embedding(Tensor ids, Tensor table, Tensor(a!) out) -> ()");
   m.def("swiglu(Tensor gu, Tensor(a!) out) -> ()");
   m.def("add(Tensor a, Tensor b, Tensor(a!) y) -> ()");
@@ -1116,17 +1020,10 @@ TORCH_LIBRARY_IMPL(mpamd, CUDA, m) {
   m.impl("kv_write", &kv_write);
   m.impl("paged_attention", &paged_attention);
   m.impl("paged_attention_rope", &paged_attention_rope);
-  m.impl("rope_kv_write_f8", &rope_kv_write_f8);
-  m.impl("paged_attention_f8", &paged_attention_f8);
-  m.impl("paged_attention_rope_f8", &paged_attention_rope_f8);
   m.impl("attention_mfma", &attention_mfma);
   m.impl("attention_fa", &attention_fa);
-  m.impl("attention_fa_f8", &attention_fa_f8);
   m.impl("attention_fa_window", &attention_fa_window);
-  m.impl("attention_fa_window_f8", &attention_fa_window_f8);
   m.impl("attention_mfma_rope", &attention_mfma_rope);
-  m.impl("attention_mfma_f8", &attention_mfma_f8);
-  m.impl("attention_mfma_rope_f8", &attention_mfma_rope_f8);
   m.impl("embedding", &embedding);
   m.impl("swiglu", &swiglu);
   m.impl("add", &add);

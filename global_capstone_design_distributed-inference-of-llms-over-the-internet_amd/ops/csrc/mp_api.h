@@ -47,7 +47,7 @@ struct AttnArgs {
   const int64_t* slots;            //   [T] cache slot of the new token (< 0: nothing written)
   QkvPart qp;                      // qp.part == nullptr: absent
   int window;                      // sliding window W: a query of context ctx sees cache positions
-                                   //   [max(0, ctx - W), ctx); 0: no window (decode kernels, mp_attention_fa_window)
+                                   //   [max(0, ctx - W), ctx); 0: no window (decode kernels, mp_attention_fa's windowed form)
 };
 
 // log2 of the page size, or -1 when it is no power of two
@@ -98,9 +98,7 @@ int mp_attention_mfma(const mp::AttnArgs* a, const int32_t* qb_tok0, const int32
                       const int32_t* sb_first, const int32_t* sb_n, int NSB, void* mx_ax, void* mx_as,
                       hipStream_t stream);
 int mp_attention_fa(const mp::AttnArgs* a, const int32_t* fb_tok0, const int32_t* fb_ntok, int NBF, int nw, int pair,
-                    hipStream_t stream);
-int mp_attention_fa_window(const mp::AttnArgs* a, const int32_t* fb_tok0, const int32_t* fb_ntok, int NBF, int nw,
-                           int pair, hipStream_t stream);  // a->window > 0: the kernel's sliding-window form
+                    int windowed, hipStream_t stream);  // windowed: the sliding-window form, a->window > 0 (else 0)
 // elementwise.hip
 int mp_embedding(const int64_t* ids, const void* table, void* out, int T, int H, int64_t vocab, hipStream_t stream);
 int mp_swiglu(const void* gu, void* out, int64_t T, int F, hipStream_t stream);

@@ -586,52 +586,46 @@ class StageExecutor:
         per-query causal rows (``qblocks`` is ignored).  Under a sliding window a prefill step with a
         row past the window runs the FA2 kernel's windowed form where FA2 covers it, else those rows."""
         table = self.sessions.table_dev
+        f8, win, prefill = self._kv_fp8, self.window, qblocks is not None
+        # FA2 covers a prefill step with blocks (plan.fablocks) and a row-major output
+        fa = prefill and self._cur_fb is not None and not packed
+
+        def flash():
+            return ops.paged_attention(qkv, kc, vc, table, q_seq, q_ctx, self.nh, self.nkv, self.scale, out=out,
+                                       workspace=ws, part_size=ps, num_parts=np_, packed=packed,
+                                       window=win, max_ctx=max_ctx)
+
         # sliding window: the decode kernels take it, and so does the FA2 prefill kernel's windowed form
         # (row-major steps it covers: window_fa).  The grouped MFMA kernel has none: a prefill step keeps
         # the unwindowed kernels only while no row is past the window (the same computation) and
         # otherwise runs the windowed FA2 form, or the flash-decoding kernel as per-query causal rows
-        win = self.window
-        if win and qblocks is not None and max_ctx > win:
-            fb = getattr(self, "_cur_fb", None)
-            if self.window_fa and fb is not None and not packed and \
-                    (self.prefill_fa_f8 if self._kv_fp8 else self._attn_fa):
-                op = ops.attention_fa_window_f8 if self._kv_fp8 else ops.attention_fa_window
-                return op(qkv, kc, vc, table, q_seq, q_ctx, fb, self.nh, self.nkv, self.scale, win, out=out,
-                          workspace=ws, max_ctx=max_ctx, waves=getattr(self, "_cur_fw", 4))
-            return ops.paged_attention(qkv, kc, vc, table, q_seq, q_ctx, self.nh, self.nkv, self.scale, out=out,
-                                       workspace=ws, part_size=ps, num_parts=np_, packed=packed,
-                                       window=win, max_ctx=max_ctx)
-        if qblocks is None and self.gqa_decode_mfma_f8 and self.device.type == "cuda":
-            ps2 = 128 * math.ceil(ps / 128)
-            np2 = max(1, math.ceil(ps * np_ / ps2))
-            return ops.attention_mfma_f8(qkv, kc, vc, table, q_seq, q_ctx, self.decode_qblocks(qkv.shape[0]), self.nh,
-                                         self.nkv, self.scale, out=out, workspace=ws, part_size=ps2, num_parts=np2,
-                                         packed=packed, window=win, max_ctx=max_ctx)
-        fb = getattr(self, "_cur_fb", None)
-        if self.prefill_fa_f8 and qblocks is not None and fb is not None and not packed:
-            return ops.attention_fa_f8(qkv, kc, vc, table, q_seq, q_ctx, fb, self.nh, self.nkv, self.scale, out=out,
-                                       workspace=ws, max_ctx=max_ctx, waves=getattr(self, "_cur_fw", 4))
-        if self._kv_fp8:
-            return ops.paged_attention(qkv, kc, vc, table, q_seq, q_ctx, self.nh, self.nkv, self.scale, out=out,
-                                       workspace=ws, part_size=ps, num_parts=np_, packed=packed,
-                                       window=win, max_ctx=max_ctx)
-        if qblocks is None and self.gqa_decode_mfma and self.device.type == "cuda":
-            T = qkv.shape[0]
-            ps2 = 128 * math.ceil(ps / 128)
-            np2 = max(1, math.ceil(ps * np_ / ps2))
-            return ops.attention_mfma(qkv, kc, vc, table, q_seq, q_ctx, self.decode_qblocks(T), self.nh, self.nkv,
-                                      self.scale, out=out, workspace=ws, part_size=ps2, num_parts=np2,
-                                      packed=packed, window=win, max_ctx=max_ctx)
-        if qblocks is not None and fb is not None and not packed:
-            return ops.attention_fa(qkv, kc, vc, table, q_seq, q_ctx, fb, self.nh, self.nkv, self.scale, out=out,
-                                    workspace=ws, max_ctx=max_ctx, waves=getattr(self, "_cur_fw", 4))
-        if qblocks is not None:
+        if win and prefill and max_ctx > win:
+            if self.window_fa and fa and (self.prefill_fa_f8 if f8 else self._attn_fa):
+                op = ops.attention_fa_window_f8 if f8 else ops.attention_fa_window
+                return op(qkv, kc, vc, table, q_seq, q_ctx, self._cur_fb, self.nh, self.nkv, self.scale, win, out=out,
+                          workspace=ws, max_ctx=max_ctx, waves=self._cur_fw)
+            return flash()
+        if not prefill and (self.gqa_decode_mfma_f8 if f8 else self.gqa_decode_mfma) and self.device.type == "cuda":
+            ps2, np2 = self._parts128(ps, np_)
+            op = ops.attention_mfma_f8 if f8 else ops.attention_mfma
+            return op(qkv, kc, vc, table, q_seq, q_ctx, self.decode_qblocks(qkv.shape[0]), self.nh, self.nkv,
+                      self.scale, out=out, workspace=ws, part_size=ps2, num_parts=np2, packed=packed, window=win,
+                      max_ctx=max_ctx)
+        if fa and (self.prefill_fa_f8 or not f8):
+            op = ops.attention_fa_f8 if f8 else ops.attention_fa
+            return op(qkv, kc, vc, table, q_seq, q_ctx, self._cur_fb, self.nh, self.nkv, self.scale, out=out,
+                      workspace=ws, max_ctx=max_ctx, waves=self._cur_fw)
+        if prefill and not f8:
             return ops.attention_mfma(qkv, kc, vc, table, q_seq, q_ctx, qblocks, self.nh, self.nkv, self.scale,
                                       out=out, workspace=ws, max_ctx=max_ctx, packed=packed,
-                                      superblocks=getattr(self, "_cur_sb", None))
-        return ops.paged_attention(qkv, kc, vc, table, q_seq, q_ctx, self.nh, self.nkv, self.scale, out=out,
-                                   workspace=ws, part_size=ps, num_parts=np_, packed=packed,
-                                   window=win, max_ctx=max_ctx)
+                                      superblocks=self._cur_sb)
+        return flash()
+
+    @staticmethod
+    def _parts128(ps: int, np_: int):
+        """The step's context slices re-cut for the MFMA kernel: a multiple of 128 tokens each."""
+        ps2 = 128 * math.ceil(ps / 128)
+        return ps2, max(1, math.ceil(ps * np_ / ps2))
 
     def _qkv_fold(self, T: int) -> bool:
         """Decode steps of T rows: qkv as split-K partial slabs folded into the attention kernel's
@@ -651,32 +645,23 @@ class StageExecutor:
         ``qkv_part``: q / k / v as the qkv GEMM's split-K slabs (decode RoPE paths only).  ``mx_out``:
         (ax, as_) MX buffers the GQA kernel writes instead of ``out`` when it can (one part, packed,
         head_dim 128); it then appends True to ``mx_used``."""
-        if decode and qblocks is None and self._fuse_rope and self.gqa_decode_mfma and not self._kv_fp8 and \
-                self.device.type == "cuda":
-            T = qkv.shape[0]
-            ps2 = 128 * math.ceil(ps / 128)
-            np2 = max(1, math.ceil(ps * np_ / ps2))
-            mx = mx_out if (mx_out is not None and np2 == 1 and packed and self.D == 128) else None
-            if mx is not None and mx_used is not None:
-                mx_used.append(True)
-            return ops.attention_mfma_rope(qkv, kc, vc, self.sessions.table_dev, q_seq, q_ctx, self.decode_qblocks(T),
-                                           positions, self.cos, self.sin, slots, self.nh, self.nkv, self.scale,
-                                           out=out, workspace=ws, part_size=ps2, num_parts=np2, packed=packed,
-                                           qkv_part=qkv_part, mx_out=mx, window=self.window, max_ctx=max_ctx)
-        if decode and qblocks is None and self._fuse_rope and self.gqa_decode_mfma_f8 and self.device.type == "cuda":
-            ps2 = 128 * math.ceil(ps / 128)
-            np2 = max(1, math.ceil(ps * np_ / ps2))
-            return ops.attention_mfma_rope_f8(qkv, kc, vc, self.sessions.table_dev, q_seq, q_ctx,
-                                              self.decode_qblocks(qkv.shape[0]), positions, self.cos, self.sin, slots,
-                                              self.nh, self.nkv, self.scale, out=out, workspace=ws, part_size=ps2,
-                                              num_parts=np2, packed=packed, qkv_part=qkv_part, window=self.window,
-                                              max_ctx=max_ctx)
-        if decode and qblocks is None and self._fuse_rope and not (
-                self.gqa_decode_mfma and not self._kv_fp8 and self.device.type == "cuda"):
-            return ops.paged_attention_rope(qkv, kc, vc, self.sessions.table_dev, q_seq, q_ctx, positions, self.cos,
-                                            self.sin, slots, self.nh, self.nkv, self.scale, out=out, workspace=ws,
-                                            part_size=ps, num_parts=np_, packed=packed, qkv_part=qkv_part,
-                                            window=self.window, max_ctx=max_ctx)
+        if decode and qblocks is None and self._fuse_rope:
+            f8, table = self._kv_fp8, self.sessions.table_dev
+            if (self.gqa_decode_mfma_f8 if f8 else self.gqa_decode_mfma) and self.device.type == "cuda":
+                ps2, np2 = self._parts128(ps, np_)
+                kw = {}
+                if not f8:  # (an fp8 cache has no MX epilogue)
+                    kw["mx_out"] = mx_out if (mx_out is not None and np2 == 1 and packed and self.D == 128) else None
+                    if kw["mx_out"] is not None and mx_used is not None:
+                        mx_used.append(True)
+                op = ops.attention_mfma_rope_f8 if f8 else ops.attention_mfma_rope
+                return op(qkv, kc, vc, table, q_seq, q_ctx, self.decode_qblocks(qkv.shape[0]), positions, self.cos,
+                          self.sin, slots, self.nh, self.nkv, self.scale, out=out, workspace=ws, part_size=ps2,
+                          num_parts=np2, packed=packed, qkv_part=qkv_part, window=self.window, max_ctx=max_ctx, **kw)
+            return ops.paged_attention_rope(qkv, kc, vc, table, q_seq, q_ctx, positions, self.cos, self.sin, slots,
+                                            self.nh, self.nkv, self.scale, out=out, workspace=ws, part_size=ps,
+                                            num_parts=np_, packed=packed, qkv_part=qkv_part, window=self.window,
+                                            max_ctx=max_ctx)
         if qkv_part is not None:
             raise RuntimeError("qkv partial slabs need a fused RoPE decode attention path")
         ops.rope_kv_write(qkv, positions, self.cos, self.sin, kc, vc, slots, self.nh, self.nkv)

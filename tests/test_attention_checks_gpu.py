@@ -3,6 +3,7 @@
 ``paged_attention_rope``, ``paged_attention_rope_f8``, ``attention_mfma``, ``attention_mfma_rope`` and
 ``attention_fa`` rejects one bad argument at a time with the message the op has always raised, before any
 kernel is launched; one valid call per op gives the bits (and the cache writes) of its ``ops.*`` wrapper.
+An ``_f8`` entry is the fp8-cache form of its base torch op: the same op with ``k_scale`` / ``v_scale``.
 
 The shape is the smallest one all three kernels and the fp8 cache accept: 2 decode tokens with contexts
 5 and 9, 4 query heads on 2 kv heads, head_dim 128, 64-token pages, one page per sequence out of a pool
@@ -50,6 +51,11 @@ MX_OUT = "mx output: packed, one part, D 128, as_"
 @pytest.fixture(scope="module", autouse=True)
 def _native():
     ops.require_native()
+
+
+def _torch_op(op):
+    """The torch op of a table entry: an ``_f8`` entry is its base op called with ``k_scale`` / ``v_scale``."""
+    return getattr(torch.ops.mpamd, op.removesuffix("_f8"))
 
 
 def _bf(*shape):
@@ -285,11 +291,55 @@ def _bad_cases(op):
 
 @pytest.mark.parametrize("op", ALL_OPS)
 def test_one_bad_argument_is_rejected_with_its_message(op):
-    fn = getattr(torch.ops.mpamd, op)
+    fn = _torch_op(op)
     a = _args(op)
     for msg, change in _bad_cases(op):
         with pytest.raises(RuntimeError, match=re.escape("mpamd: " + msg) + r"(\n|$)"):
             fn(**(a | change))
+
+
+def _f8_args(op):
+    """``_args(op)`` of an MFMA op on the fp8 cache of the same data."""
+    a = _args(op)
+    kf, vf = ops.KVF8.from_dense(a["k_cache"]), ops.KVF8.from_dense(a["v_cache"])
+    return a | dict(k_cache=kf.codes, v_cache=vf.codes, k_scale=kf.scales, v_scale=vf.scales)
+
+
+ONE_SCALE = "fp8 KV cache: k_scale and v_scale are given together (neither: a bf16 cache)"
+F8_SUPERBLOCKS = "attention_mfma on an fp8 KV cache has no grouped prefill form: superblocks must be None"
+F8_MX_OUT = "attention_mfma on an fp8 KV cache has no MX output: mx_ax must be None"
+
+
+def _scale_cases(rule):
+    """(op, message, arguments) of the rules the trailing ``k_scale`` / ``v_scale`` bring."""
+    if rule == "one_scale":  # on every merged op, from its fp8 call and from its bf16 call
+        cases = []
+        for op in F8_OPS:
+            a = _args(op)
+            cases += [(op, ONE_SCALE, a | dict(k_scale=None)), (op, ONE_SCALE, a | dict(v_scale=None))]
+        for op in ("attention_mfma", "attention_mfma_rope", "attention_fa"):
+            a = _args(op)
+            s = ops.KVF8.from_dense(a["k_cache"]).scales
+            cases += [(op, ONE_SCALE, a | dict(k_scale=s)), (op, ONE_SCALE, a | dict(v_scale=s))]
+        return cases
+    if rule == "superblocks":
+        sb = _i32(ops.query_superblocks([1] * T, NH // NKV))
+        return [("attention_mfma", F8_SUPERBLOCKS, _f8_args("attention_mfma") | dict(superblocks=sb))]
+    W = NH * 128
+    mx = dict(packed=1, out=_bf(ops.packed_numel(T, W)), mx_ax=_u8(16 * W), mx_as=_u8(2 * W))
+    return [("attention_mfma_rope", F8_MX_OUT, _f8_args("attention_mfma_rope") | mx)]
+
+
+@pytest.mark.parametrize("rule", ["one_scale", "superblocks", "mx_ax"])
+def test_scale_arguments_refuse_what_no_kernel_form_covers(rule):
+    """One scale tensor without the other, and the two MFMA forms a bf16 cache alone has - superblocks
+    and the MX output - with scales: raised before any launch (the zeroed output stays zero)."""
+    for op, msg, a in _scale_cases(rule):
+        with pytest.raises(RuntimeError, match=re.escape("mpamd: " + msg) + r"(\n|$)"):
+            _torch_op(op)(**a)
+        if "out" in a:
+            torch.cuda.synchronize()
+            assert not bool(a["out"].any())
 
 
 # ----------------------------------------------------------------------------------------- valid calls
@@ -316,7 +366,7 @@ def _same_writes(a, b):
 def test_rope_kv_write_valid_call_equals_wrapper(op):
     base = _args(op)
     a, b = _cloned(base), _cloned(base)
-    getattr(torch.ops.mpamd, op)(**a)
+    _torch_op(op)(**a)
     ops.rope_kv_write(b["qkv"], b["positions"], b["cos"], b["sin"], *_caches(b), b["slots"], NH, NKV)
     assert _same_writes(a, b)
     assert not torch.equal(a["k_cache"], base["k_cache"]) and not torch.equal(a["qkv"], base["qkv"])
@@ -334,7 +384,7 @@ def test_kv_write_valid_call_equals_wrapper():
 @pytest.mark.parametrize("op", ["paged_attention", "paged_attention_f8"])
 def test_paged_attention_valid_call_equals_wrapper(op):
     a = _args(op)
-    getattr(torch.ops.mpamd, op)(**a)
+    _torch_op(op)(**a)
     want = ops.paged_attention(a["q"], *_caches(a), a["block_tables"], a["q_seq"], a["q_ctx"], NH, NKV, a["scale"],
                                part_size=PART, num_parts=NPARTS)
     assert torch.equal(a["out"], want) and bool(a["out"].any())
@@ -344,7 +394,7 @@ def test_paged_attention_valid_call_equals_wrapper(op):
 def test_paged_attention_rope_valid_call_equals_wrapper(op):
     base = _args(op)
     a, b = _cloned(base), _cloned(base)
-    getattr(torch.ops.mpamd, op)(**a)
+    _torch_op(op)(**a)
     want = ops.paged_attention_rope(b["qkv"], *_caches(b), b["block_tables"], b["q_seq"], b["q_ctx"], b["positions"],
                                     b["cos"], b["sin"], b["slots"], NH, NKV, b["scale"], part_size=PART,
                                     num_parts=NPARTS)

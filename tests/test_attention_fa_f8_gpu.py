@@ -152,7 +152,8 @@ def test_the_fa_f8_binding_refuses_what_the_kernel_does_not_cover():
     ws = ops.attention_workspace(T, nh, D, 1, DEV)
 
     def call(k, v, ks, vs, fb_=fb, waves=4, q_=q, out_=out):
-        torch.ops.mpamd.attention_fa_f8(q_, k, v, ks, vs, bt, q_seq, q_ctx, fb_, out_, ws, nh, nkv, 1.0, 384, 1, waves, 0)
+        torch.ops.mpamd.attention_fa(q_, k, v, bt, q_seq, q_ctx, fb_, out_, ws, nh, nkv, 1.0, 384, 1, waves, 0,
+                                     k_scale=ks, v_scale=vs)
 
     call(kf.codes, vf.codes, kf.scales, vf.scales)  # the accepted form
     with pytest.raises(RuntimeError, match="uint8"):  # bf16 caches

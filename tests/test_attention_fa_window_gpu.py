@@ -108,7 +108,7 @@ def test_the_window_binding_refuses_what_it_does_not_cover():
     with pytest.raises(RuntimeError, match="waves"):
         torch.ops.mpamd.attention_fa_window(*args[:-2], 5, 0, W)
     with pytest.raises(RuntimeError, match="uint8"):
-        torch.ops.mpamd.attention_fa_window_f8(a["q"], a["k_cache"], a["v_cache"], kf.scales, vf.scales, *args[3:], W)
+        torch.ops.mpamd.attention_fa_window(*args, W, k_scale=kf.scales, v_scale=vf.scales)
     with pytest.raises(ValueError, match="cover"):
         ops.attention_fa_window(a["q"], a["k_cache"], a["v_cache"], *_meta(a), fb, nh, nkv, case.scale, W, waves=4,
                                 part_size=64, num_parts=1, max_ctx=int(case.q_ctx.max()))

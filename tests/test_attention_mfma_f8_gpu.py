@@ -301,11 +301,11 @@ def test_the_f8_bindings_refuse_what_the_kernel_does_not_cover():
     m = torch.ops.mpamd
 
     def plain(k, v, ks, vs, qb_=qb, nkv_=nkv):
-        m.attention_mfma_f8(q, k, v, ks, vs, bt, q_seq, q_ctx, qb_, out, ws, nh, nkv_, 1.0, 128, 1, 0)
+        m.attention_mfma(q, k, v, bt, q_seq, q_ctx, qb_, out, ws, nh, nkv_, 1.0, 128, 1, 0, k_scale=ks, v_scale=vs)
 
     def rope(k, v, ks, vs, qb_=qb, nkv_=nkv):
-        m.attention_mfma_rope_f8(q, k, v, ks, vs, bt, q_seq, q_ctx, qb_, pos, cos, sin, slots, out, ws, nh, nkv_, 1.0,
-                                 128, 1, 0)
+        m.attention_mfma_rope(q, k, v, bt, q_seq, q_ctx, qb_, pos, cos, sin, slots, out, ws, nh, nkv_, 1.0,
+                              128, 1, 0, k_scale=ks, v_scale=vs)
 
     half = kf.scales[:, :, :32].contiguous()
     for call in (plain, rope):

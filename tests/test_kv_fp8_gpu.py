@@ -259,9 +259,9 @@ def test_mfma_and_fa_attention_reject_an_fp8_cache():
         torch.ops.mpamd.attention_mfma(q, kf.codes, vf.codes, bt, q_seq, q_ctx, qb, out, ws, nh, nkv, 1.0, 128, 1, 0,
                                        None)
     with pytest.raises(RuntimeError, match="scales"):  # scales of another page_size
-        torch.ops.mpamd.paged_attention_f8(q, kf.codes, vf.codes, kf.scales[:, :, :32].contiguous(),
-                                           vf.scales[:, :, :32].contiguous(), bt, q_seq, q_ctx, out, ws, nh, nkv,
-                                           1.0, 64, 1, 0, None)
+        torch.ops.mpamd.paged_attention(q, kf.codes, vf.codes, bt, q_seq, q_ctx, out, ws, nh, nkv, 1.0, 64, 1, 0, None,
+                                        k_scale=kf.scales[:, :, :32].contiguous(),
+                                        v_scale=vf.scales[:, :, :32].contiguous())
 
 
 # ----------------------------------------------------------------------------------------- executor
