@@ -591,7 +591,25 @@ void sample(const at::Tensor& logits, const at::Tensor& temps, const at::Tensor&
                "sample");
 }
 
-// flags bit 0: x is packed (holds ceil(M/16)*16*K elements, M given); bit 1: packed SwiGLU output
+// The decode GEMM arguments every gemm* op shares, after its checks (the caller sets x_stride, wsc,
+// as, gate where it has them)
+static mp::GemmArgs gemm_args(const void* x, const void* w, void* y, int64_t y_stride, const void* res,
+                              int64_t res_stride, int M, int N, int K, int64_t epilogue, int64_t flags, void* ws,
+                              void* ap, const c10::optional<at::Tensor>& ss_out,
+                              const c10::optional<at::Tensor>& ss_zero, const c10::optional<at::Tensor>& ss_in,
+                              double inv_k, double eps) {
+  mp::GemmArgs a{};
+  a.x = x, a.w = w, a.y = y, a.y_stride = y_stride, a.res = res, a.res_stride = res_stride;
+  a.M = M, a.N = N, a.K = K, a.epilogue = (int)epilogue, a.flags = (int)flags;
+  a.ws = ws, a.ap = ap;
+  a.ss_out = opt_ss(ss_out, "ss_out");
+  a.ss_zero = opt_ss(ss_zero, "ss_zero");
+  a.ss_in = opt_ss(ss_in, "ss_in");
+  a.inv_k = (float)inv_k, a.eps = (float)eps;
+  return a;
+}
+
+// flags (mp::GemmFlags): GEMM_A_PACKED: x holds ceil(M/16)*16*K elements, M given
 void gemm(const at::Tensor& x, const at::Tensor& wp, at::Tensor& y, const c10::optional<at::Tensor>& residual,
           int64_t epilogue, int64_t M_, int64_t flags, const c10::optional<at::Tensor>& workspace,
           const c10::optional<at::Tensor>& gate, const c10::optional<at::Tensor>& ap,
@@ -603,7 +621,7 @@ void gemm(const at::Tensor& x, const at::Tensor& wp, at::Tensor& y, const c10::o
   MP_CHECK(wp.dim() == 4 && wp.size(2) == 64 && wp.size(3) == 8 && wp.is_contiguous(),
            "wp must be a packed weight [N/16, K/32, 64, 8] (ops.pack_weight)");
   const int N = 16 * wp.size(0), K = 32 * wp.size(1);
-  const bool apk = flags & 1, opk = flags & 2;
+  const bool apk = flags & mp::GEMM_A_PACKED, opk = flags & mp::GEMM_OUT_PACKED;
   int M;
   if (apk) {
     M = (int)M_;
@@ -618,20 +636,16 @@ void gemm(const at::Tensor& x, const at::Tensor& wp, at::Tensor& y, const c10::o
   MP_CHECK(epilogue < 2 || rp != nullptr, "residual epilogue needs residual");
   MP_CHECK(epilogue >= 0 && epilogue <= 3, "epilogue");
   void* app = opt_packed(ap, M, N);
-  void* sso = opt_ss(ss_out, "ss_out");
-  void* ssz = opt_ss(ss_zero, "ss_zero");
-  const void* ssi = opt_ss(ss_in, "ss_in");
+  mp::GemmArgs a = gemm_args(x.data_ptr(), wp.data_ptr(), y.data_ptr(), opk ? 0 : y.stride(0), rp, rs, M, N, K, epilogue,
+                             flags, nullptr, app, ss_out, ss_zero, ss_in, inv_k, eps);
+  a.x_stride = apk ? 0 : x.stride(0);
   MP_CHECK(epilogue != 3 || (app != nullptr && !opk), "epilogue 3 needs ap (and ss_out outside ablations)");
-  void* ws = opt_workspace(workspace);
-  const int* gp = nullptr;
+  a.ws = opt_workspace(workspace);
   if (gate.has_value()) {  // MoE expert gate: one int32 on the device (0 -> the GEMM is skipped)
     MP_CHECK(gate->is_cuda() && gate->scalar_type() == at::kInt && gate->numel() == 1, "gate must be one cuda int32");
-    gp = gate->data_ptr<int>();
+    a.gate = gate->data_ptr<int>();
   }
-  check_launch(mp_gemm_bf16(x.data_ptr(), apk ? 0 : x.stride(0), wp.data_ptr(), y.data_ptr(), opk ? 0 : y.stride(0),
-                            rp, rs, M, N, K, (int)epilogue, (int)flags, ws, gp, app, sso, ssz, ssi, (float)inv_k,
-                            (float)eps, cur_stream()),
-               "gemm");
+  check_launch(mp_gemm_bf16(&a, cur_stream()), "gemm");
 }
 
 void pack_act(const at::Tensor& x, at::Tensor& ap) {
@@ -652,8 +666,7 @@ at::Tensor pack_weight(const at::Tensor& w) {
 }
 
 // W8A16 decode GEMM (gemm.hip mp_gemm_w8): packed bf16 x (M rows), fp8 weight Wq uint8
-// [N/16, K/32, 64, 8] + per-column fp32 scales; flags as mp_gemm_w8 (bit 1 packed SwiGLU out,
-// bit 7 ring, bit 8 split-K ring)
+// [N/16, K/32, 64, 8] + per-column fp32 scales; flags as mp_gemm_w8
 void gemm_w8(const at::Tensor& x, const at::Tensor& wq, const at::Tensor& wsc, at::Tensor& y,
              const c10::optional<at::Tensor>& residual, int64_t epilogue, int64_t M_, int64_t flags,
              const c10::optional<at::Tensor>& workspace, const c10::optional<at::Tensor>& ap,
@@ -663,7 +676,7 @@ void gemm_w8(const at::Tensor& x, const at::Tensor& wq, const at::Tensor& wsc, a
   check_bf16_cuda(y, "y");
   const auto [N, K] = check_w8_weight(wq, wsc);
   const int M = (int)M_;
-  const bool opk = flags & 2;
+  const bool opk = flags & mp::GEMM_OUT_PACKED;
   MP_CHECK(M >= 0 && M <= 64, "gemm_w8: 0 <= M <= 64");
   MP_CHECK(x.is_contiguous() && x.numel() >= packed_numel(M, K), "packed x too small");
   check_gemm_out(y, M, N, epilogue, opk);
@@ -672,9 +685,10 @@ void gemm_w8(const at::Tensor& x, const at::Tensor& wq, const at::Tensor& wsc, a
   void* app = opt_packed(ap, M, N);
   MP_CHECK(epilogue != 3 || (app != nullptr && rp != nullptr), "epilogue 3 needs residual and ap");
   void* ws = opt_workspace(workspace);
-  const int rc = mp_gemm_w8(x.data_ptr(), wq.data_ptr(), wsc.data_ptr<float>(), y.data_ptr(), opk ? 0 : y.stride(0),
-                            rp, rs, M, N, K, (int)epilogue, (int)flags, ws, app, opt_ss(ss_out, "ss_out"),
-                            opt_ss(ss_zero, "ss_zero"), opt_ss(ss_in, "ss_in"), (float)inv_k, (float)eps, cur_stream());
+  mp::GemmArgs a = gemm_args(x.data_ptr(), wq.data_ptr(), y.data_ptr(), opk ? 0 : y.stride(0), rp, rs, M, N, K, epilogue,
+                             flags, ws, app, ss_out, ss_zero, ss_in, inv_k, eps);
+  a.wsc = wsc.data_ptr<float>();
+  const int rc = mp_gemm_w8(&a, cur_stream());
   TORCH_CHECK(rc != 1, "mpamd: gemm_w8: no fp8-weight kernel covers M=", M, " N=", N, " K=", K, " epilogue=",
               epilogue);
   check_launch(rc, "gemm_w8");
@@ -760,8 +774,8 @@ static void check_w4(const at::Tensor& w4, const at::Tensor& s4) {
            "s4 must be the e8m0 block scales uint8 [N/16, K/128, 16, 4] (ops.pack_weight_w4)");
 }
 
-// W4A16 decode GEMM (gemm_w4.hip mp_gemm_w4): packed bf16 x (M rows), MXFP4 weight; flags bit 1 =
-// packed SwiGLU output
+// W4A16 decode GEMM (gemm_w4.hip mp_gemm_w4): packed bf16 x (M rows), MXFP4 weight; flags:
+// GEMM_OUT_PACKED = packed SwiGLU output
 void gemm_w4(const at::Tensor& x, const at::Tensor& w4, const at::Tensor& s4, at::Tensor& y,
              const c10::optional<at::Tensor>& residual, int64_t epilogue, int64_t M_, int64_t flags,
              const c10::optional<at::Tensor>& ap, const c10::optional<at::Tensor>& ss_out,
@@ -772,7 +786,7 @@ void gemm_w4(const at::Tensor& x, const at::Tensor& w4, const at::Tensor& s4, at
   check_w4(w4, s4);
   const int N = 16 * w4.size(0), K = 128 * w4.size(1);
   const int M = (int)M_;
-  const bool opk = flags & 2;
+  const bool opk = flags & mp::GEMM_OUT_PACKED;
   MP_CHECK(M >= 0 && M <= 64, "gemm_w4: 0 <= M <= 64");
   MP_CHECK(x.is_contiguous() && x.numel() >= packed_numel(M, K), "packed x too small");
   MP_CHECK(epilogue == 0 || epilogue == 3 || (epilogue == 1 && opk), "gemm_w4: epilogue 0, 3 or packed SwiGLU");
@@ -781,9 +795,10 @@ void gemm_w4(const at::Tensor& x, const at::Tensor& w4, const at::Tensor& s4, at
   const auto [rp, rs] = opt_rows(residual, "residual", M, N);
   void* app = opt_packed(ap, M, N);
   MP_CHECK(epilogue != 3 || (app != nullptr && rp != nullptr), "epilogue 3 needs residual and ap");
-  const int rc = mp_gemm_w4(x.data_ptr(), w4.data_ptr(), s4.data_ptr(), y.data_ptr(), opk ? 0 : y.stride(0), rp, rs, M,
-                            N, K, (int)epilogue, (int)flags, app, opt_ss(ss_out, "ss_out"), opt_ss(ss_zero, "ss_zero"),
-                            opt_ss(ss_in, "ss_in"), (float)inv_k, (float)eps, cur_stream());
+  mp::GemmArgs a = gemm_args(x.data_ptr(), w4.data_ptr(), y.data_ptr(), opk ? 0 : y.stride(0), rp, rs, M, N, K, epilogue,
+                             flags, nullptr, app, ss_out, ss_zero, ss_in, inv_k, eps);
+  a.wsc = s4.data_ptr();
+  const int rc = mp_gemm_w4(&a, cur_stream());
   TORCH_CHECK(rc != 1, "mpamd: gemm_w4: no MXFP4-weight kernel covers M=", M, " N=", N, " K=", K, " epilogue=",
               epilogue);
   check_launch(rc, "gemm_w4");
@@ -846,8 +861,8 @@ void quant_mx(const at::Tensor& ap, at::Tensor& ax, at::Tensor& as, int64_t M, i
 }
 
 // W8A8-MX decode GEMM (gemm_mx.hip): ax / as from quant_mx, fp8 weight in the W8A16 layout + column
-// scales; epilogue 0 (optional ss_in row scale) or 3; flags bit 10 rotated k walk, bit 14 partial
-// slabs only (y unused, the slabs stay in the workspace)
+// scales; epilogue 0 (optional ss_in row scale) or 3; flags: GEMM_ROT_K, GEMM_PARTIALS (y unused,
+// the slabs stay in the workspace)
 void gemm_mx(const at::Tensor& ax, const at::Tensor& as, const at::Tensor& wq, const at::Tensor& wsc, at::Tensor& y,
              const c10::optional<at::Tensor>& residual, int64_t epilogue, int64_t M_, int64_t flags,
              const at::Tensor& workspace, const c10::optional<at::Tensor>& ap,
@@ -860,7 +875,7 @@ void gemm_mx(const at::Tensor& ax, const at::Tensor& as, const at::Tensor& wq, c
   MP_CHECK(ax.is_cuda() && ax.scalar_type() == at::kByte && ax.is_contiguous() && ax.numel() >= rows * K, "ax size");
   MP_CHECK(as.is_cuda() && as.scalar_type() == at::kByte && as.is_contiguous() && as.numel() >= 2 * K, "as size");
   MP_CHECK(epilogue == 0 || epilogue == 3, "gemm_mx: epilogue 0 or 3");
-  const bool partial = flags & 16384;
+  const bool partial = flags & mp::GEMM_PARTIALS;
   if (!partial) {
     check_bf16_cuda(y, "y");
     check_gemm_out(y, M, N, epilogue, false);
@@ -869,10 +884,11 @@ void gemm_mx(const at::Tensor& ax, const at::Tensor& as, const at::Tensor& wq, c
   void* app = opt_packed(ap, M, N);
   MP_CHECK(epilogue != 3 || (app != nullptr && rp != nullptr), "epilogue 3 needs residual and ap");
   void* ws = opt_workspace(workspace);
-  const int rc = mp_gemm_mx(ax.data_ptr(), as.data_ptr(), wq.data_ptr(), wsc.data_ptr<float>(),
-                            partial ? nullptr : y.data_ptr(), partial ? 0 : y.stride(0), rp, rs, M, N, K,
-                            (int)epilogue, (int)flags, ws, app, opt_ss(ss_out, "ss_out"),
-                            opt_ss(ss_zero, "ss_zero"), opt_ss(ss_in, "ss_in"), (float)inv_k, (float)eps, cur_stream());
+  mp::GemmArgs a = gemm_args(ax.data_ptr(), wq.data_ptr(), partial ? nullptr : y.data_ptr(), partial ? 0 : y.stride(0),
+                             rp, rs, M, N, K, epilogue, flags, ws, app, ss_out, ss_zero, ss_in, inv_k, eps);
+  a.wsc = wsc.data_ptr<float>();
+  a.as = as.data_ptr();
+  const int rc = mp_gemm_mx(&a, cur_stream());
   TORCH_CHECK(rc != 1, "mpamd: gemm_mx: no split-K geometry for M=", M, " N=", N, " K=", K);
   check_launch(rc, "gemm_mx");
 }

@@ -30,7 +30,7 @@ extern "C" int mp_gemm_ss_elems() { return mp::SS_NSH * mp::SS_ROWS; }
 extern "C" int64_t mp_gemm_slab_offset() { return mp::RWK_SLAB_OFFSET; }
 extern "C" int64_t mp_gemm_slab_bytes() { return mp::RWK_SLAB_BYTES; }
 
-// Split count S of the split-K ring form for this shape (0: not covered): with flags bit 14 the
+// Split count S of the split-K ring form for this shape (0: not covered): with GEMM_PARTIALS the
 // GEMM leaves S fp32 partial slabs [S][M][N] at mp_gemm_slab_offset() of the workspace for a
 // consumer that sums them (fixed order s = 0..S-1 from zero: the reduce launch's bits).
 extern "C" int mp_gemm_rwk_split(int M, int N, int K, int f8) {
@@ -49,77 +49,51 @@ extern "C" int mp_gemm_rwk_split(int M, int N, int K, int f8) {
 
 extern "C" int64_t mp_gemm_workspace_bytes() { return mp::RWK_SLAB_OFFSET + mp::RWK_SLAB_BYTES; }
 
-// flags: bit 0 = x is packed (Ap[K/32][ceil(M/16)][64][8]); bit 1 = SwiGLU output packed;
-//        bit 2 = use the stream-K kernel (needs ws: mp_gemm_workspace_bytes(), zero-initialised,
-//        used by one stream at a time); bit 3 = force the one-group-per-workgroup kernel;
-//        bit 4 = shared-A (LDS-staged activation) kernel when the shape allows it;
-//        bit 7 = balanced ring kernel; bit 8 = split-K ring kernel + reduce launch (epilogue
-//        0 / 2 / 3, needs ws); bits 8 + 9 = split-K ring kernel with the in-launch combine;
-//        bit 10 = rotated k walk per workgroup (EpiArgs::rot); bits 8 + 11 = split-K ring with
-//        the symmetric in-launch combine; bit 12 = row-split ring (epilogue 0 / 2 / 3, even row
-//        tiles), + bit 13 = its weights loaded with the default cache policy.
-//        epilogue 3 / ss_in: the fused-norm decode path (EpiArgs above; ap / ss_out / ss_zero /
-//        ss_in may be null when unused).
-extern "C" int mp_gemm_bf16(const void* x, int64_t x_stride, const void* w, void* y, int64_t y_stride,
-                            const void* res, int64_t res_stride, int M, int N, int K, int epilogue, int flags,
-                            void* ws, const int* gate, void* ap, void* ss_out, void* ss_zero, const void* ss_in,
-                            float inv_k, float eps, hipStream_t stream) {
+// bf16 weights, M <= 256 rows (flags: GemmFlags, mp_api.h).  The forms are tried in this order; one
+// that does not cover the shape hands on to the next, the one-group kernel covers what is left.
+extern "C" int mp_gemm_bf16(const mp::GemmArgs* args, hipStream_t stream) {
   (void)hipGetLastError();  // an earlier non-mpamd HIP call's stale error is not this launch's
   using namespace mp;
+  const GemmArgs& a = *args;
+  const int M = a.M;
+  int flags = a.flags, rc;
   if (M == 0) return 0;
-  if (epilogue == 3 && (ap == nullptr || res == nullptr)) return -5;
-  EpiArgs ep{(bf16_t*)ap, (u64*)ss_out, (u64*)ss_zero, (const u64*)ss_in, inv_k, eps, (M + 15) / 16};
-  ep.rot = (flags >> 10) & 1;
-  if (M > 256 || K % (32 * GU_MAX) || N % 16 || ((flags & 1) == 0 && x_stride % 8)) return -1;
-  int rc;
+  if (a.epilogue == 3 && (a.ap == nullptr || a.res == nullptr)) return -5;
+  const EpiArgs ep = gemm_epi(a);
+  if (M > 256 || a.K % (32 * GU_MAX) || a.N % 16 || (!(flags & GEMM_A_PACKED) && a.x_stride % 8)) return -1;
   if (M > 64) {  // 65..256 rows: gemm_wide.hip (split-K ring / balanced ring, packed A, no gate)
-    if (!(flags & 1) || gate != nullptr) return -1;
-    return mp_gemm_bf16_wide(x, w, y, y_stride, res, res_stride, M, N, K, epilogue, flags, ws, ep, stream);
+    if (!(flags & GEMM_A_PACKED) || a.gate != nullptr) return -1;
+    return mp_gemm_bf16_wide(args, ep, stream);
   }
-  if ((flags & 1) && (flags & 4096) && !(flags & 2) && gate == nullptr) {  // row-split ring
+  const bool apk = flags & GEMM_A_PACKED, plain = !(flags & GEMM_OUT_PACKED) && a.gate == nullptr;
+  if (apk && (flags & GEMM_ROW_SPLIT) && plain) {  // row-split ring
     switch ((M + 15) / 16) {
-      case 2: rc = launch_gemm_rwr<2>(x, w, y, y_stride, res, res_stride, M, N, K, epilogue, flags, ep, stream); break;
-      case 4: rc = launch_gemm_rwr<4>(x, w, y, y_stride, res, res_stride, M, N, K, epilogue, flags, ep, stream); break;
+      case 2: rc = launch_gemm_rwr<2>(a, ep, stream); break;
+      case 4: rc = launch_gemm_rwr<4>(a, ep, stream); break;
       default: rc = 1; break;
     }
-    if (rc < 0) return rc;
-    if (rc == 0) return (int)hipGetLastError();
+    if (gemm_form_done(rc)) return rc;
   }
-  if ((flags & 1) && (flags & 256) && !(flags & 2) && gate == nullptr && ws != nullptr) {  // split-K ring
-    rc = with_row_tiles(M, [&](auto mt) {
-      return launch_gemm_rwk<mt()>(x, w, y, y_stride, res, res_stride, M, N, K, epilogue, ep, ws, stream,
-                                   rwk_comb(flags));
-    });
-    if (rc < 0) return rc;
-    if (rc == 0) return (int)hipGetLastError();
+  if (apk && (flags & GEMM_SPLITK) && plain && a.ws != nullptr) {  // split-K ring
+    rc = with_row_tiles(M, [&](auto mt) { return launch_gemm_rwk<mt()>(a, ep, stream, rwk_comb(flags)); });
+    if (gemm_form_done(rc)) return rc;
   }
-  if (flags & 16384) return -6;  // partials only: nothing else writes them
-  if (gate != nullptr) flags &= ~(4 | 16 | 128);  // gated (MoE expert) GEMMs use the one-group kernel
-  if ((flags & 1) && (flags & 128) && !(flags & 8)) {  // balanced ring kernel
-    rc = with_row_tiles(M, [&](auto mt) {
-      return launch_gemm_rw<mt()>(x, w, y, y_stride, res, res_stride, M, N, K, epilogue, flags, ep, stream);
-    });
-    if (rc < 0) return rc;
-    if (rc == 0) return (int)hipGetLastError();
+  if (flags & GEMM_PARTIALS) return -6;  // partials only: nothing else writes them
+  // gated (MoE expert) GEMMs use the one-group kernel
+  if (a.gate != nullptr) flags &= ~(GEMM_STREAM_K | GEMM_SHARED_A | GEMM_RING);
+  if (apk && (flags & GEMM_RING) && !(flags & GEMM_ONE_GROUP)) {  // balanced ring kernel
+    rc = with_row_tiles(M, [&](auto mt) { return launch_gemm_rw<mt()>(a, ep, stream); });
+    if (gemm_form_done(rc)) return rc;
   }
-  if ((flags & 1) && (flags & 16) && !(flags & 8)) {  // shared-A kernel
-    rc = with_row_tiles(M, [&](auto mt) {
-      return launch_gemm_lds<mt()>(x, w, y, y_stride, res, res_stride, M, N, K, epilogue, flags, ep, stream);
-    });
-    if (rc < 0) return rc;
-    if (rc == 0) return (int)hipGetLastError();
+  if (apk && (flags & GEMM_SHARED_A) && !(flags & GEMM_ONE_GROUP)) {  // shared-A kernel
+    rc = with_row_tiles(M, [&](auto mt) { return launch_gemm_lds<mt()>(a, ep, stream); });
+    if (gemm_form_done(rc)) return rc;
   }
-  if ((flags & 1) && (flags & 4) && !(flags & 8) && ws != nullptr) {
-    rc = with_row_tiles(M, [&](auto mt) {
-      return launch_gemm_sk<mt()>(x, y, y_stride, w, res, res_stride, M, N, K, epilogue, flags, ws, ep, stream);
-    });
-    if (rc < 0) return rc;
-    if (rc == 0) return (int)hipGetLastError();
-    // rc == 1: shape not covered by the stream-K form -> one-group-per-workgroup kernel
+  if (apk && (flags & GEMM_STREAM_K) && !(flags & GEMM_ONE_GROUP) && a.ws != nullptr) {  // stream-K
+    rc = with_row_tiles(M, [&](auto mt) { return launch_gemm_sk<mt()>(a, ep, stream); });
+    if (gemm_form_done(rc)) return rc;
   }
-  rc = with_row_tiles(M, [&](auto mt) {
-    return launch_gemm<mt()>(x, x_stride, w, y, y_stride, res, res_stride, M, N, K, epilogue, flags, gate, ep, stream);
-  });
+  rc = with_row_tiles(M, [&](auto mt) { return launch_gemm<mt()>(a, ep, stream); });
   if (rc) return rc;
   return (int)hipGetLastError();
 }

@@ -95,9 +95,44 @@ struct EpiArgs {
   float eps;
   int mt_out;
   const float* wsc;    // fp8 weights (W8A16 kernels): per-output-column dequantization scales
-  int rot = 0;         // rotate each workgroup's k walk (rw_krot; flags bit 10, chosen per shape)
+  int rot = 0;         // rotate each workgroup's k walk (rw_krot; GEMM_ROT_K, chosen per shape)
   const uint8_t* xsc = nullptr;  // MX activations (gemm_mx.hip): e8m0 block scales [K/128][MT][64]
 };
+
+// The kernels' epilogue arguments of a launch (a dry run's GemmArgs gives null pointers + mt_out).
+inline EpiArgs gemm_epi(const GemmArgs& a) {
+  EpiArgs ep{(bf16_t*)a.ap, (u64*)a.ss_out, (u64*)a.ss_zero, (const u64*)a.ss_in, a.inv_k, a.eps, (a.M + 15) / 16};
+  ep.wsc = (const float*)a.wsc;
+  ep.rot = (a.flags & GEMM_ROT_K) != 0;
+  ep.xsc = (const uint8_t*)a.as;
+  return ep;
+}
+
+// The entry points try their forms in a fixed order; a launcher returns 0 (launched), 1 (the form
+// does not cover the shape: try the next) or < 0 (bad call).  True when ``rc`` ends the cascade; it
+// then holds the entry point's return value: the negative code, or the launch's HIP error.
+inline bool gemm_form_done(int& rc) {
+  if (rc > 0) return false;
+  if (rc == 0) rc = (int)hipGetLastError();
+  return true;
+}
+
+// The run-time (epilogue, packed output) pair as compile-time constants, for the forms that build
+// epilogues 0 / 2 / 3 with row-major output and SwiGLU (1) with either output:
+// fn(integral_constant<int, EPI>, bool_constant<OPK>) for those five pairs, -3 for any other packed
+// output (only SwiGLU packs: it feeds the down projection).  A form that builds fewer pairs keeps
+// its own ladder.
+template <class Fn>
+static inline int with_epilogue(int epi, bool opk, Fn&& fn) {
+  using std::integral_constant;
+  constexpr std::true_type packed{};
+  constexpr std::false_type rows{};
+  if (epi == 1) return opk ? fn(integral_constant<int, 1>{}, packed) : fn(integral_constant<int, 1>{}, rows);
+  if (opk) return -3;
+  if (epi == 2) return fn(integral_constant<int, 2>{}, rows);
+  if (epi == 3) return fn(integral_constant<int, 3>{}, rows);
+  return fn(integral_constant<int, 0>{}, rows);
+}
 
 // fp8 (OCP e4m3) weight fragment -> bf16 MFMA B operand (exact: every e4m3 value is a bf16
 // value): the W8A16 form of the ring kernels streams 1 byte per weight and keeps bf16
@@ -227,7 +262,7 @@ __device__ __forceinline__ f32x4 mfma16(const u16x8& a, const u16x8& b, const f3
 // per-workgroup offset spreads the 256 concurrent A streams over the whole block (L2 channels)
 // instead of one moving 16 KB window.  A bijection on the slices: every slice is still summed
 // exactly once (the accumulation order per column group changes, deterministically).
-// Per launch (EpiArgs::rot, flags bit 10) and chosen per shape by the start-up autotuners: it
+// Per launch (EpiArgs::rot, GEMM_ROT_K) and chosen per shape by the start-up autotuners: it
 // helped the Llama-2-7B and 70B fp8 shapes (profiles/r3_r, r3_s: 64 sessions 4.36 -> 4.32 ms, 70B
 // 17.8 -> 17.3-17.4) and cost 2.4 % on Llama-3-8B's (r3_t), whose lock-step readers share L2 lines
 // that a spread-out walk lets the weight stream evict.  -DMP_RW_ROT=0 compiles it out.
@@ -397,37 +432,29 @@ __global__ __launch_bounds__(512) void gemm_packed_kernel(const bf16_t* __restri
 }
 
 template <int MT>
-static int launch_gemm(const void* x, int64_t xs, const void* w, void* y, int64_t ys, const void* res, int64_t rs,
-                       int M, int N, int K, int epi, int flags, const int* gate, const EpiArgs& ep,
-                       hipStream_t stream) {
-  const int ntiles = N / 16;
+static int launch_gemm(const GemmArgs& a, const EpiArgs& ep, hipStream_t stream) {
+  const int ntiles = a.N / 16, epi = a.epilogue;
   // two column tiles per wave when there are enough workgroups to fill the 256 CUs
   const bool two = epi == 1 || (ntiles % 2 == 0 && ntiles / 2 >= 256);
-  const bool apk = flags & 1, opk = flags & 2;
+  const bool apk = a.flags & GEMM_A_PACKED, opk = a.flags & GEMM_OUT_PACKED;
 #define MP_LAUNCH(NT_, EPI_, APK_, OPK_)                                                                       \
   hipLaunchKernelGGL((gemm_packed_kernel<MT, NT_, EPI_, APK_, OPK_>), dim3(ntiles / NT_), dim3(512), 0, stream, \
-                     (const bf16_t*)x, xs, (const bf16_t*)w, (bf16_t*)y, ys, (const bf16_t*)res, rs, M, N, K, \
-                     gate, ep)
+                     (const bf16_t*)a.x, a.x_stride, (const bf16_t*)a.w, (bf16_t*)a.y, a.y_stride,              \
+                     (const bf16_t*)a.res, a.res_stride, a.M, a.N, a.K, a.gate, ep)
   // Only the packed-activation form is instantiated: row-major callers pack x first
   // (mp_pack_act).  The row-major-A variant miscompiled at MT=1/NT=1 (ROCm 7.2, wrong
   // results with several k-groups per wave) and loses to the packed form anyway.
   if (!apk) return -4;
-#define MP_APK(NT_, EPI_, OPK_) MP_LAUNCH(NT_, EPI_, true, OPK_);
-  if (epi == 1) {
-    if (ntiles % 2) return -2;
-    if (opk) { MP_APK(2, 1, true) } else { MP_APK(2, 1, false) }
-  } else if (opk) {
-    return -3;  // packed output only for the SwiGLU epilogue (it feeds the down projection)
-  } else if (epi == 2) {
-    if (two) { MP_APK(2, 2, false) } else { MP_APK(1, 2, false) }
-  } else if (epi == 3) {
-    if (two) { MP_APK(2, 3, false) } else { MP_APK(1, 3, false) }
-  } else {
-    if (two) { MP_APK(2, 0, false) } else { MP_APK(1, 0, false) }
-  }
-#undef MP_APK
+  return with_epilogue(epi, opk, [&](auto e, auto o) {
+    if constexpr (e() == 1) {
+      if (ntiles % 2) return -2;
+      MP_LAUNCH(2, 1, true, o());
+    } else {
+      if (two) MP_LAUNCH(2, e(), true, false); else MP_LAUNCH(1, e(), true, false);
+    }
+    return 0;
+  });
 #undef MP_LAUNCH
-  return 0;
 }
 
 // ---------------------------------------------------------------------------------------
@@ -641,46 +668,38 @@ __global__ __launch_bounds__(512) void gemm_lds_kernel(const bf16_t* __restrict_
 }
 
 template <int MT, int NT, int CH>
-static int launch_gemm_lds_cfg(const void* x, const void* w, void* y, int64_t ys, const void* res, int64_t rs, int M,
-                               int N, int K, int epi, int flags, const EpiArgs& ep, hipStream_t stream) {
+static int launch_gemm_lds_cfg(const GemmArgs& a, const EpiArgs& ep, hipStream_t stream) {
   if constexpr ((2 * MT) % CH != 0) {
     return 1;  // the A group does not split evenly over the column waves
   } else {
-    const int ntiles = N / 16;
-    const bool opk = flags & 2;
-    if (ntiles % (CH * NT) || K % 64) return 1;
-    if (opk && epi != 1) return -3;
+    const int ntiles = a.N / 16, epi = a.epilogue;
+    const bool opk = a.flags & GEMM_OUT_PACKED;
+    if (ntiles % (CH * NT) || a.K % 64) return 1;
     const dim3 grid(ntiles / (CH * NT));
 #define MP_LL(EPI_, OPK_)                                                                                      \
-  hipLaunchKernelGGL((gemm_lds_kernel<MT, NT, CH, EPI_, OPK_>), grid, dim3(512), 0, stream, (const bf16_t*)x,   \
-                     (const bf16_t*)w, (bf16_t*)y, ys, (const bf16_t*)res, rs, M, N, K, ep)
-    if (epi == 1) {
-      if constexpr (NT % 2 == 0) {  // gate/up tile pairs must sit in one wave
-        if (opk) { MP_LL(1, true); } else { MP_LL(1, false); }
+  hipLaunchKernelGGL((gemm_lds_kernel<MT, NT, CH, EPI_, OPK_>), grid, dim3(512), 0, stream, (const bf16_t*)a.x, \
+                     (const bf16_t*)a.w, (bf16_t*)a.y, a.y_stride, (const bf16_t*)a.res, a.res_stride, a.M, a.N, \
+                     a.K, ep)
+    return with_epilogue(epi, opk, [&](auto e, auto o) {
+      if constexpr (e() == 1 && NT % 2 != 0) {
+        return 1;  // gate/up tile pairs must sit in one wave
       } else {
-        return 1;
+        MP_LL(e(), o());
+        return 0;
       }
-    } else if (epi == 2) {
-      MP_LL(2, false);
-    } else if (epi == 3) {
-      MP_LL(3, false);
-    } else {
-      MP_LL(0, false);
-    }
+    });
 #undef MP_LL
-    return 0;
   }
 }
 
-// flags bits 5-6 pick (NT, CH): 0 = (2, 2), 1 = (2, 4), 2 = (1, 4), 3 = (4, 2)
+// GEMM_SHARED_A_CFG picks (NT, CH)
 template <int MT>
-static int launch_gemm_lds(const void* x, const void* w, void* y, int64_t ys, const void* res, int64_t rs, int M,
-                           int N, int K, int epi, int flags, const EpiArgs& ep, hipStream_t stream) {
-  switch ((flags >> 5) & 3) {
-    case 1: return launch_gemm_lds_cfg<MT, 2, 4>(x, w, y, ys, res, rs, M, N, K, epi, flags, ep, stream);
-    case 2: return launch_gemm_lds_cfg<MT, 1, 4>(x, w, y, ys, res, rs, M, N, K, epi, flags, ep, stream);
-    case 3: return launch_gemm_lds_cfg<MT, 4, 2>(x, w, y, ys, res, rs, M, N, K, epi, flags, ep, stream);
-    default: return launch_gemm_lds_cfg<MT, 2, 2>(x, w, y, ys, res, rs, M, N, K, epi, flags, ep, stream);
+static int launch_gemm_lds(const GemmArgs& a, const EpiArgs& ep, hipStream_t stream) {
+  switch (gemm_shared_a_cfg(a.flags)) {
+    case 1: return launch_gemm_lds_cfg<MT, 2, 4>(a, ep, stream);
+    case 2: return launch_gemm_lds_cfg<MT, 1, 4>(a, ep, stream);
+    case 3: return launch_gemm_lds_cfg<MT, 4, 2>(a, ep, stream);
+    default: return launch_gemm_lds_cfg<MT, 2, 2>(a, ep, stream);
   }
 }
 
@@ -909,40 +928,31 @@ static int sk_num_cus() {
 }
 
 template <int MT, int NT, int D>
-static int launch_gemm_sk_cfg(const void* x, void* y, int64_t ys, const void* w, const void* res, int64_t rs, int M,
-                              int N, int K, int epi, int flags, void* ws, int G, const EpiArgs& ep,
-                              hipStream_t stream) {
-  const int nks = K / 32;
-  const int ngrp = (N / 16) / NT;
-  if ((N / 16) % NT || nks % 8 || nks < 8 * D || ngrp > SK_MAX_GROUPS) return 1;  // caller falls back
+static int launch_gemm_sk_cfg(const GemmArgs& a, const EpiArgs& ep, hipStream_t stream, int G) {
+  const int nks = a.K / 32, epi = a.epilogue;
+  const int ngrp = (a.N / 16) / NT;
+  if ((a.N / 16) % NT || nks % 8 || nks < 8 * D || ngrp > SK_MAX_GROUPS) return 1;  // caller falls back
   const int U = ngrp * nks;
   if (G > SK_MAX_BLOCKS) G = SK_MAX_BLOCKS;
   if (G > U) G = U;
   // EPI 3 keeps its epilogue out of the ring loop, which needs every range <= one group
   if (epi == 3 && (U + G - 1) / G > nks) return 1;
-  int* cnt = (int*)ws;  // [SK_MAX_GROUPS] counters, [SK_ZERO_BYTES] zeros, slabs
-  f32x4* slab = (f32x4*)((char*)ws + SK_MAX_GROUPS * sizeof(int) + SK_ZERO_BYTES);
-  const bool opk = flags & 2;
+  int* cnt = (int*)a.ws;  // [SK_MAX_GROUPS] counters, [SK_ZERO_BYTES] zeros, slabs
+  f32x4* slab = (f32x4*)((char*)a.ws + SK_MAX_GROUPS * sizeof(int) + SK_ZERO_BYTES);
+  const bool opk = a.flags & GEMM_OUT_PACKED;
 #define MP_SK(EPI_, OPK_)                                                                                         \
-  hipLaunchKernelGGL((gemm_sk_kernel<MT, NT, D, EPI_, OPK_>), dim3(G), dim3(512), 0, stream, (const bf16_t*)x,     \
-                     (const bf16_t*)w, (bf16_t*)y, ys, (const bf16_t*)res, rs, M, N, K, cnt, slab, 1, ep)
-  if (epi == 1) {
-    if constexpr (NT % 2 == 0) {
-      if (opk) { MP_SK(1, true); } else { MP_SK(1, false); }
-    } else {
+  hipLaunchKernelGGL((gemm_sk_kernel<MT, NT, D, EPI_, OPK_>), dim3(G), dim3(512), 0, stream, (const bf16_t*)a.x,   \
+                     (const bf16_t*)a.w, (bf16_t*)a.y, a.y_stride, (const bf16_t*)a.res, a.res_stride, a.M, a.N,   \
+                     a.K, cnt, slab, 1, ep)
+  return with_epilogue(epi, opk, [&](auto e, auto o) {
+    if constexpr (e() == 1 && NT % 2 != 0) {
       return 1;
+    } else {
+      MP_SK(e(), o());
+      return 0;
     }
-  } else if (opk) {
-    return -3;
-  } else if (epi == 2) {
-    MP_SK(2, false);
-  } else if (epi == 3) {
-    MP_SK(3, false);
-  } else {
-    MP_SK(0, false);
-  }
+  });
 #undef MP_SK
-  return 0;
 }
 
 // Largest grid G in [0.9 C, C] that divides the group count (every workgroup then owns whole
@@ -957,19 +967,16 @@ static int sk_whole_grid(int ngrp, int C) {
 // group count splits evenly over ~all CUs (no split groups); otherwise NT = 4 on every CU with
 // split groups (deferred sc1 hand-off).
 template <int MT>
-static int launch_gemm_sk(const void* x, void* y, int64_t ys, const void* w, const void* res, int64_t rs, int M, int N,
-                          int K, int epi, int flags, void* ws, const EpiArgs& ep, hipStream_t stream) {
+static int launch_gemm_sk(const GemmArgs& a, const EpiArgs& ep, hipStream_t stream) {
   // ring depth 4 (3 when MT x NT >= 16: the 256-VGPR cap)
   constexpr int DW = (MT * 4 >= 16) ? 3 : 4, D3 = (MT * 3 >= 16) ? 3 : 4;
-  const int C = sk_num_cus(), nt = N / 16;
+  const int C = sk_num_cus(), nt = a.N / 16;
   int G;
-  if (nt % 4 == 0 && (G = sk_whole_grid(nt / 4, C)))
-    return launch_gemm_sk_cfg<MT, 4, DW>(x, y, ys, w, res, rs, M, N, K, epi, flags, ws, G, ep, stream);
-  if (epi != 1 && nt % 3 == 0 && (G = sk_whole_grid(nt / 3, C)))
-    return launch_gemm_sk_cfg<MT, 3, D3>(x, y, ys, w, res, rs, M, N, K, epi, flags, ws, G, ep, stream);
-  if (nt % 2 == 0 && (G = sk_whole_grid(nt / 2, C)))
-    return launch_gemm_sk_cfg<MT, 2, 4>(x, y, ys, w, res, rs, M, N, K, epi, flags, ws, G, ep, stream);
-  return launch_gemm_sk_cfg<MT, 4, DW>(x, y, ys, w, res, rs, M, N, K, epi, flags, ws, C, ep, stream);
+  if (nt % 4 == 0 && (G = sk_whole_grid(nt / 4, C))) return launch_gemm_sk_cfg<MT, 4, DW>(a, ep, stream, G);
+  if (a.epilogue != 1 && nt % 3 == 0 && (G = sk_whole_grid(nt / 3, C)))
+    return launch_gemm_sk_cfg<MT, 3, D3>(a, ep, stream, G);
+  if (nt % 2 == 0 && (G = sk_whole_grid(nt / 2, C))) return launch_gemm_sk_cfg<MT, 2, 4>(a, ep, stream, G);
+  return launch_gemm_sk_cfg<MT, 4, DW>(a, ep, stream, C);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1165,9 +1172,14 @@ __global__ __launch_bounds__(RW_WAVES * 64) void gemm_rw_kernel(const bf16_t* __
 }
 
 template <int MT, int NTB, int NTS, bool F8 = false>
-static int launch_gemm_rw_cfg(const void* x, const void* w, void* y, int64_t ys, const void* res, int64_t rs, int M,
-                              int K, int epi, bool opk, int G, int n_big, const EpiArgs& ep, hipStream_t stream,
-                              bool dry) {
+static int launch_gemm_rw_cfg(const GemmArgs& a, const EpiArgs& ep, hipStream_t stream, int G, int n_big, bool dry) {
+  const int epi = a.epilogue;
+  const bool opk = a.flags & GEMM_OUT_PACKED;
+  // every instantiation takes the same kernel arguments
+#define MP_RW(EPI_, OPK_)                                                                                          \
+  hipLaunchKernelGGL((gemm_rw_kernel<MT, NTB, NTS, EPI_, OPK_, F8>), dim3(G), dim3(RW_WAVES * 64), 0, stream,      \
+                     (const bf16_t*)a.x, (const bf16_t*)a.w, (bf16_t*)a.y, a.y_stride, (const bf16_t*)a.res,       \
+                     a.res_stride, a.M, a.K, n_big, ep)
   if constexpr (F8) {
     // fp8-weight (W8A16) forms, M <= 64: the fused-norm decode epilogues (0 with row scale,
     // packed SwiGLU, residual-stream producer)
@@ -1177,15 +1189,11 @@ static int launch_gemm_rw_cfg(const void* x, const void* w, void* y, int64_t ys,
       if (!(epi == 0 || epi == 3 || (epi == 1 && opk)) || (epi == 1 && (NTB % 2 || NTS % 2))) return 1;
       if (dry) return 0;
       if (epi == 1) {
-        if constexpr (NTB % 2 == 0 && NTS % 2 == 0)
-          hipLaunchKernelGGL((gemm_rw_kernel<MT, NTB, NTS, 1, true, true>), dim3(G), dim3(RW_WAVES * 64), 0, stream,
-                             (const bf16_t*)x, (const bf16_t*)w, (bf16_t*)y, ys, (const bf16_t*)res, rs, M, K, n_big, ep);
+        if constexpr (NTB % 2 == 0 && NTS % 2 == 0) MP_RW(1, true);
       } else if (epi == 3) {
-        hipLaunchKernelGGL((gemm_rw_kernel<MT, NTB, NTS, 3, false, true>), dim3(G), dim3(RW_WAVES * 64), 0, stream,
-                           (const bf16_t*)x, (const bf16_t*)w, (bf16_t*)y, ys, (const bf16_t*)res, rs, M, K, n_big, ep);
+        MP_RW(3, false);
       } else {
-        hipLaunchKernelGGL((gemm_rw_kernel<MT, NTB, NTS, 0, false, true>), dim3(G), dim3(RW_WAVES * 64), 0, stream,
-                           (const bf16_t*)x, (const bf16_t*)w, (bf16_t*)y, ys, (const bf16_t*)res, rs, M, K, n_big, ep);
+        MP_RW(0, false);
       }
       return 0;
     }
@@ -1198,49 +1206,35 @@ static int launch_gemm_rw_cfg(const void* x, const void* w, void* y, int64_t ys,
       if (!(epi == 0 || (epi == 1 && opk)) || (epi == 1 && (NTB % 2 || NTS % 2))) return 1;
       if (dry) return 0;
       if (epi == 1) {
-        if constexpr (NTB % 2 == 0 && NTS % 2 == 0)
-          hipLaunchKernelGGL((gemm_rw_kernel<MT, NTB, NTS, 1, true>), dim3(G), dim3(RW_WAVES * 64), 0, stream, (const bf16_t*)x,
-                             (const bf16_t*)w, (bf16_t*)y, ys, (const bf16_t*)res, rs, M, K, n_big, ep);
+        if constexpr (NTB % 2 == 0 && NTS % 2 == 0) MP_RW(1, true);
       } else {
-        hipLaunchKernelGGL((gemm_rw_kernel<MT, NTB, NTS, 0, false>), dim3(G), dim3(RW_WAVES * 64), 0, stream, (const bf16_t*)x,
-                           (const bf16_t*)w, (bf16_t*)y, ys, (const bf16_t*)res, rs, M, K, n_big, ep);
+        MP_RW(0, false);
       }
       return 0;
     }
   } else {
-  if (epi == 1 && (NTB % 2 || NTS % 2)) return 1;
-  if (dry) return 0;
-#define MP_RW(EPI_, OPK_)                                                                                          \
-  hipLaunchKernelGGL((gemm_rw_kernel<MT, NTB, NTS, EPI_, OPK_>), dim3(G), dim3(RW_WAVES * 64), 0, stream, (const bf16_t*)x, \
-                     (const bf16_t*)w, (bf16_t*)y, ys, (const bf16_t*)res, rs, M, K, n_big, ep)
-  if (epi == 1) {
-    if constexpr (NTB % 2 == 0 && NTS % 2 == 0) {
-      if (opk) { MP_RW(1, true); } else { MP_RW(1, false); }
-    } else {
-      return 1;
-    }
-  } else if (opk) {
-    return -3;
-  } else if (epi == 2) {
-    MP_RW(2, false);
-  } else if (epi == 3) {
-    MP_RW(3, false);
-  } else {
-    MP_RW(0, false);
+    if (epi == 1 && (NTB % 2 || NTS % 2)) return 1;
+    if (dry) return 0;
+    return with_epilogue(epi, opk, [&](auto e, auto o) {
+      if constexpr (e() == 1 && (NTB % 2 || NTS % 2)) {
+        return 1;
+      } else {
+        MP_RW(e(), o());
+        return 0;
+      }
+    });
   }
 #undef MP_RW
-  return 0;
-  }
 }
 
 // Split the column units (tiles, or gate/up tile pairs) over G = min(#CUs, units) workgroups:
 // n_big of them take ceil, the rest floor.  Returns 1 (caller falls back) for widths not built.
 template <int MT, bool F8 = false>
-static int launch_gemm_rw(const void* x, const void* w, void* y, int64_t ys, const void* res, int64_t rs, int M,
-                          int N, int K, int epi, int flags, const EpiArgs& ep, hipStream_t stream, bool dry = false) {
+static int launch_gemm_rw(const GemmArgs& a, const EpiArgs& ep, hipStream_t stream, bool dry = false) {
+  const int epi = a.epilogue;
   const int step = epi == 1 ? 2 : 1;
-  const int units = (N / 16) / step;
-  if ((N / 16) % step || units == 0) return 1;
+  const int units = (a.N / 16) / step;
+  if ((a.N / 16) % step || units == 0) return 1;
   int G = units < sk_num_cus() ? units : sk_num_cus();
   if constexpr (MT > 8) {
     // 129..256 rows: at most 64 / MT column tiles per workgroup (256 accumulator AGPRs), so wide
@@ -1251,9 +1245,7 @@ static int launch_gemm_rw(const void* x, const void* w, void* y, int64_t ys, con
   const int base = units / G, rem = units % G;
   const int ntb = (base + (rem ? 1 : 0)) * step;
   const int n_big = rem ? rem : G;
-  const bool opk = flags & 2;
-#define MP_RWC(B_, S_) \
-  return launch_gemm_rw_cfg<MT, B_, S_, F8>(x, w, y, ys, res, rs, M, K, epi, opk, G, n_big, ep, stream, dry)
+#define MP_RWC(B_, S_) return launch_gemm_rw_cfg<MT, B_, S_, F8>(a, ep, stream, G, n_big, dry)
   if (epi == 1) {
     switch (ntb) {
       case 2: if (rem) return 1; MP_RWC(2, 2);
@@ -1307,25 +1299,21 @@ __global__ __launch_bounds__(RW_WAVES * 64) void gemm_rwr_kernel(const bf16_t* _
 // Grid = 2 x (tiles / NT) = #CUs (a multiple of 16); epilogues 0 / 2 / 3, MT even.  Returns 1
 // (caller falls back) when the shape does not split that way.
 template <int MT>
-static int launch_gemm_rwr(const void* x, const void* w, void* y, int64_t ys, const void* res, int64_t rs, int M,
-                           int N, int K, int epi, int flags, const EpiArgs& ep, hipStream_t stream) {
+static int launch_gemm_rwr(const GemmArgs& a, const EpiArgs& ep, hipStream_t stream) {
   if constexpr (MT % 2 != 0) {
     return 1;
   } else {
     constexpr int MTH = MT / 2;
-    const int tiles = N / 16, C0 = sk_num_cus();
-    if (epi == 1 || (flags & 2) || C0 % 16 || (2 * tiles) % C0) return 1;
+    const int tiles = a.N / 16, C0 = sk_num_cus(), epi = a.epilogue;
+    if (epi == 1 || (a.flags & GEMM_OUT_PACKED) || C0 % 16 || (2 * tiles) % C0) return 1;
     const int nt = 2 * tiles / C0;
-    const bool ntw = !(flags & 8192);
-#define MP_RWR(NT_, EPI_)                                                                                          \
-  {                                                                                                                \
-    if (ntw)                                                                                                       \
-      hipLaunchKernelGGL((gemm_rwr_kernel<MTH, NT_, EPI_, true>), dim3(C0), dim3(RW_WAVES * 64), 0, stream,       \
-                         (const bf16_t*)x, (const bf16_t*)w, (bf16_t*)y, ys, (const bf16_t*)res, rs, M, K, ep);    \
-    else                                                                                                           \
-      hipLaunchKernelGGL((gemm_rwr_kernel<MTH, NT_, EPI_, false>), dim3(C0), dim3(RW_WAVES * 64), 0, stream,      \
-                         (const bf16_t*)x, (const bf16_t*)w, (bf16_t*)y, ys, (const bf16_t*)res, rs, M, K, ep);    \
-  }
+    const bool ntw = !(a.flags & GEMM_ROW_SPLIT_DEFAULT_CACHE);
+#define MP_RWR_W(NT_, EPI_, NTW_)                                                                                  \
+  hipLaunchKernelGGL((gemm_rwr_kernel<MTH, NT_, EPI_, NTW_>), dim3(C0), dim3(RW_WAVES * 64), 0, stream,            \
+                     (const bf16_t*)a.x, (const bf16_t*)a.w, (bf16_t*)a.y, a.y_stride, (const bf16_t*)a.res,       \
+                     a.res_stride, a.M, a.K, ep)
+#define MP_RWR(NT_, EPI_) \
+  { if (ntw) MP_RWR_W(NT_, EPI_, true); else MP_RWR_W(NT_, EPI_, false); }
 #define MP_RWR_E(NT_) \
   { if (epi == 3) MP_RWR(NT_, 3) else if (epi == 2) MP_RWR(NT_, 2) else MP_RWR(NT_, 0) }
     switch (nt) {
@@ -1336,6 +1324,7 @@ static int launch_gemm_rwr(const void* x, const void* w, void* y, int64_t ys, co
     }
 #undef MP_RWR_E
 #undef MP_RWR
+#undef MP_RWR_W
     return 0;
   }
 }
@@ -1675,15 +1664,13 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
 
 // The split count is a template parameter of the reduce (all S slab loads issued back to back).
 template <int EPI>
-static void launch_splitk_reduce_e(int S, dim3 g2, hipStream_t stream, const float* part, int M, int N, void* y,
-                                   int64_t ys, const void* res, int64_t rs, const EpiArgs& ep) {
-#define MP_SKR(S_)                                                                                          \
-  if (N <= MP_SKR_WT_MAXN)                                                                                  \
-    hipLaunchKernelGGL((splitk_reduce_kernel<EPI, S_, true>), g2, dim3(256), 0, stream, part, M, N, (bf16_t*)y, \
-                       ys, (const bf16_t*)res, rs, ep);                                                     \
-  else                                                                                                      \
-    hipLaunchKernelGGL((splitk_reduce_kernel<EPI, S_, false>), g2, dim3(256), 0, stream, part, M, N,          \
-                       (bf16_t*)y, ys, (const bf16_t*)res, rs, ep)
+static void launch_splitk_reduce_e(const GemmArgs& a, const EpiArgs& ep, hipStream_t stream, const float* part, int S) {
+  const dim3 g2(a.N / (256 * SKR_CPT), a.M);
+#define MP_SKR_W(S_, WT_)                                                                                       \
+  hipLaunchKernelGGL((splitk_reduce_kernel<EPI, S_, WT_>), g2, dim3(256), 0, stream, part, a.M, a.N, (bf16_t*)a.y, \
+                     a.y_stride, (const bf16_t*)a.res, a.res_stride, ep)
+#define MP_SKR(S_) \
+  if (a.N <= MP_SKR_WT_MAXN) MP_SKR_W(S_, true); else MP_SKR_W(S_, false)
   switch (S) {
     case 2: MP_SKR(2); break;
     case 3: MP_SKR(3); break;
@@ -1694,13 +1681,15 @@ static void launch_splitk_reduce_e(int S, dim3 g2, hipStream_t stream, const flo
     default: MP_SKR(8); break;
   }
 #undef MP_SKR
+#undef MP_SKR_W
 }
 
-static inline void launch_splitk_reduce(int S, int epi, dim3 g2, hipStream_t stream, const float* part, int M, int N,
-                                        void* y, int64_t ys, const void* res, int64_t rs, const EpiArgs& ep) {
-  if (epi == 3) launch_splitk_reduce_e<3>(S, g2, stream, part, M, N, y, ys, res, rs, ep);
-  else if (epi == 2) launch_splitk_reduce_e<2>(S, g2, stream, part, M, N, y, ys, res, rs, ep);
-  else launch_splitk_reduce_e<0>(S, g2, stream, part, M, N, y, ys, res, rs, ep);
+// Sum the S partial slabs at ``part`` and apply epilogue 0 / 2 / 3: the second launch of the split-K forms.
+static inline void launch_splitk_reduce(const GemmArgs& a, const EpiArgs& ep, hipStream_t stream, const float* part,
+                                        int S) {
+  if (a.epilogue == 3) launch_splitk_reduce_e<3>(a, ep, stream, part, S);
+  else if (a.epilogue == 2) launch_splitk_reduce_e<2>(a, ep, stream, part, S);
+  else launch_splitk_reduce_e<0>(a, ep, stream, part, S);
 }
 
 // Split-K ring geometry: column-group width NT and split count S (C x S <= #CUs, 2 <= S <= 8):
@@ -1757,20 +1746,20 @@ static inline int rwk_nt_max(int M) {
   return rwk_nt_max_mt(mt <= 8 ? mt : (mt <= 12 ? 12 : 16));
 }
 
-// ``comb``: 0 = reduce launch, 1 = in-launch combine by the last arriver (flags 256 = split-K ring,
-// + 512 -> comb 1), -1 = partial slabs only (flags bit 14).
+// ``comb`` of the split-K ring: 0 = reduce launch, 1 = in-launch combine by the last arriver
+// (GEMM_SPLITK_INLINE), -1 = fp32 partial slabs only, no reduce launch (GEMM_PARTIALS).
 static inline int rwk_comb(int flags) {
-  if (flags & 16384) return -1;  // bit 14: fp32 partial slabs only, no reduce launch
-  return (flags & 512) ? 1 : 0;
+  if (flags & GEMM_PARTIALS) return -1;
+  return (flags & GEMM_SPLITK_INLINE) ? 1 : 0;
 }
 
 template <int MT, bool F8 = false, bool MX = false>
-static int launch_gemm_rwk(const void* x, const void* w, void* y, int64_t ys, const void* res, int64_t rs, int M,
-                           int N, int K, int epi, const EpiArgs& ep, void* ws, hipStream_t stream,
-                           int comb = 0) {
+static int launch_gemm_rwk(const GemmArgs& a, const EpiArgs& ep, hipStream_t stream, int comb = 0) {
   const bool inl = comb > 0 && !MX;
+  const int M = a.M, N = a.N, epi = a.epilogue;
+  void* const ws = a.ws;
   if (epi == 1 || ws == nullptr || N % 2048 != 0) return 1;
-  const int tiles = N / 16, C0 = sk_num_cus(), nks = K / 32;
+  const int tiles = N / 16, C0 = sk_num_cus(), nks = a.K / 32;
   int nt = 0, S = 0;
   // accumulators: 192 AGPRs up to 128 rows, all 256 beyond (MT 9..16 -> NT <= 64 / MT)
   constexpr int nt_max = rwk_nt_max_mt(MT);
@@ -1785,8 +1774,9 @@ static int launch_gemm_rwk(const void* x, const void* w, void* y, int64_t ys, co
       (int64_t)tiles * MT * S * 1024 <= RWK_SLAB_BYTES) {
     if constexpr (MT <= 4 && !MX) {  // the MX form has no in-launch combine (inl is false there)
 #define MP_RWKI(NT_, E_)                                                                                       \
-  hipLaunchKernelGGL((gemm_rwk_kernel<MT, NT_, F8, E_>), g1, dim3(RW_WAVES * 64), 0, stream, (const bf16_t*)x,    \
-                     (const bf16_t*)w, part, M, N, K, S, ep, (bf16_t*)y, ys, (const bf16_t*)res, rs, tick)
+  hipLaunchKernelGGL((gemm_rwk_kernel<MT, NT_, F8, E_>), g1, dim3(RW_WAVES * 64), 0, stream, (const bf16_t*)a.x,  \
+                     (const bf16_t*)a.w, part, M, N, a.K, S, ep, (bf16_t*)a.y, a.y_stride, (const bf16_t*)a.res,   \
+                     a.res_stride, tick)
 #define MP_RWKI_E(NT_) \
   { if (epi == 3) MP_RWKI(NT_, 3); else if (epi == 2) MP_RWKI(NT_, 2); else MP_RWKI(NT_, 0); }
       switch (nt) {
@@ -1803,7 +1793,8 @@ static int launch_gemm_rwk(const void* x, const void* w, void* y, int64_t ys, co
 #define MP_RWKS(NT_)                                                                                           \
   if constexpr (NT_ <= nt_max)                                                                                 \
     hipLaunchKernelGGL((gemm_rwk_kernel<MT, NT_, F8, -1, MX>), g1, dim3(RW_WAVES * 64), 0, stream,             \
-                       (const bf16_t*)x, (const bf16_t*)w, part, M, N, K, S, ep, nullptr, 0, nullptr, 0, nullptr)
+                       (const bf16_t*)a.x, (const bf16_t*)a.w, part, M, N, a.K, S, ep, nullptr, 0, nullptr, 0,    \
+                       nullptr)
   switch (nt) {
     case 1: MP_RWKS(1); break;
     case 2: MP_RWKS(2); break;
@@ -1813,8 +1804,7 @@ static int launch_gemm_rwk(const void* x, const void* w, void* y, int64_t ys, co
   }
 #undef MP_RWKS
   if (comb < 0) return 0;  // partials only: the consumer sums the S slabs itself (rwk_split)
-  const dim3 g2(N / (256 * SKR_CPT), M);
-  launch_splitk_reduce(S, epi, g2, stream, part, M, N, y, ys, res, rs, ep);
+  launch_splitk_reduce(a, ep, stream, part, S);
   return 0;
 }
 

@@ -231,7 +231,7 @@ static int launch_moe_gate_up(const void* x, const void* w8, const float* wsc, c
   MoeSplit s;
   if (!moe_split(N, 1, s)) return 1;
   // the single-expert ring form must cover (and so split) the shape the same way
-  if (launch_gemm_rw<MT, true>(nullptr, nullptr, nullptr, 0, nullptr, 0, M, N, K, 1, 2, ep, stream, true) != 0) return 1;
+  if (launch_gemm_rw<MT, true>(gemm_shape_args(M, N, K, 1, GEMM_OUT_PACKED), ep, stream, true) != 0) return 1;
   if (dry) return 0;
 #define MP_MGU(B_, S_)                                                                                           \
   hipLaunchKernelGGL((moe_gate_up_kernel<MT, B_, S_>), dim3(s.G, E), dim3(RW_WAVES * 64), 0, stream,            \
@@ -255,7 +255,7 @@ static int launch_moe_down(const void* act, const void* w8, const float* wsc, co
   ep.mt_out = MT;
   MoeSplit s;
   if (!moe_split(N, 0, s)) return 1;
-  if (launch_gemm_rw<MT, true>(nullptr, nullptr, nullptr, 0, nullptr, 0, M, N, K, 0, 0, ep, stream, true) != 0) return 1;
+  if (launch_gemm_rw<MT, true>(gemm_shape_args(M, N, K, 0, 0), ep, stream, true) != 0) return 1;
   if (dry) return 0;
 #define MP_MDN(B_, S_)                                                                                           \
   hipLaunchKernelGGL((moe_down_kernel<MT, B_, S_>), dim3(s.G), dim3(RW_WAVES * 64), 0, stream,                  \

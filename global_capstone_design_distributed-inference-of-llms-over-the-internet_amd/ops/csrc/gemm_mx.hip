@@ -103,28 +103,22 @@ extern "C" int mp_quant_mx(const void* ap, void* ax, void* as, int M, int K, hip
   return (int)hipGetLastError();
 }
 
-// MX activation (mp_quant_mx) x fp8 weight (W8A16 layout + column scales), M <= 64: the split-K
-// ring kernel + reduce launch (epilogue 0 with the optional ss_in row scale, or 3), or partial
-// slabs only (flags bit 14, the qkv fold).  Returns 1 when the shape has no split-K geometry.
-extern "C" int mp_gemm_mx(const void* ax, const void* as, const void* wq, const float* wsc, void* y, int64_t y_stride,
-                          const void* res, int64_t res_stride, int M, int N, int K, int epilogue, int flags, void* ws,
-                          void* ap, void* ss_out, void* ss_zero, const void* ss_in, float inv_k, float eps,
-                          hipStream_t stream) {
+// MX activation (mp_quant_mx: a.x the e4m3 bytes, a.as the block scales) x fp8 weight (W8A16 layout +
+// column scales), M <= 64: the split-K ring kernel + reduce launch (epilogue 0 with the optional ss_in
+// row scale, or 3), or partial slabs only (GEMM_PARTIALS, the qkv fold).  Returns 1 when the shape has
+// no split-K geometry.
+extern "C" int mp_gemm_mx(const mp::GemmArgs* args, hipStream_t stream) {
   (void)hipGetLastError();
   using namespace mp;
-  if (M == 0) return 0;
-  if (M > 64 || K % 128 || N % 16 || wsc == nullptr || as == nullptr || ws == nullptr) return -1;
-  if (epilogue != 0 && epilogue != 3) return -2;
-  if (epilogue == 3 && (ap == nullptr || res == nullptr)) return -5;
-  EpiArgs ep{(bf16_t*)ap, (u64*)ss_out, (u64*)ss_zero, (const u64*)ss_in, inv_k, eps, (M + 15) / 16};
-  ep.wsc = wsc;
-  ep.rot = (flags >> 10) & 1;
-  ep.xsc = (const uint8_t*)as;
-  const int comb = (flags & 16384) ? -1 : 0;
-  const int rc = with_row_tiles(M, [&](auto mt) {
-    return launch_gemm_rwk<mt(), true, true>(ax, wq, y, y_stride, res, res_stride, M, N, K, epilogue, ep, ws, stream,
-                                             comb);
-  });
+  const GemmArgs& a = *args;
+  if (a.M == 0) return 0;
+  if (a.M > 64 || a.K % 128 || a.N % 16 || a.wsc == nullptr || a.as == nullptr || a.ws == nullptr) return -1;
+  if (a.epilogue != 0 && a.epilogue != 3) return -2;
+  if (a.epilogue == 3 && (a.ap == nullptr || a.res == nullptr)) return -5;
+  const EpiArgs ep = gemm_epi(a);
+  const int comb = (a.flags & GEMM_PARTIALS) ? -1 : 0;
+  const int rc =
+      with_row_tiles(a.M, [&](auto mt) { return launch_gemm_rwk<mt(), true, true>(a, ep, stream, comb); });
   if (rc != 0) return rc;
   return (int)hipGetLastError();
 }

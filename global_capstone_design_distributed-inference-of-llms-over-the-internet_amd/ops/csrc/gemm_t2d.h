@@ -263,13 +263,14 @@ __global__ __launch_bounds__(512) void gemm_t2d_kernel(const bf16_t* __restrict_
 // ``S_force`` > 0 forces the k split (lab); 0 picks (t2d_pick_split).
 // ``dry``: only report coverage.
 template <int MW, int NW, int WM, int WN, int D, int KU, bool GL>
-static int launch_t2d_cfg(const void* x, const void* w, void* y, int64_t ys, const void* res, int64_t rs, float* part,
-                          int M, int N, int K, int epi, bool opk, int MB, int S, int G, int nbig, int NBB, int NBS,
-                          const EpiArgs& ep, hipStream_t stream) {
+static int launch_t2d_cfg(const GemmArgs& a, const EpiArgs& ep, hipStream_t stream, float* part, int MB, int S, int G,
+                          int nbig, int NBB, int NBS) {
+  const int epi = a.epilogue;
+  const bool opk = a.flags & GEMM_OUT_PACKED;
 #define T2D_L(EPI_, OPK_, SPLIT_)                                                                                  \
   hipLaunchKernelGGL((gemm_t2d_kernel<MW, NW, WM, WN, D, KU, GL, EPI_, OPK_, SPLIT_>), dim3(G), dim3(512), 0, stream, \
-                     (const bf16_t*)x, (const bf16_t*)w, (bf16_t*)y, ys, (const bf16_t*)res, rs, part, M, N, K, MB, \
-                     S, nbig, NBB, NBS, ep)
+                     (const bf16_t*)a.x, (const bf16_t*)a.w, (bf16_t*)a.y, a.y_stride, (const bf16_t*)a.res,       \
+                     a.res_stride, part, a.M, a.N, a.K, MB, S, nbig, NBB, NBS, ep)
   if (S > 1) {
     T2D_L(0, false, true);
   } else if (epi == 1) {
@@ -300,23 +301,23 @@ static inline int t2d_pick_split(int K, int epi, bool gl, int S_force) {
   return (epi == 0 && !gl) ? 2 : 1;
 }
 
-// WM = 4 x WN = 2 waves, MW = 2 (128-row blocks); NW by the column-group width.  flags bit 18:
+// WM = 4 x WN = 2 waves, MW = 2 (128-row blocks); NW by the column-group width.  GEMM_T2D_DMA:
 // the LDS-DMA ring (2 k-slices per stage while a stage fits in 32 KB, else 1, so 4+ stages fit in
 // LDS).  (64-row blocks - a quarter of the activation intake per block for twice the weight
 // intake - measured slower on every shape, profiles/r5x, and were removed.)
-static int launch_gemm_t2d(const void* x, const void* w, void* y, int64_t ys, const void* res, int64_t rs, int M,
-                           int N, int K, int epi, int flags, const EpiArgs& ep, void* ws, hipStream_t stream,
-                           int S_force = 0, bool dry = false) {
+static int launch_gemm_t2d(const GemmArgs& a, const EpiArgs& ep, hipStream_t stream, int S_force = 0,
+                           bool dry = false) {
   constexpr int D = 4;
+  const int M = a.M, N = a.N, K = a.K, epi = a.epilogue, flags = a.flags;
   const int mto = (M + 15) / 16;
-  if (M <= 64 || M > 256 || N % 16 || K % 128 || (flags & 2 && epi != 1)) return 1;
+  if (M <= 64 || M > 256 || N % 16 || K % 128 || (flags & GEMM_OUT_PACKED && epi != 1)) return 1;
   if (!(epi == 0 || epi == 1 || epi == 3)) return 1;
   // the SwiGLU consumer (gate/up: 6-tile waves) keeps the register ring: 4 stages of 40 KB in
   // registers against the LDS-DMA ring's 5 of 20 KB, 1-4 % faster at 192 / 256 rows (profiles/r5x)
-  bool gl = (flags & 262144) && epi != 1;
+  bool gl = (flags & GEMM_T2D_DMA) && epi != 1;
   const int MB = (mto + 7) / 8;
   const int S = t2d_pick_split(K, epi, gl, S_force);
-  if (S > 1 && (epi == 1 || ws == nullptr || (int64_t)S * M * N * 4 > RWK_SLAB_BYTES || N % (256 * SKR_CPT)))
+  if (S > 1 && (epi == 1 || a.ws == nullptr || (int64_t)S * M * N * 4 > RWK_SLAB_BYTES || N % (256 * SKR_CPT)))
     return 1;
   if (K / 64 < 2 * S) return 1;
   const int step = epi == 1 ? 2 : 1;
@@ -329,10 +330,7 @@ static int launch_gemm_t2d(const void* x, const void* w, void* y, int64_t ys, co
   const int NBB = (base + (rem ? 1 : 0)) * step, NBS = base * step;
   const int nbig = rem ? rem : NB;
   const int G = NB * MB * S;
-  float* part = S > 1 ? (float*)((char*)ws + (int64_t)SK_MAX_GROUPS * sizeof(int) + SK_ZERO_BYTES +
-                                 (int64_t)SK_MAX_BLOCKS * 2 * SK_MAX_S * 64 * sizeof(float))
-                      : nullptr;
-  const bool opk = flags & 2;
+  float* part = S > 1 ? (float*)((char*)a.ws + RWK_SLAB_OFFSET) : nullptr;
   // the narrowest wave width that holds NBB tiles on 2 column waves (even for SwiGLU pairs)
   int nw = (NBB + 1) / 2;
   if (epi == 1 && nw % 2) ++nw;
@@ -341,10 +339,8 @@ static int launch_gemm_t2d(const void* x, const void* w, void* y, int64_t ys, co
 #define T2D_KU(MW_, NW_) ((4 * MW_ + 2 * NW_) * 2 <= 32 ? 2 : 1)
 #define T2D_C(NW_)                                                                                                 \
   rc = dry ? 0                                                                                                     \
-     : gl  ? launch_t2d_cfg<2, NW_, 4, 2, D, T2D_KU(2, NW_), true>(x, w, y, ys, res, rs, part, M, N, K, epi, opk,   \
-                                                                  MB, S, G, nbig, NBB, NBS, ep, stream)             \
-           : launch_t2d_cfg<2, NW_, 4, 2, D, 2, false>(x, w, y, ys, res, rs, part, M, N, K, epi, opk, MB, S, G, nbig, \
-                                                      NBB, NBS, ep, stream)
+     : gl  ? launch_t2d_cfg<2, NW_, 4, 2, D, T2D_KU(2, NW_), true>(a, ep, stream, part, MB, S, G, nbig, NBB, NBS)  \
+           : launch_t2d_cfg<2, NW_, 4, 2, D, 2, false>(a, ep, stream, part, MB, S, G, nbig, NBB, NBS)
   switch (nw) {
     case 1: if (epi == 1) return 1; T2D_C(1); break;
     case 2: T2D_C(2); break;
@@ -352,18 +348,14 @@ static int launch_gemm_t2d(const void* x, const void* w, void* y, int64_t ys, co
     case 4: T2D_C(4); break;
     case 6: T2D_C(6); break;
     case 8:
-      rc = dry ? 0 : launch_t2d_cfg<2, 8, 4, 2, D, 1, true>(x, w, y, ys, res, rs, part, M, N, K, epi, opk, MB, S, G,
-                                                           nbig, NBB, NBS, ep, stream);
+      rc = dry ? 0 : launch_t2d_cfg<2, 8, 4, 2, D, 1, true>(a, ep, stream, part, MB, S, G, nbig, NBB, NBS);
       break;
     default: return 1;
   }
 #undef T2D_C
 #undef T2D_KU
   if (rc != 0 || dry) return rc;
-  if (S > 1) {
-    const dim3 g2(N / (256 * SKR_CPT), M);
-    launch_splitk_reduce(S, epi, g2, stream, part, M, N, y, ys, res, rs, ep);
-  }
+  if (S > 1) launch_splitk_reduce(a, ep, stream, part, S);
   return 0;
 }
 

@@ -159,14 +159,13 @@ __global__ __launch_bounds__(RW_WAVES * 64) void gemm_rw4_kernel(const bf16_t* _
 
 // GU: a gate/up width (even tile counts, packed SwiGLU epilogue only); otherwise epilogues 0 / 3
 template <int MT, int NTB, int NTS, bool GU>
-static int launch_gemm_rw4_cfg(const void* x, const void* w4, const void* s4, void* y, int64_t ys, const void* res,
-                               int64_t rs, int M, int K, int epi, int G, int n_big, const EpiArgs& ep,
-                               hipStream_t stream, bool dry) {
+static int launch_gemm_rw4_cfg(const GemmArgs& a, const EpiArgs& ep, hipStream_t stream, int G, int n_big, bool dry) {
   if (dry) return 0;
+  const int epi = a.epilogue;
 #define MP_RW4(EPI_, OPK_)                                                                                     \
   hipLaunchKernelGGL((gemm_rw4_kernel<MT, NTB, NTS, EPI_, OPK_>), dim3(G), dim3(RW_WAVES * 64), 0, stream,     \
-                     (const bf16_t*)x, (const uint8_t*)w4, (const uint8_t*)s4, (bf16_t*)y, ys, (const bf16_t*)res, rs, \
-                     M, K, n_big, ep)
+                     (const bf16_t*)a.x, (const uint8_t*)a.w, (const uint8_t*)a.wsc, (bf16_t*)a.y, a.y_stride, \
+                     (const bf16_t*)a.res, a.res_stride, a.M, a.K, n_big, ep)
   if constexpr (GU) {
     static_assert(NTB % 2 == 0 && NTS % 2 == 0, "gate/up tile pairs");
     if (epi != 1) return 1;
@@ -188,9 +187,9 @@ static int launch_gemm_rw4_cfg(const void* x, const void* w4, const void* s4, vo
 // n_big take ceil, the rest floor.  G = min(#CUs, units), raised until a workgroup owns at most
 // 4 units (the widths built: up to 4 tiles, or 8 = 4 gate/up pairs).
 template <int MT>
-static int launch_gemm_rw4(const void* x, const void* w4, const void* s4, void* y, int64_t ys, const void* res,
-                           int64_t rs, int M, int N, int K, int epi, bool opk, const EpiArgs& ep, hipStream_t stream,
-                           bool dry = false) {
+static int launch_gemm_rw4(const GemmArgs& a, const EpiArgs& ep, hipStream_t stream, bool dry = false) {
+  const int epi = a.epilogue, N = a.N;
+  const bool opk = a.flags & GEMM_OUT_PACKED;
   if (!(epi == 0 || epi == 3 || (epi == 1 && opk)) || (epi != 1 && opk)) return 1;
   const int step = epi == 1 ? 2 : 1;
   const int units = (N / 16) / step;
@@ -200,8 +199,7 @@ static int launch_gemm_rw4(const void* x, const void* w4, const void* s4, void* 
   const int base = units / G, rem = units % G;
   const int ntb = (base + (rem ? 1 : 0)) * step;
   const int n_big = rem ? rem : G;
-#define MP_RW4C(B_, S_, GU_) \
-  return launch_gemm_rw4_cfg<MT, B_, S_, GU_>(x, w4, s4, y, ys, res, rs, M, K, epi, G, n_big, ep, stream, dry)
+#define MP_RW4C(B_, S_, GU_) return launch_gemm_rw4_cfg<MT, B_, S_, GU_>(a, ep, stream, G, n_big, dry)
   if (epi == 1) {
     switch (ntb) {
       case 2: MP_RW4C(2, 2, true);
@@ -221,12 +219,8 @@ static int launch_gemm_rw4(const void* x, const void* w4, const void* s4, void* 
 #undef MP_RW4C
 }
 
-static int gemm_w4_dispatch(const void* x, const void* w4, const void* s4, void* y, int64_t ys, const void* res,
-                            int64_t rs, int M, int N, int K, int epi, bool opk, const EpiArgs& ep, hipStream_t stream,
-                            bool dry) {
-  return with_row_tiles(M, [&](auto mt) {
-    return launch_gemm_rw4<mt()>(x, w4, s4, y, ys, res, rs, M, N, K, epi, opk, ep, stream, dry);
-  });
+static int gemm_w4_dispatch(const GemmArgs& a, const EpiArgs& ep, hipStream_t stream, bool dry) {
+  return with_row_tiles(a.M, [&](auto mt) { return launch_gemm_rw4<mt()>(a, ep, stream, dry); });
 }
 
 // One thread per 16-byte lane chunk: 32 weights (8 of each of 4 k-slices) -> 4 x 16 B of row-major bf16
@@ -247,20 +241,21 @@ __global__ __launch_bounds__(256) void dequant_w4_kernel(const uint8_t* __restri
 
 }  // namespace mp
 
-// W4A16 decode GEMM: MXFP4 weights (layout above), packed bf16 activations, M <= 64, epilogues 0
-// (optional ss_in row scale), 1 (packed SwiGLU output: flags bit 1) and 3 (residual-stream
-// producer).  Returns 1 when the shape is not covered (nothing launched), < 0 for a bad call.
-extern "C" int mp_gemm_w4(const void* x, const void* w4, const void* s4, void* y, int64_t y_stride, const void* res,
-                          int64_t res_stride, int M, int N, int K, int epilogue, int flags, void* ap, void* ss_out,
-                          void* ss_zero, const void* ss_in, float inv_k, float eps, hipStream_t stream) {
+// W4A16 decode GEMM: MXFP4 weights (layout above; a.w the codes, a.wsc the block scales), packed bf16
+// activations, M <= 64, epilogues 0 (optional ss_in row scale), 1 (packed SwiGLU output:
+// GEMM_OUT_PACKED, the only flag read) and 3 (residual-stream producer).  Returns 1 when the shape is
+// not covered (nothing launched), < 0 for a bad call.
+extern "C" int mp_gemm_w4(const mp::GemmArgs* args, hipStream_t stream) {
   (void)hipGetLastError();  // an earlier non-mpamd HIP call's stale error is not this launch's
   using namespace mp;
-  if (M == 0) return 0;
-  if (M < 0 || M > 64 || K <= 0 || K % 128 || N <= 0 || N % 16) return 1;
-  if (epilogue == 3 && (ap == nullptr || res == nullptr)) return -5;
-  EpiArgs ep{(bf16_t*)ap, (u64*)ss_out, (u64*)ss_zero, (const u64*)ss_in, inv_k, eps, (M + 15) / 16};
-  const int rc = gemm_w4_dispatch(x, w4, s4, y, y_stride, res, res_stride, M, N, K, epilogue, flags & 2, ep, stream,
-                                  false);
+  const GemmArgs& a = *args;
+  if (a.M == 0) return 0;
+  if (a.M < 0 || a.M > 64 || a.K <= 0 || a.K % 128 || a.N <= 0 || a.N % 16) return 1;
+  if (a.epilogue == 3 && (a.ap == nullptr || a.res == nullptr)) return -5;
+  EpiArgs ep = gemm_epi(a);
+  ep.wsc = nullptr;  // the block scales are a kernel parameter of their own, and the k walk is never
+  ep.rot = 0;        // rotated: these kernels read neither field
+  const int rc = gemm_w4_dispatch(a, ep, stream, false);
   if (rc != 0) return rc;
   return (int)hipGetLastError();
 }
@@ -268,10 +263,8 @@ extern "C" int mp_gemm_w4(const void* x, const void* w4, const void* s4, void* y
 extern "C" int mp_gemm_w4_ok(int M, int N, int K, int epilogue) {
   using namespace mp;
   if (M <= 0 || M > 64 || K <= 0 || K % 128 || N <= 0 || N % 16) return 0;
-  EpiArgs ep{};
-  ep.mt_out = (M + 15) / 16;
-  return gemm_w4_dispatch(nullptr, nullptr, nullptr, nullptr, 0, nullptr, 0, M, N, K, epilogue, epilogue == 1, ep, 0,
-                          true) == 0;
+  const GemmArgs a = gemm_shape_args(M, N, K, epilogue, epilogue == 1 ? GEMM_OUT_PACKED : 0);
+  return gemm_w4_dispatch(a, gemm_epi(a), 0, true) == 0;
 }
 
 // MXFP4 -> row-major bf16 W[N, K] (exact: code x 2^(e - 127)), one launch

@@ -4,35 +4,24 @@
 
 // W8A16 decode GEMM: fp8 (e4m3) weights in the bf16 fragment order at 1 byte per element
 // (Wq[N/16][K/32][64][8], per-output-column scales wsc[N]), packed bf16 activations, M <= 64.
-// flags: bit 1 = packed SwiGLU output; bit 7 = balanced ring kernel; bit 8 = split-K ring +
-// reduce launch (epilogue 0 / 3, needs ws).  Same epilogues / EpiArgs as mp_gemm_bf16.
-// Returns 1 when neither form covers the shape (nothing launched).
-extern "C" int mp_gemm_w8(const void* x, const void* wq, const float* wsc, void* y, int64_t y_stride,
-                          const void* res, int64_t res_stride, int M, int N, int K, int epilogue, int flags, void* ws,
-                          void* ap, void* ss_out, void* ss_zero, const void* ss_in, float inv_k, float eps,
-                          hipStream_t stream) {
+// flags: GEMM_OUT_PACKED, GEMM_RING, GEMM_SPLITK (epilogue 0 / 3, needs ws), GEMM_PARTIALS, GEMM_ROT_K.
+// Same epilogues / EpiArgs as mp_gemm_bf16.  Returns 1 when neither form covers the shape (nothing launched).
+extern "C" int mp_gemm_w8(const mp::GemmArgs* args, hipStream_t stream) {
   (void)hipGetLastError();  // an earlier non-mpamd HIP call's stale error is not this launch's
   using namespace mp;
+  const GemmArgs& a = *args;
+  const int M = a.M, flags = a.flags;
   if (M == 0) return 0;
-  if (M > 64 || K % (32 * GU_MAX) || N % 16 || wsc == nullptr) return -1;
-  if (epilogue == 3 && (ap == nullptr || res == nullptr)) return -5;
-  EpiArgs ep{(bf16_t*)ap, (u64*)ss_out, (u64*)ss_zero, (const u64*)ss_in, inv_k, eps, (M + 15) / 16};
-  ep.wsc = wsc;
-  ep.rot = (flags >> 10) & 1;
+  if (M > 64 || a.K % (32 * GU_MAX) || a.N % 16 || a.wsc == nullptr) return -1;
+  if (a.epilogue == 3 && (a.ap == nullptr || a.res == nullptr)) return -5;
+  const EpiArgs ep = gemm_epi(a);
   int rc = 1;
-  if ((flags & 256) && !(flags & 2) && ws != nullptr) {
-    rc = with_row_tiles(M, [&](auto mt) {
-      return launch_gemm_rwk<mt(), true>(x, wq, y, y_stride, res, res_stride, M, N, K, epilogue, ep, ws, stream,
-                                         rwk_comb(flags));
-    });
-    if (rc < 0) return rc;
-    if (rc == 0) return (int)hipGetLastError();
+  if ((flags & GEMM_SPLITK) && !(flags & GEMM_OUT_PACKED) && a.ws != nullptr) {
+    rc = with_row_tiles(M, [&](auto mt) { return launch_gemm_rwk<mt(), true>(a, ep, stream, rwk_comb(flags)); });
+    if (gemm_form_done(rc)) return rc;
   }
-  if (flags & 16384) return -6;  // partials only: nothing else writes them
-  rc = with_row_tiles(M, [&](auto mt) {
-    return launch_gemm_rw<mt(), true>(x, wq, y, y_stride, res, res_stride, M, N, K, epilogue, flags | 1, ep, stream);
-  });
+  if (flags & GEMM_PARTIALS) return -6;  // partials only: nothing else writes them
+  rc = with_row_tiles(M, [&](auto mt) { return launch_gemm_rw<mt(), true>(a, ep, stream); });
   if (rc != 0) return rc;
   return (int)hipGetLastError();
 }
-

@@ -1,6 +1,6 @@
 // Decode GEMM for 65..256 rows (the packed decode path at 96..256 sessions): split-K ring (o,
 // down) and balanced ring kernels at MT = 5..8, 12 and 16 (kernels: gemm_kernels.h), and the
-// two-dimensionally tiled kernel (gemm_t2d.h, flags bit 15), which ops picks from ops.T2D_MIN
+// two-dimensionally tiled kernel (gemm_t2d.h, GEMM_T2D), which ops picks from ops.T2D_MIN
 // (129) rows up: there the ring forms measured slower than hipBLASLt (profiles/r4d) and the tiled
 // form faster (profiles/r5x).
 #include "gemm_t2d.h"
@@ -21,43 +21,35 @@ static inline int with_row_tiles_wide(int M, Fn&& fn) {
   }
 }
 
-extern "C" int mp_gemm_bf16_wide(const void* x, const void* w, void* y, int64_t y_stride, const void* res,
-                                 int64_t res_stride, int M, int N, int K, int epilogue, int flags, void* ws,
-                                 const mp::EpiArgs& ep, hipStream_t stream) {
+extern "C" int mp_gemm_bf16_wide(const mp::GemmArgs* args, const mp::EpiArgs& ep, hipStream_t stream) {
   using namespace mp;
+  const GemmArgs& a = *args;
+  const int M = a.M, flags = a.flags;
   int rc = 1;
-  if (flags & 32768) {  // two-dimensionally tiled form (gemm_t2d.h); bits 16-17: forced k split
-    rc = launch_gemm_t2d(x, w, y, y_stride, res, res_stride, M, N, K, epilogue, flags, ep, ws, stream,
-                         (flags >> 16) & 3);
-    if (rc == 1 && ((flags >> 16) & 3)) return -7;  // a forced split this shape does not take (lab)
-    if (rc < 0) return rc;
-    if (rc == 0) return (int)hipGetLastError();
+  if (flags & GEMM_T2D) {  // two-dimensionally tiled form (gemm_t2d.h)
+    rc = launch_gemm_t2d(a, ep, stream, gemm_t2d_split(flags));
+    if (rc == 1 && gemm_t2d_split(flags)) return -7;  // a forced split this shape does not take (lab)
+    if (gemm_form_done(rc)) return rc;
   }
-  if ((flags & 256) && !(flags & 2) && ws != nullptr) {  // split-K ring
-    rc = with_row_tiles_wide(M, [&](auto mt) {
-      return launch_gemm_rwk<mt()>(x, w, y, y_stride, res, res_stride, M, N, K, epilogue, ep, ws, stream,
-                                   rwk_comb(flags));
-    });
-    if (rc < 0) return rc;
-    if (rc == 0) return (int)hipGetLastError();
+  if ((flags & GEMM_SPLITK) && !(flags & GEMM_OUT_PACKED) && a.ws != nullptr) {  // split-K ring
+    rc = with_row_tiles_wide(M, [&](auto mt) { return launch_gemm_rwk<mt()>(a, ep, stream, rwk_comb(flags)); });
+    if (gemm_form_done(rc)) return rc;
   }
-  rc = with_row_tiles_wide(M, [&](auto mt) {
-    return launch_gemm_rw<mt()>(x, w, y, y_stride, res, res_stride, M, N, K, epilogue, flags, ep, stream);
-  });
+  rc = with_row_tiles_wide(M, [&](auto mt) { return launch_gemm_rw<mt()>(a, ep, stream); });
   if (rc != 0) return rc < 0 ? rc : -1;
   return (int)hipGetLastError();
 }
 
-// 1 if the two-dimensionally tiled form covers this shape (flags as mp_gemm_bf16; no launch).
+// 1 if the two-dimensionally tiled form covers this shape, with and without the LDS-DMA ring (no launch).
 extern "C" int mp_gemm_t2d_ok(int M, int N, int K, int epilogue, int out_packed, int with_ws) {
   using namespace mp;
-  EpiArgs ep{};
-  ep.mt_out = (M + 15) / 16;
   char dummy = 0;
-  return launch_gemm_t2d(nullptr, nullptr, nullptr, 0, nullptr, 0, M, N, K, epilogue, 1 | (out_packed ? 2 : 0), ep,
-                         with_ws ? &dummy : nullptr, 0, 0, true) == 0 &&
-         launch_gemm_t2d(nullptr, nullptr, nullptr, 0, nullptr, 0, M, N, K, epilogue,
-                         1 | (out_packed ? 2 : 0) | 262144, ep, with_ws ? &dummy : nullptr, 0, 0, true) == 0;
+  GemmArgs a = gemm_shape_args(M, N, K, epilogue, GEMM_A_PACKED | (out_packed ? GEMM_OUT_PACKED : 0));
+  a.ws = with_ws ? &dummy : nullptr;
+  const EpiArgs ep = gemm_epi(a);
+  if (launch_gemm_t2d(a, ep, 0, 0, true) != 0) return 0;
+  a.flags |= GEMM_T2D_DMA;
+  return launch_gemm_t2d(a, ep, 0, 0, true) == 0;
 }
 
 // 1 if mp_gemm_bf16 covers a packed-activation decode GEMM of M = 65..256 rows (balanced ring
@@ -68,12 +60,8 @@ extern "C" int mp_gemm_rw_ok(int M, int N, int K, int epilogue, int out_packed) 
   // the fused-norm producer (residual + packed copy + row statistics) at 65..256 rows runs as
   // the split-K ring + its reduce launch (the reduce applies the epilogue): o / down widths
   if (epilogue == 3) return !out_packed && N % 2048 == 0;
-  EpiArgs ep{};
-  ep.mt_out = (M + 15) / 16;
-  const int flags = 1 | (out_packed ? 2 : 0) | 128;
-  const int rc = with_row_tiles_wide(M, [&](auto mt) {
-    return launch_gemm_rw<mt()>(nullptr, nullptr, nullptr, 0, nullptr, 0, M, N, K, epilogue, flags, ep, 0, true);
-  });
+  const GemmArgs a =
+      gemm_shape_args(M, N, K, epilogue, GEMM_A_PACKED | (out_packed ? GEMM_OUT_PACKED : 0) | GEMM_RING);
+  const int rc = with_row_tiles_wide(M, [&](auto mt) { return launch_gemm_rw<mt()>(a, gemm_epi(a), 0, true); });
   return rc == 0;
 }
-

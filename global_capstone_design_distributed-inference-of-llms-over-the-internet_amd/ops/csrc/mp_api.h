@@ -8,7 +8,7 @@
 
 namespace mp {
 
-// The qkv projection left as split-K partial slabs (decode GEMM flags bit 14, mp_gemm_rwk_split):
+// The qkv projection left as split-K partial slabs (decode GEMM flag GEMM_PARTIALS, mp_gemm_rwk_split):
 // part[s][row][col] fp32, s < S, plus the fused-norm row statistics (gemm_kernels.h EpiArgs::ss_in:
 // QP_SS_NSH shards of QP_SS_ROWS rows, fixed-point sums of squares).  The decode attention kernels
 // read q / k / v through qkv_part_load8 (common.h), which is the split-K reduce launch's epilogue 0
@@ -75,6 +75,61 @@ inline float attn_scale_log2(const AttnArgs& a) { return a.scale * 1.44269504088
 
 struct EpiArgs;  // gemm_kernels.h
 
+// Decode GEMM flag word (GemmArgs::flags); every entry point reads the bits its forms have and
+// ignores the rest.  The values are part of the op interface: ops/__init__.py and the tests pass
+// them as integers.
+constexpr int GEMM_SHARED_A_CFG_SHIFT = 5, GEMM_T2D_SPLIT_SHIFT = 16;
+enum GemmFlags : int {
+  GEMM_A_PACKED = 1 << 0,    // x is packed (Ap[K/32][ceil(M/16)][64][8])
+  GEMM_OUT_PACKED = 1 << 1,  // SwiGLU output packed
+  GEMM_STREAM_K = 1 << 2,    // stream-K kernel (needs ws, zero-initialised, used by one stream at a time)
+  GEMM_ONE_GROUP = 1 << 3,   // force the one-group-per-workgroup kernel
+  GEMM_SHARED_A = 1 << 4,    // shared-A (LDS-staged activation) kernel when the shape allows it
+  GEMM_SHARED_A_CFG = 3 << GEMM_SHARED_A_CFG_SHIFT,  // its (NT, CH): 0 = (2, 2), 1 = (2, 4), 2 = (1, 4), 3 = (4, 2)
+  GEMM_RING = 1 << 7,            // balanced ring kernel
+  GEMM_SPLITK = 1 << 8,          // split-K ring kernel + reduce launch (epilogue 0 / 2 / 3, needs ws)
+  GEMM_SPLITK_INLINE = 1 << 9,   // with GEMM_SPLITK: in-launch combine by the last arriver, no reduce launch
+  GEMM_ROT_K = 1 << 10,          // rotated k walk per workgroup (EpiArgs::rot)
+  GEMM_ROW_SPLIT = 1 << 12,      // row-split ring (epilogue 0 / 2 / 3, even row tiles)
+  GEMM_ROW_SPLIT_DEFAULT_CACHE = 1 << 13,  // with GEMM_ROW_SPLIT: weights loaded with the default cache policy
+  GEMM_PARTIALS = 1 << 14,       // with GEMM_SPLITK: fp32 partial slabs only, no reduce launch (QkvPart)
+  GEMM_T2D = 1 << 15,            // two-dimensionally tiled form, 65..256 rows (gemm_t2d.h)
+  GEMM_T2D_SPLIT = 3 << GEMM_T2D_SPLIT_SHIFT,  // its forced k split (lab); 0: picked per shape
+  GEMM_T2D_DMA = 1 << 18,        // its LDS-DMA ring
+};
+inline int gemm_shared_a_cfg(int flags) { return (flags & GEMM_SHARED_A_CFG) >> GEMM_SHARED_A_CFG_SHIFT; }
+inline int gemm_t2d_split(int flags) { return (flags & GEMM_T2D_SPLIT) >> GEMM_T2D_SPLIT_SHIFT; }
+
+// What every decode GEMM launcher takes (mp_gemm_bf16 and _wide, mp_gemm_w8, mp_gemm_w4, mp_gemm_mx).
+struct GemmArgs {
+  const void* x;                   // activation: bf16 rows, or packed (GEMM_A_PACKED; w8 / w4: always);
+  int64_t x_stride;                //   mx: the e4m3 bytes of mp_quant_mx.  x_stride: row-major x only (bf16)
+  const void* w;                   // packed weight: bf16 (bf16), e4m3 bytes (w8, mx), MXFP4 codes (w4)
+  const void* wsc;                 // w8 / mx: fp32 column scales [N]; w4: the e8m0 block scales s4; bf16: nullptr
+  const void* as;                  // mx: the e8m0 activation block scales of mp_quant_mx; else nullptr
+  void* y;                         // bf16 output rows, or packed (GEMM_OUT_PACKED); nullptr with GEMM_PARTIALS
+  int64_t y_stride;
+  const void* res;                 // epilogue 2 / 3: residual rows [M, N] (all)
+  int64_t res_stride;
+  int M, N, K;
+  int epilogue;                    // 0 store, 1 SwiGLU, 2 residual add, 3 residual-stream producer
+  int flags;                       // GemmFlags
+  void* ws;                        // workspace of mp_gemm_workspace_bytes() (bf16, w8; mx: required), or nullptr
+  const int* gate;                 // bf16: MoE expert gate, one device int32 (0: GEMM skipped), or nullptr
+  void* ap;                        // epilogue 3: packed copy of the output rows (all; EpiArgs, gemm_kernels.h)
+  void* ss_out;                    // epilogue 3: row sums of squares are added into it, or nullptr (all)
+  void* ss_zero;                   // the other statistics buffer, cleared by the launch, or nullptr (all)
+  const void* ss_in;               // epilogue 0 / 1: scale row r by rsqrt(ss_in[r] * inv_k + eps), or nullptr (all)
+  float inv_k, eps;
+};
+
+// the shape-only arguments of a dry run: every pointer null
+inline GemmArgs gemm_shape_args(int M, int N, int K, int epilogue, int flags) {
+  GemmArgs a{};
+  a.M = M, a.N = N, a.K = K, a.epilogue = epilogue, a.flags = flags;
+  return a;
+}
+
 }  // namespace mp
 
 extern "C" {
@@ -108,36 +163,26 @@ int mp_argmax(const void* logits, int64_t stride, int R, int V, int64_t* out, hi
 int mp_sample(const void* logits, int64_t stride, int R, int V, const float* temps, const float* top_ps,
               const int32_t* top_ks, const float* rep_pens, int32_t* recent, int recent_stride, int32_t* recent_len,
               const int64_t* seeds, float* ws, int64_t* out, int update, hipStream_t stream);
-// gemm.hip, gemm_wide.hip
+// gemm.hip, gemm_wide.hip.  The GEMM entry points return 0, 1 when no form covers the shape (nothing
+// launched), < 0 for a bad call, else the HIP error.
 int mp_gemm_ss_elems();
 int64_t mp_gemm_slab_offset();
 int64_t mp_gemm_slab_bytes();
 int mp_gemm_rwk_split(int M, int N, int K, int f8);
 int64_t mp_gemm_workspace_bytes();
-int mp_gemm_bf16(const void* x, int64_t x_stride, const void* w, void* y, int64_t y_stride, const void* res,
-                 int64_t res_stride, int M, int N, int K, int epilogue, int flags, void* ws, const int* gate,
-                 void* ap, void* ss_out, void* ss_zero, const void* ss_in, float inv_k, float eps,
-                 hipStream_t stream);
+int mp_gemm_bf16(const mp::GemmArgs* a, hipStream_t stream);
 int mp_pack_act(const void* x, int64_t xs, void* ap, int M, int K, hipStream_t stream);
 int mp_pack_weight(const void* w, void* wp, int N, int K, hipStream_t stream);
-int mp_gemm_bf16_wide(const void* x, const void* w, void* y, int64_t y_stride, const void* res, int64_t res_stride,
-                      int M, int N, int K, int epilogue, int flags, void* ws, const mp::EpiArgs& ep,
-                      hipStream_t stream);
+int mp_gemm_bf16_wide(const mp::GemmArgs* a, const mp::EpiArgs& ep, hipStream_t stream);
 int mp_gemm_t2d_ok(int M, int N, int K, int epilogue, int out_packed, int with_ws);
 int mp_gemm_rw_ok(int M, int N, int K, int epilogue, int out_packed);
 // gemm_w8.hip, gemm_w4.hip, gemm_mx.hip
-int mp_gemm_w8(const void* x, const void* wq, const float* wsc, void* y, int64_t y_stride, const void* res,
-               int64_t res_stride, int M, int N, int K, int epilogue, int flags, void* ws, void* ap, void* ss_out,
-               void* ss_zero, const void* ss_in, float inv_k, float eps, hipStream_t stream);
-int mp_gemm_w4(const void* x, const void* w4, const void* s4, void* y, int64_t y_stride, const void* res,
-               int64_t res_stride, int M, int N, int K, int epilogue, int flags, void* ap, void* ss_out, void* ss_zero,
-               const void* ss_in, float inv_k, float eps, hipStream_t stream);
+int mp_gemm_w8(const mp::GemmArgs* a, hipStream_t stream);
+int mp_gemm_w4(const mp::GemmArgs* a, hipStream_t stream);
 int mp_gemm_w4_ok(int M, int N, int K, int epilogue);
 int mp_dequant_w4(const void* w4, const void* s4, void* w, int N, int K, hipStream_t stream);
 int mp_quant_mx(const void* ap, void* ax, void* as, int M, int K, hipStream_t stream);
-int mp_gemm_mx(const void* ax, const void* as, const void* wq, const float* wsc, void* y, int64_t y_stride,
-               const void* res, int64_t res_stride, int M, int N, int K, int epilogue, int flags, void* ws, void* ap,
-               void* ss_out, void* ss_zero, const void* ss_in, float inv_k, float eps, hipStream_t stream);
+int mp_gemm_mx(const mp::GemmArgs* a, hipStream_t stream);
 // gemm_moe.hip: the grouped W8A16 GEMMs of a sparse-MoE MLP (all experts of a layer in two launches)
 int mp_moe_gate_up_w8(const void* x, const void* w8, const float* wsc, const int32_t* cnt, void* act, int M, int E,
                       int H, int F, hipStream_t stream);

@@ -90,9 +90,10 @@ int main(int argc, char** argv) {
     for (int q = 0; q < j; ++q) off += (size_t)g[q].N * g[q].K;
     const int fl = 1 | (M > 32 ? s.f64 : s.f32);
     const int nc = s.epi == 1 ? s.N / 2 : s.N;
-    const int rc = mp_gemm_bf16(x[lane], s.K, wts + off, s.epi == 1 ? ap[lane] : y[lane], nc, nullptr, 0, M, s.N,
-                                s.K, s.epi, fl, ws[lane], nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, 0.f,
-                                st[lane]);
+    mp::GemmArgs a = mp::gemm_shape_args(M, s.N, s.K, s.epi, fl);
+    a.x = x[lane], a.x_stride = s.K, a.w = wts + off, a.y = s.epi == 1 ? ap[lane] : y[lane], a.y_stride = nc;
+    a.ws = ws[lane];
+    const int rc = mp_gemm_bf16(&a, st[lane]);
     if (rc) {
       fprintf(stderr, "gemm rc=%d (N=%d K=%d M=%d)\n", rc, s.N, s.K, M);
       exit(1);

@@ -354,8 +354,9 @@ static int launch_gemm_rg(const void* x, const void* w, void* y, int64_t ys, con
 #undef MP_RGC
   if (rc != 0) return rc;
   if (g.S > 1) {
-    const dim3 g2(N / (256 * SKR_CPT), M);
-    launch_splitk_reduce(g.S, epi, g2, stream, part, M, N, y, ys, res, rs, ep);
+    GemmArgs a = gemm_shape_args(M, N, K, epi, flags);
+    a.y = y, a.y_stride = ys, a.res = res, a.res_stride = rs;
+    launch_splitk_reduce(a, ep, stream, part, g.S);
   }
   return 0;
 }

@@ -109,8 +109,9 @@ int main(int argc, char** argv) {
         const int flags = 1 | (kind == 0 ? 8 : kind == 1 ? 4 : kind == 6 ? 128 : kind == 7 ? 256 : 16 | ((kind - 2) << 5));
         auto run = [&](int i, unsigned short* out) {
           const unsigned short* w = pool + (size_t)(i % copies) * (wbytes / 2);
-          return mp_gemm_bf16(x, s.K, w, out, ncols, nullptr, 0, M, s.N, s.K, s.epi, flags, ws, nullptr, nullptr,
-                              nullptr, nullptr, nullptr, 0.f, 0.f, 0);
+          mp::GemmArgs a = mp::gemm_shape_args(M, s.N, s.K, s.epi, flags);
+          a.x = x, a.x_stride = s.K, a.w = w, a.y = out, a.y_stride = ncols, a.ws = ws;
+          return mp_gemm_bf16(&a, 0);
         };
         int rc = run(0, kind == 0 ? yref : y);
         if (rc) {

@@ -97,8 +97,10 @@ int main(int argc, char** argv) {
     const int copies = (int)(pool_bytes / wbytes);
     auto gemm = [&](int i) {
       const unsigned short* w = pool + (size_t)(i % copies) * (wbytes / 2);
-      return mp_gemm_bf16(x, s.K, w, res, s.N, res, s.N, M, s.N, s.K, s.epi, 1 | s.flags, ws, nullptr, ap, ss, ss2,
-                          nullptr, 1.f / s.K, 1e-5f, s0);
+      mp::GemmArgs a = mp::gemm_shape_args(M, s.N, s.K, s.epi, mp::GEMM_A_PACKED | s.flags);
+      a.x = x, a.x_stride = s.K, a.w = w, a.y = res, a.y_stride = s.N, a.res = res, a.res_stride = s.N, a.ws = ws;
+      a.ap = ap, a.ss_out = ss, a.ss_zero = ss2, a.inv_k = 1.f / s.K, a.eps = 1e-5f;
+      return mp_gemm_bf16(&a, s0);
     };
     auto attn = [&]() {
       hipLaunchKernelGGL(stream_read<0>, dim3(2048), dim3(256), 0, s0, (const uint4*)kv, (kv_mb << 20) / 16, sink);

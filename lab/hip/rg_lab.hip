@@ -110,9 +110,14 @@ int main(int argc, char** argv) {
         unsigned short* y = s.epi == 3 ? res : (S < 0 ? yb : yn);
         auto run = [&](int i) -> int {
           const unsigned short* w = pool + (size_t)(i % copies) * (wbytes / 2);
-          if (S < 0)
-            return mp_gemm_bf16(x, s.K, w, y, Nout, s.epi == 3 ? res : nullptr, s.N, M, s.N, s.K, s.epi, s.base_flags,
-                                ws, nullptr, ap, ss, ss2, s.epi < 2 ? ss_in : nullptr, 1.f / s.K, 1e-5f, 0);
+          if (S < 0) {
+            mp::GemmArgs a = mp::gemm_shape_args(M, s.N, s.K, s.epi, s.base_flags);
+            a.x = x, a.x_stride = s.K, a.w = w, a.y = y, a.y_stride = Nout;
+            a.res = s.epi == 3 ? res : nullptr, a.res_stride = s.N, a.ws = ws;
+            a.ap = ap, a.ss_out = ss, a.ss_zero = ss2, a.ss_in = s.epi < 2 ? ss_in : nullptr;
+            a.inv_k = 1.f / s.K, a.eps = 1e-5f;
+            return mp_gemm_bf16(&a, 0);
+          }
           const int fl = (s.epi == 1 ? 2 : 0) | (S > 1 ? (S << 16) : 0);
           int rc;
           switch (MT) {

@@ -107,8 +107,11 @@ int main(int argc, char** argv) {
           const unsigned short* w = pool + (size_t)(i % copies) * (wbytes / 2);
           unsigned short* y = s.epi == 3 ? res : yref + 0;  // EPI 3 updates the residual in place
           if (s.epi == 0) y = res;
-          return mp_gemm_bf16(x, s.K, w, y, s.N, s.epi == 3 ? res : nullptr, s.N, M, s.N, s.K, s.epi, 1 | kd.flags,
-                              ws, nullptr, ap, ss, ss2, nullptr, 1.f / s.K, 1e-5f, 0);
+          mp::GemmArgs a = mp::gemm_shape_args(M, s.N, s.K, s.epi, mp::GEMM_A_PACKED | kd.flags);
+          a.x = x, a.x_stride = s.K, a.w = w, a.y = y, a.y_stride = s.N;
+          a.res = s.epi == 3 ? res : nullptr, a.res_stride = s.N, a.ws = ws;
+          a.ap = ap, a.ss_out = ss, a.ss_zero = ss2, a.inv_k = 1.f / s.K, a.eps = 1e-5f;
+          return mp_gemm_bf16(&a, 0);
         };
         // correctness: one call from the saved residual with zeroed statistics
         CK(hipMemcpy(res, res0, (size_t)64 * 12288 * 2, hipMemcpyDeviceToDevice));

@@ -116,6 +116,30 @@ def test_one_bad_argument_is_rejected_with_its_message(op):
             fn(**(_args(op) | change))
 
 
+def test_launcher_return_codes_before_any_launch():
+    """Calls that pass every binding check and are refused by the launchers (``mp_gemm_*``) before a
+    kernel is launched: each keeps its return code, which the op raises as it always has."""
+    ops.require_native()
+    ws = ops.gemm_workspace(DEV)
+    partials = 1 | 256 | 16384  # packed A | split-K ring | partial slabs only
+    wide = dict(y=_bf(M, 1024), workspace=ws, flags=partials)
+    cases = [
+        # a row-major x: only the packed-activation kernels are built
+        ("gemm", dict(x=_bf(M, K), flags=0), "gemm launch failed with code -4"),
+        # SwiGLU over an odd number of column tiles (N = 48: three)
+        ("gemm", _args("gemm", N=48) | dict(epilogue=1, y=_bf(M, 24)), "gemm launch failed with code -2"),
+        # N = 1024 has no split-K geometry, and nothing else writes partial slabs
+        ("gemm", _args("gemm", N=1024) | wide, "gemm launch failed with code -6"),
+        ("gemm_w8", _args("gemm_w8", N=1024) | wide, "gemm_w8 launch failed with code -6"),
+        # K = 64 is no multiple of the 128 a wave group walks
+        ("gemm", _args("gemm", K=64), "gemm launch failed with code -1"),
+        ("gemm_mx", _args("gemm_mx", N=1024), "gemm_mx: no split-K geometry for M=16 N=1024 K=256"),
+    ]
+    for op, change, msg in cases:
+        with pytest.raises(RuntimeError, match=re.escape("mpamd: " + msg) + r"(\n|$)"):
+            getattr(torch.ops.mpamd, op)(**(_args(op) | change))
+
+
 def _operands(n, k):
     torch.manual_seed(n + k)
     x = torch.randn(M, k, device=DEV).to(torch.bfloat16)
