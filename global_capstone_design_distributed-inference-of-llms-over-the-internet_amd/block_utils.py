@@ -78,11 +78,33 @@ def kv_cache_bytes_per_block(cfg: ModelConfig, tokens: Optional[int] = None, dty
     return tokens * cfg.kv_bytes_per_token_per_layer(_DTYPE_BYTES[resolve_block_dtype(cfg, dtype)], kv_cache_dtype)
 
 
+def adapter_bytes_per_block(cfg: ModelConfig, specs, dtype=torch.bfloat16, folded: bool = False) -> int:
+    """Bytes one block's LoRA stacks take for the adapters ``specs`` (``--adapters``; upstream
+    ``estimate_adapter_memory_per_block``): per fused projection A [S, R, K] + B [S, N, R] with R the
+    largest fused rank over the adapters, padded to 16 (models/adapters.py) - read from the adapters'
+    configs alone, no weights.  ``folded``: plus the A diag(g) copies a stage on the fused-norm path
+    keeps for qkv and gate_up."""
+    from .models import adapters as ad
+
+    specs = list(specs or ())
+    if not specs:
+        return 0
+    elt = _DTYPE_BYTES[resolve_block_dtype(cfg, dtype)]
+    ranks = [ad.spec_ranks(s) for s in specs]
+    n = 0
+    for proj in ad.FUSED:
+        R = ad.fused_rank(ranks, proj)
+        N, K = ad.fused_shape(cfg, proj)
+        n += len(specs) * R * (K + N + (K if folded and proj in ("qkv", "gate_up") else 0)) * elt
+    return int(n)
+
+
 def auto_num_blocks(cfg: ModelConfig, free_bytes: Optional[int] = None, dtype=torch.bfloat16,
                     quant_type: Optional[str] = None, attn_cache_tokens: Optional[int] = None,
                     reserve_bytes: int = 2 << 30, device=None, total_blocks: Optional[int] = None,
-                    kv_cache_dtype: str = "bf16") -> int:
+                    kv_cache_dtype: str = "bf16", adapter_bytes: int = 0) -> int:
     """How many blocks this GPU can serve: floor((free - reserve) / (block + KV per block)).
+    ``adapter_bytes``: LoRA stacks per block (``adapter_bytes_per_block``), added to the block.
 
     ``free_bytes`` defaults to the device's free memory (``torch.cuda.mem_get_info``); on a
     CPU host the caller must pass it.  The result is clamped to [1, total_blocks].
@@ -93,6 +115,7 @@ def auto_num_blocks(cfg: ModelConfig, free_bytes: Optional[int] = None, dtype=to
         free_bytes = torch.cuda.mem_get_info(torch.device(device))[0]
     per_block = get_block_size(cfg, "memory", dtype, quant_type) + kv_cache_bytes_per_block(cfg, attn_cache_tokens,
                                                                                            dtype, kv_cache_dtype)
+    per_block += int(adapter_bytes)
     n = int((int(free_bytes) - int(reserve_bytes)) // per_block)
     total = cfg.num_hidden_layers if total_blocks is None else int(total_blocks)
     return max(1, min(n, total))

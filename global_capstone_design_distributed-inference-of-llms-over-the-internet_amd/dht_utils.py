@@ -89,6 +89,13 @@ def register_blocks_on_dht(dht: DHT, peer_id, block_indices: List[int], model_na
         return False
 
 
+def record_hosts_adapter(rec: dict, adapter: Optional[str]) -> bool:
+    """Whether the server of a stage / module record can run ``adapter`` ("" / None: the base model,
+    which every server runs).  Servers announce ``adapters`` (the names, upstream ServerInfo.adapters)
+    only when they host any."""
+    return not adapter or adapter in ((rec or {}).get("adapters") or ())
+
+
 def _unwrap(v: Any) -> Any:
     if hasattr(v, "value"):
         return v.value

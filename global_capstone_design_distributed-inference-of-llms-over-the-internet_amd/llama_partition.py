@@ -25,12 +25,12 @@ from __future__ import annotations
 import dataclasses
 import logging
 import uuid
-from typing import Optional
+from typing import Optional, Sequence
 
 import torch
 
 from .models.config import ModelConfig, resolve_model
-from .models.weights import StageWeights, build_stage_weights
+from .models.weights import LlamaLayer, StageWeights, build_stage_weights
 from .runtime.executor import StageExecutor
 
 logger = logging.getLogger(__name__)
@@ -96,12 +96,18 @@ def resolve_quant_type(quant_type) -> str:
 
 def load_stage_model(model_name: str, device, role: str, *, start: int = 0, end: Optional[int] = None,
                      dtype=torch.bfloat16, use_cpu_offload: bool = False, seed: int = 0,
-                     quant_type: Optional[str] = None, **executor_kwargs) -> LoadedStage:
+                     quant_type: Optional[str] = None, adapters: Optional[Sequence[str]] = None,
+                     **executor_kwargs) -> LoadedStage:
     """Load ONLY the role's blocks (+ embeddings for stage0, norm/head for last).  ``quant_type``
     ("fp8" / "mxfp4", or upstream's "int8" / "nf4"): the blocks are quantized one by one as they
-    are built."""
+    are built.  ``adapters``: LoRA adapter specs (``--adapters``, models/adapters.py), loaded for
+    these blocks only."""
     cfg = resolve_model(model_name)
     quant = resolve_quant_type(quant_type)
+    if adapters and quant != "none":
+        raise ValueError(f"adapters with {quant} weights are not built: serve adapters on 16-bit weights")
+    if adapters and use_cpu_offload:
+        raise ValueError("adapters with CPU offload are not built")
     if quant != "none" and use_cpu_offload:
         raise ValueError(f"CPU offload is not supported with {quant} weights")
     L = cfg.num_hidden_layers
@@ -125,6 +131,9 @@ def load_stage_model(model_name: str, device, role: str, *, start: int = 0, end:
     w = build_stage_weights(cfg, model_name, s, e, has_embed=role in ("stage0", "full"),
                             has_head=role in ("last", "full"), device=load_dev, dtype=dt, seed=seed,
                             quant_type=quant)
+    if adapters:
+        w.load_adapters(adapters, seed=seed)
+        logger.info(f"adapters {w.lora.names} loaded for blocks [{s},{e}): {w.lora.nbytes() / 2**20:.1f} MiB")
     logger.info(f"load_stage_model: role={role}, layers={e - s}, start={s}, end={e}, quant_type={quant}")
     return LoadedStage(cfg, w, role, s, e, device, dt, model_name, executor_kwargs, bool(use_cpu_offload))
 
@@ -139,6 +148,14 @@ def _to_device(w: StageWeights, device) -> StageWeights:
         t = getattr(w, name)
         if t is not None:
             setattr(w, name, t.to(device))
+    if w.lora is not None:
+        w.lora.scale = w.lora.scale.to(device)
+        for L in w.lora.layers:
+            for p in LlamaLayer.PROJ:
+                lp = getattr(L, p)
+                if lp is not None:
+                    lp.A, lp.B = lp.A.to(device), lp.B.to(device)
+                    lp.A_folded = None if lp.A_folded is None else lp.A_folded.to(device)
     return w
 
 

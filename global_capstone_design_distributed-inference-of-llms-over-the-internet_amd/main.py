@@ -88,6 +88,14 @@ def build_parser() -> argparse.ArgumentParser:
                    help="stage servers, models with a sliding window (mistral-7b: 4096): cap = sessions end at the "
                         "window; attend = sessions run to max_seq_len, every token attends to the last window "
                         "tokens and KV memory per session stops growing at the window")
+    p.add_argument("--adapters", nargs="*", default=[], metavar="SPEC",
+                   help="LoRA adapters to host (upstream Petals --adapters): a local PEFT directory "
+                        "(adapter_config.json + adapter_model.safetensors; its base name is the adapter's name), "
+                        "NAME=DIR, or synthetic:NAME:R[:mod,mod...]. The client passes them too: it runs the first "
+                        "blocks itself")
+    p.add_argument("--active_adapter", type=str, default="",
+                   help="client: generate with this hosted adapter (request metadata active_adapter); every "
+                        "server of the route must host it")
     p.add_argument("--use_cpu_offload", action="store_true")
     p.add_argument("--keep_layers_on_gpu", type=int, default=0)
     p.add_argument("--use_load_balancing", action="store_true")
@@ -212,9 +220,14 @@ def run_rank0(args, device, cuts: List[int], on_token=None, results: Optional[li
     n_servers = len(cuts)
     dtype = resolve_dtype(args.dtype, device)
     full = load_stage_model(args.model, device, "stage0", end=stage0_end, dtype=dtype, seed=args.seed,
-                            **_executor_kwargs(args))
+                            adapters=_adapters(args), **_executor_kwargs(args))
     w = full.weights
     ex = StageExecutor(cfg, w, device, dtype=dtype, **full.executor_kwargs)
+    adapter = getattr(args, "active_adapter", "") or ""
+    ex.adapter_slot(adapter)  # KeyError("adapter X not found") unless --adapters hosts it for the first blocks
+    if adapter and args.device_channel != "off":
+        logger.info("--active_adapter: the device channel does not carry adapters; using --device_channel off")
+        args.device_channel = "off"
     tok = load_tokenizer(args.model, cfg)
     total_blocks = args.total_blocks or L
     tx = RpcTransport(device, 0, _peers(args.dht_initial_peers), args.dht_port, args.rpc_port,
@@ -222,7 +235,7 @@ def run_rank0(args, device, cuts: List[int], on_token=None, results: Optional[li
                       top_k=args.top_k, stage_keys=[get_stage_key(i) for i in range(1, n_servers + 1)],
                       routing="module" if args.use_load_balancing else "stage", model_name=args.model,
                       total_blocks=total_blocks, start_block=stage0_end, repetition_penalty=args.repetition_penalty,
-                      push=args.push)
+                      push=args.push, active_adapter=adapter)
     ids = tok(args.prompt, return_tensors="pt").input_ids.reshape(-1)
     Lp = int(ids.numel())
     sid = str(uuid.uuid4())
@@ -235,7 +248,7 @@ def run_rank0(args, device, cuts: List[int], on_token=None, results: Optional[li
     if int(args.num_sessions) > 1:
         return _run_rank0_tcp_sessions(args, device, ex, tok, tx, ids)
     t0 = time.perf_counter()
-    hidden = ex.forward([(sid, Lp)], ids.to(device), reset=[True], max_length=max_length)
+    hidden = ex.forward([(sid, Lp)], ids.to(device), reset=[True], max_length=max_length, adapters=[adapter])
     tx.send_prefill(Lp, hidden, session_id=sid, max_length=max_length)
     next_id = tx.recv_token()
     generated = [next_id]
@@ -249,7 +262,8 @@ def run_rank0(args, device, cuts: List[int], on_token=None, results: Optional[li
         if eos is not None and next_id == eos:
             logger.info("EOS token generated, stopping generation")
             break
-        hidden = ex.forward([(sid, 1)], torch.tensor([next_id], device=device), starts=[cur_len - 1])
+        hidden = ex.forward([(sid, 1)], torch.tensor([next_id], device=device), starts=[cur_len - 1],
+                            adapters=[adapter])
         tx.send_decode_step(cur_len, hidden, session_id=sid, max_length=max_length, generated_tokens=generated)
         next_id = tx.recv_token()
         if eos is not None and next_id == eos:
@@ -292,8 +306,9 @@ def _run_rank0_tcp_sessions(args, device, ex, tok, tx, ids):
     sids = [str(uuid.uuid4()) for _ in range(n)]
     eos = getattr(tok, "eos_token_id", None)
     t0 = time.perf_counter()
+    adapter = getattr(args, "active_adapter", "") or ""
     hidden = ex.forward([(s, Lp) for s in sids], ids.repeat(n).to(device), reset=[True] * n,
-                        max_length=max_length)
+                        max_length=max_length, adapters=[adapter] * n)
     rows = hidden.reshape(n, Lp, -1)
     nxt = tx.send_steps([(s, rows[i], Lp, Lp, max_length, None) for i, s in enumerate(sids)])
     ttft = time.perf_counter() - t0
@@ -305,7 +320,7 @@ def _run_rank0_tcp_sessions(args, device, ex, tok, tx, ids):
         if not live:
             break
         toks = torch.tensor([gen[s][-1] for s in live], device=device)
-        hidden = ex.forward([(s, 1) for s in live], toks)
+        hidden = ex.forward([(s, 1) for s in live], toks, adapters=[adapter] * len(live))
         out = tx.send_steps([(s, hidden[i:i + 1], 1, Lp + len(gen[s]), max_length, gen[s])
                              for i, s in enumerate(live)])
         n_dec += len(live)
@@ -502,6 +517,10 @@ def _log_stage_stats(replica: int, rows, route) -> None:
 
 
 # ================================================================================ servers
+def _adapters(args) -> List[str]:
+    return list(getattr(args, "adapters", None) or [])
+
+
 def _quant(args) -> str:
     """``--quant_type`` resolved once per process (the nf4 / int8 mapping logs one line)."""
     q = getattr(args, "_quant_resolved", None)
@@ -547,6 +566,8 @@ class _Server:
                      kv_cache_dtype=getattr(ex, "kv_cache_dtype", "bf16"))
         if getattr(ex, "sliding_window", None):  # models with a window: the mode and W
             extra.update(sliding_window=ex.sliding_window, window=int(ex.cfg.sliding_window))
+        if getattr(ex, "adapters", None):  # hosted LoRA adapters (upstream ServerInfo.adapters)
+            extra["adapters"] = list(ex.adapters)
         if self.next_pings:
             extra["next_pings"] = dict(self.next_pings)
         if self.lb:
@@ -559,6 +580,8 @@ class _Server:
 
             chan = dict(channel_host=host_id(), device=str(ex.device))
             extra.update(chan)
+        if "adapters" in extra:  # (the module records carry them too: module routing filters on them)
+            chan = dict(chan, adapters=extra["adapters"])
         if state == ServerState.ONLINE:
             register_stage_on_dht(self.dht, self.stage_idx, self.peer_id, self.maddrs, ttl=a.ttl, **extra)
         register_model_on_dht(self.dht, a.model, getattr(a, "total_blocks", None) or ex.cfg.num_hidden_layers,
@@ -654,7 +677,8 @@ def run_stage_server_fixed(args, device, cuts: List[int], stop: Optional[threadi
     role = "last" if final else "segment"
     dtype = resolve_dtype(args.dtype, device)
     full = load_stage_model(args.model, device, role, start=s, end=e, dtype=dtype, seed=args.seed,
-                            use_cpu_offload=args.use_cpu_offload, quant_type=_quant(args), **_executor_kwargs(args))
+                            use_cpu_offload=args.use_cpu_offload, quant_type=_quant(args), adapters=_adapters(args),
+                            **_executor_kwargs(args))
     off = bool(args.use_cpu_offload) and device.type == "cuda"
     ex = StageExecutor(cfg, full.weights if off or not args.use_cpu_offload else _onto(full, device), device,
                        dtype=dtype, offload=off, keep_layers_on_gpu=args.keep_layers_on_gpu, **full.executor_kwargs)
@@ -685,9 +709,12 @@ def run_stage_server_with_load_balancing(args, device, cuts: List[int], stop: Op
     if args.num_blocks is None and getattr(args, "auto_num_blocks", False) and device.type == "cuda":
         from .block_utils import auto_num_blocks
 
+        from .block_utils import adapter_bytes_per_block
+
         num_blocks = auto_num_blocks(cfg, dtype=dtype, quant_type=quant, device=device,
                                      total_blocks=total - min_block,
-                                     kv_cache_dtype=getattr(args, "kv_cache_dtype", "bf16"))
+                                     kv_cache_dtype=getattr(args, "kv_cache_dtype", "bf16"),
+                                     adapter_bytes=adapter_bytes_per_block(cfg, _adapters(args), dtype, folded=True))
         logger.info(f"auto num_blocks = {num_blocks}")
     else:
         num_blocks = args.num_blocks or 4
@@ -724,7 +751,7 @@ def run_stage_server_with_load_balancing(args, device, cuts: List[int], stop: Op
         final = e >= total
         logger.info(f"Selected blocks [{s}, {e}) (final={final})")
         full = load_stage_model(args.model, device, "last" if final else "segment", start=s, end=e, dtype=dtype,
-                                seed=args.seed, quant_type=quant, **_executor_kwargs(args))
+                                seed=args.seed, quant_type=quant, adapters=_adapters(args), **_executor_kwargs(args))
         ex = StageExecutor(cfg, full.weights, device, dtype=dtype, **full.executor_kwargs)
         tb = max(1, int(getattr(args, "throughput_batch", 16)))
         srv = _Server(args, dht, ex, final, args.stage, throughput=FALLBACK_THROUGHPUT, lb=True, announce=False)

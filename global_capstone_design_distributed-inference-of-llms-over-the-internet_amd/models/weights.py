@@ -163,6 +163,7 @@ class StageWeights:
     lm_head: Optional[torch.Tensor] = None      # [V, H]
     lm_head_p: Optional[torch.Tensor] = None    # packed lm_head (V padded to a multiple of 16)
     lm_head_folded: bool = False                # lm_head_p carries final_norm in its K columns
+    lora: Optional[object] = None               # adapters.LoraStacks once load_adapters() ran
 
     @property
     def has_embed(self) -> bool:
@@ -177,6 +178,29 @@ class StageWeights:
         for t in self.tensors():
             n += t.numel() * t.element_size()
         return n
+
+    def load_adapters(self, specs, seed: int = 0):
+        """Load LoRA adapters (models/adapters.py: PEFT directories, ``NAME=path`` or
+        ``synthetic:NAME:R[:mods]``) and stack them per layer and fused projection on the stage's
+        device, in the stage's dtype; slot order is the order of ``specs``.  Once per stage (no hot
+        loading).  Quantized, MoE and GPT-2 stages raise."""
+        from . import adapters as ad
+
+        specs = list(specs or ())
+        if not specs:
+            return None
+        if self.lora is not None:
+            raise ValueError("adapters are loaded once per stage (hot loading is not built)")
+        ad.check_adapters_supported(self)
+        if self.layers:
+            dev, dtype = self.layers[0].qkv.device, self.layers[0].qkv.dtype
+        else:
+            t = next(iter(self.tensors()), None)
+            dev, dtype = (t.device, t.dtype) if t is not None else (torch.device("cpu"), torch.bfloat16)
+        loaded = [ad.load_adapter(self.cfg, s, self.start, self.end, seed=seed, dtype=dtype) for s in specs]
+        self.lora = ad.build_stacks(self.cfg, loaded, self.start, self.end, dev, dtype)
+        self.lora.fold_norms(self.layers)
+        return self.lora
 
     def pack_for_decode(self, fold_norms: bool = False) -> None:
         """Add fragment-native copies of every projection (MI355X decode GEMM layout).

@@ -1754,3 +1754,110 @@ def autotune_w8(shapes, device, ms=(4, 16, 32, 48, 64), iters: int = 12, rounds:
     finally:
         _W8_MODE = saved
     return dict(_W8_CHOICE)
+
+
+# ---------------------------------------------------------------------------------------
+# Batched LoRA (csrc/lora.hip): rows of one ragged step carry the slot of their adapter, int32 in
+# [-1, S); slot -1 is a base-model row, which neither op reads or writes.  Stacked adapter matrices
+# ``A`` [S, R, K], ``B`` [S, N, R] and ``scale`` fp32 [S] (models/adapters.py); for every row m with
+# s = slots[m] >= 0
+#     t[m]  = scale[s] * (A[s] x[m])                       fp32 [R], never rounded to bf16
+#     y[m]  = dtype( fp32(y[m]) + fp32(B[s]) t[m] )        one more rounding of the stored y
+# A row's result depends on its own x, slot and the shape alone - never on the other rows' slots.
+_LORA_OK = {}
+
+
+def lora_ok(M: int, N: int, K: int, R: int) -> bool:
+    """Whether the two kernels cover the shape: 1 <= M <= 64, K % 32 == 0, N % 8 == 0, R % 16 == 0,
+    R <= 192 (a dry dispatch where the library is loaded, as ``moe_w8_ok``)."""
+    key = (int(M), int(N), int(K), int(R))
+    if key not in _LORA_OK:
+        if native_available():
+            _LORA_OK[key] = bool(key[0] >= 1 and torch.ops.mpamd.lora_ok(*key))
+        else:
+            _LORA_OK[key] = bool(1 <= key[0] <= 64 and key[1] > 0 and key[1] % 8 == 0 and key[2] > 0 and
+                                 key[2] % 32 == 0 and 0 < key[3] <= 192 and key[3] % 16 == 0)
+    return _LORA_OK[key]
+
+
+def _lora_dims(mats: torch.Tensor, name: str, slots: torch.Tensor, t: Optional[torch.Tensor], M: int):
+    """(S, rows, cols) of an adapter stack, with the checks both LoRA ops share."""
+    if mats.dim() != 3 or not mats.is_contiguous():
+        raise ValueError(f"{name} must be a contiguous adapter stack [S, rows, cols], got {tuple(mats.shape)}")
+    if slots.dtype != torch.int32 or slots.dim() != 1 or slots.numel() < M or slots.device != mats.device:
+        raise ValueError(f"slots must be int32 [{M}] on the adapters' device")
+    if M < 0:
+        raise ValueError(f"the LoRA ops take M >= 0 rows, got {M}")
+    R = mats.shape[1] if name == "A" else mats.shape[2]
+    if t is not None and (t.dtype != torch.float32 or t.dim() != 2 or t.shape[0] < M or t.shape[1] != R or
+                          not t.is_contiguous() or t.device != mats.device):
+        raise ValueError(f"t must be contiguous fp32 [{M}, {R}] on the adapters' device")
+    return mats.shape[0], mats.shape[1], mats.shape[2]
+
+
+def _lora_rows(slots: torch.Tensor, M: int, S: int):
+    """(row indices, their slots) of the rows with a slot in [0, S) - the torch forms' gather."""
+    sl = slots[:M].long()
+    idx = torch.nonzero((sl >= 0) & (sl < S)).flatten()
+    return idx, sl[idx]
+
+
+def lora_shrink(x, A, scale, slots, a_rows: int, out=None):
+    """t fp32 [M, R]: ``x`` packed (``a_rows`` = M rows of K, M <= 64 on the GPU).  Rows with slot -1
+    are not written (``out`` keeps what it held; a fresh one holds zeros)."""
+    M = int(a_rows)
+    if out is None:
+        out = torch.zeros(M, A.shape[1] if A.dim() == 3 else 0, dtype=torch.float32, device=A.device)
+    S, R, K = _lora_dims(A, "A", slots, out, M)
+    if scale.dtype != torch.float32 or scale.numel() != S:
+        raise ValueError(f"scale must be fp32 [{S}]")
+    if x.numel() < packed_numel(M, K):
+        raise ValueError(f"packed x holds fewer than {M} rows of {K}")
+    if M == 0:
+        return out
+    if not _native(x):
+        xr = ref.unpack_act(x, M, K)
+        for m, s in zip(*map(torch.Tensor.tolist, _lora_rows(slots, M, S))):  # row by row: a row's bits
+            out[m] = scale[s] * torch.mv(A[s].float(), xr[m].float())       # never depend on the others
+        return out
+    torch.ops.mpamd.lora_shrink(x, A, scale, slots, out, M)
+    return out
+
+
+def lora_expand(t, B, slots, y):
+    """``y`` [M, N] (row-major, any row stride that is a multiple of 8) updated in place."""
+    M = int(y.shape[0])
+    S, N, R = _lora_dims(B, "B", slots, t, M)
+    if y.dim() != 2 or y.shape[1] != N or y.stride(1) != 1 or y.dtype != B.dtype:
+        raise ValueError(f"y must be [M, {N}] rows of the adapters' dtype with unit inner stride")
+    if M == 0:
+        return y
+    if not _native(y):
+        for m, s in zip(*map(torch.Tensor.tolist, _lora_rows(slots, M, S))):
+            y[m] = (y[m].float() + torch.mv(B[s].float(), t[m])).to(y.dtype)
+        return y
+    torch.ops.mpamd.lora_expand(t, B, slots, y)
+    return y
+
+
+def lora_runs(slots) -> list:
+    """Maximal runs (row0, row1, slot) of consecutive rows with the same slot >= 0, from the
+    host-side slots of a plan (no device read)."""
+    runs, r0 = [], 0
+    sl = [int(s) for s in slots]
+    for i in range(1, len(sl) + 1):
+        if i == len(sl) or sl[i] != sl[r0]:
+            if sl[r0] >= 0:
+                runs.append((r0, i, sl[r0]))
+            r0 = i
+    return runs
+
+
+def lora_update(x, y, A, B, scale, runs):
+    """The whole update in torch, by runs, on row-major ``x`` [T, K] and ``y`` [T, N] (in place):
+    the form of steps the kernels do not take (more than 64 rows, prefill, CPU stages), with the
+    semantics above - fp32 ``t``, one rounding into ``y``'s dtype."""
+    for r0, r1, s in runs:
+        t = scale[s] * (x[r0:r1].float() @ A[s].float().t())
+        y[r0:r1] = (y[r0:r1].float() + t @ B[s].float().t()).to(y.dtype)
+    return y

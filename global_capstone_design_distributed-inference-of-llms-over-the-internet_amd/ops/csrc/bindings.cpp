@@ -763,6 +763,67 @@ bool moe_w8_ok(int64_t M, int64_t E, int64_t H, int64_t F) {
   return mp_moe_w8_ok((int)M, (int)E, (int)H, (int)F) != 0;
 }
 
+// Batched LoRA (lora.hip): the stacked adapter matrices, the row slots and the fp32 intermediate
+static mp::LoraArgs lora_args(const at::Tensor& mats, const char* name, const at::Tensor& slots, const at::Tensor& t,
+                              int64_t M_) {
+  MP_CHECK(M_ >= 0 && M_ <= (1 << 20), "lora: M out of range");
+  const int M = (int)M_;
+  check_bf16_cuda(mats, name);
+  MP_CHECK(mats.dim() == 3 && mats.size(0) >= 1 && mats.stride(2) == 1 && mats.stride(1) == mats.size(2) &&
+               mats.stride(0) >= mats.size(1) * mats.size(2) && mats.stride(0) % 8 == 0 &&
+               reinterpret_cast<uintptr_t>(mats.data_ptr()) % 16 == 0,
+           std::string(name) + ": bf16 [S, rows, cols] stack, rows contiguous, 16-B aligned");
+  MP_CHECK(slots.is_cuda() && slots.scalar_type() == at::kInt && slots.is_contiguous() && slots.numel() >= M &&
+               slots.device() == mats.device(),
+           "slots: int32 [M] on the adapters' device");
+  mp::LoraArgs a{};
+  a.M = M, a.S = (int)mats.size(0);
+  a.slots = slots.data_ptr<int32_t>();
+  MP_CHECK(t.is_cuda() && t.scalar_type() == at::kFloat && t.is_contiguous() && t.dim() == 2 && t.size(0) >= M &&
+               t.device() == mats.device() && reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0,
+           "t: fp32 [M, R] contiguous on the adapters' device");
+  a.R = (int)t.size(1);
+  a.t = t.data_ptr<float>();
+  return a;
+}
+
+// t[m] = scale[s] * (A[s] x[m]), s = slots[m] >= 0 (lora.hip mp_lora_shrink): packed bf16 x (M rows)
+void lora_shrink(const at::Tensor& x, const at::Tensor& A, const at::Tensor& scale, const at::Tensor& slots,
+                 at::Tensor& t, int64_t M) {
+  mp::LoraArgs a = lora_args(A, "A", slots, t, M);
+  MP_CHECK(A.size(1) == a.R, "A: [S, R, K] with R = t.size(1)");
+  a.K = (int)A.size(2);
+  a.A = A.data_ptr(), a.a_stride = A.stride(0);
+  check_bf16_cuda(x, "x");
+  MP_CHECK(x.is_contiguous() && x.numel() >= packed_numel(a.M, a.K) && x.device() == A.device() &&
+               reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0,
+           "packed x too small");
+  MP_CHECK(scale.is_cuda() && scale.scalar_type() == at::kFloat && scale.is_contiguous() && scale.numel() == a.S &&
+               scale.device() == A.device(),
+           "scale: fp32 [S]");
+  a.x = x.data_ptr(), a.scale = scale.data_ptr<float>();
+  const int rc = mp_lora_shrink(&a, cur_stream());
+  TORCH_CHECK(rc != 1, "mpamd: lora_shrink: no kernel covers M=", a.M, " K=", a.K, " R=", a.R);
+  check_launch(rc, "lora_shrink");
+}
+
+// y[m] = bf16(y[m] + B[s] t[m]) in place, s = slots[m] >= 0 (lora.hip mp_lora_expand)
+void lora_expand(const at::Tensor& t, const at::Tensor& B, const at::Tensor& slots, at::Tensor& y) {
+  check_bf16_cuda(y, "y");
+  check_rows(y, "y");
+  mp::LoraArgs a = lora_args(B, "B", slots, t, y.size(0));
+  MP_CHECK(B.size(2) == a.R, "B: [S, N, R] with R = t.size(1)");
+  MP_CHECK(y.size(1) == B.size(1) && y.device() == B.device(), "y: [M, N] with N = B.size(1)");
+  a.N = (int)B.size(1);
+  a.B = B.data_ptr(), a.b_stride = B.stride(0);
+  a.y = y.data_ptr(), a.y_stride = y.stride(0);
+  const int rc = mp_lora_expand(&a, cur_stream());
+  TORCH_CHECK(rc != 1, "mpamd: lora_expand: no kernel covers M=", a.M, " N=", a.N, " R=", a.R);
+  check_launch(rc, "lora_expand");
+}
+
+bool lora_ok(int64_t M, int64_t N, int64_t K, int64_t R) { return mp_lora_ok((int)M, (int)N, (int)K, (int)R) != 0; }
+
 // MXFP4 weight operands (gemm_w4.hip): codes uint8 [N/16, K/128, 64, 16] + e8m0 scales uint8 [N/16, K/128, 16, 4]
 static void check_w4(const at::Tensor& w4, const at::Tensor& s4) {
   MP_CHECK(w4.is_cuda() && w4.scalar_type() == at::kByte && w4.dim() == 4 && w4.size(2) == 64 && w4.size(3) == 16 &&
@@ -1016,6 +1077,9 @@ TORCH_LIBRARY(mpamd, m) {
   m.def("moe_gate_up_w8(Tensor x, Tensor w8, Tensor wsc, Tensor cnt, Tensor(a!) act, int M) -> ()");
   m.def("moe_down_w8(Tensor act, Tensor w8, Tensor wsc, Tensor cnt, Tensor wd, Tensor(a!) y, int M) -> ()");
   m.def("moe_w8_ok(int M, int E, int H, int F) -> bool", &moe_w8_ok);
+  m.def("lora_shrink(Tensor x, Tensor A, Tensor scale, Tensor slots, Tensor(a!) t, int M) -> ()");
+  m.def("lora_expand(Tensor t, Tensor B, Tensor slots, Tensor(a!) y) -> ()");
+  m.def("lora_ok(int M, int N, int K, int R) -> bool", &lora_ok);
   m.def("pack_act(Tensor x, Tensor(a!) ap) -> ()");
   m.def("pack_weight(Tensor w) -> Tensor");
   m.def("quant_act_fp8(Tensor ap, Tensor(a!) a8, Tensor(b!) scale, int M, int K) -> ()");
@@ -1051,6 +1115,8 @@ TORCH_LIBRARY_IMPL(mpamd, CUDA, m) {
   m.impl("dequant_w4", &dequant_w4);
   m.impl("moe_gate_up_w8", &moe_gate_up_w8);
   m.impl("moe_down_w8", &moe_down_w8);
+  m.impl("lora_shrink", &lora_shrink);
+  m.impl("lora_expand", &lora_expand);
   m.impl("pack_weight", &pack_weight);
   m.impl("pack_act", &pack_act);
   m.impl("quant_act_fp8", &quant_act_fp8);

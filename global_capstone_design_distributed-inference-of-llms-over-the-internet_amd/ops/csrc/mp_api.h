@@ -130,6 +130,22 @@ inline GemmArgs gemm_shape_args(int M, int N, int K, int epilogue, int flags) {
   return a;
 }
 
+// What both batched-LoRA launchers take (lora.hip).  Row m belongs to adapter slot slots[m] in
+// [-1, S); a row with slot -1 is a base-model row: nothing of it is read or written.
+struct LoraArgs {
+  const void* x;                   // shrink: packed bf16 activation (apk_off, common.h), M rows of K
+  const void* A;                   // shrink: bf16 [S, R, K], slot s at A + s * a_stride elements
+  int64_t a_stride;
+  const void* B;                   // expand: bf16 [S, N, R], slot s at B + s * b_stride elements
+  int64_t b_stride;
+  const float* scale;              // shrink: fp32 [S], lora_alpha / r (or / sqrt(r)) of each slot
+  const int32_t* slots;            // int32 [M]
+  float* t;                        // fp32 [M, R]: shrink writes scale * (A x), expand reads it
+  void* y;                         // expand: bf16 rows [M, N], updated in place
+  int64_t y_stride;
+  int M, N, K, R, S;               // shrink ignores N, expand ignores K
+};
+
 }  // namespace mp
 
 extern "C" {
@@ -189,6 +205,11 @@ int mp_moe_gate_up_w8(const void* x, const void* w8, const float* wsc, const int
 int mp_moe_down_w8(const void* act, const void* w8, const float* wsc, const int32_t* cnt, const float* wd, void* y,
                    int64_t y_stride, int M, int E, int H, int F, hipStream_t stream);
 int mp_moe_w8_ok(int M, int E, int H, int F);
+// lora.hip: 0, 1 when the shape is not covered (needs M <= 64, K % 32 == 0, N % 8 == 0, R % 16 == 0,
+// R <= 192; nothing launched), < 0 for a bad call, else the HIP error.  M == 0 returns 0.
+int mp_lora_ok(int M, int N, int K, int R);
+int mp_lora_shrink(const mp::LoraArgs* a, hipStream_t stream);
+int mp_lora_expand(const mp::LoraArgs* a, hipStream_t stream);
 // fp8.hip
 void mp_fp8_set_kernel(int kind);
 int mp_quant_act_fp8(const void* ap, void* a8, float* scale, float* part, int M, int K, hipStream_t stream);

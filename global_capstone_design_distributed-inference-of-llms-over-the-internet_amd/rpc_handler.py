@@ -73,6 +73,7 @@ class _Req:
     t0: float
     priority: float = 2.0
     prompts: Optional[torch.Tensor] = None  # deep prompts [n_blocks, P, H] for this step
+    adapter: str = ""        # metadata["active_adapter"] (upstream _get_active_adapter); "": the base model
 
 
 class StageConnectionHandler:
@@ -155,6 +156,9 @@ class StageConnectionHandler:
         if self.executor.is_first:
             raise ValueError("stateless forward/backward takes hidden states; this span starts with the embedding")
         md, ts = msg.metadata, list(msg.tensors)
+        if md.get("active_adapter"):
+            raise ValueError(f"adapters with the stateless rpc_forward / rpc_backward are not built "
+                             f"(active_adapter={md.get('active_adapter')!r})")
         has_prompts = bool(md.get("has_prompts", False))
         need = (2 if backward else 1) + int(has_prompts)
         if len(ts) != need:
@@ -379,6 +383,8 @@ class StageConnectionHandler:
 
     async def rpc_info(self, msg: Message) -> Message:
         ex = self.executor
+        # hosted LoRA adapters (upstream ServerInfo.adapters): announced only when there are any
+        extra = {"adapters": list(ex.adapters)} if getattr(ex, "adapters", None) else {}
         return Message({"cache_tokens_left": ex.sessions.cache_tokens_left(), "sessions": len(ex.sessions.sessions),
                         "start_block": ex.start, "end_block": ex.end, "final_stage": self.final_stage,
                         "quant_type": getattr(ex, "quant_type", "none"),
@@ -386,7 +392,7 @@ class StageConnectionHandler:
                         # models with a sliding window: "cap" / "attend" and W (None / 0 otherwise)
                         "sliding_window": getattr(ex, "sliding_window", None),
                         "window": int(getattr(ex.cfg, "sliding_window", None) or 0),
-                        "phases": self.timer.summary(), **self.stats})
+                        "phases": self.timer.summary(), **extra, **self.stats})
 
     async def rpc_close_session(self, msg: Message) -> Message:
         sid = msg.metadata.get("session_id")
@@ -441,7 +447,8 @@ class StageConnectionHandler:
             if prompts.dim() == 4:
                 prompts = prompts[:, 0]
         return _Req(sid, x, start, reset, params, list(md.get("generated_tokens", []) or []),
-                    md.get("max_length"), None, time.perf_counter(), prompts=prompts)
+                    md.get("max_length"), None, time.perf_counter(), prompts=prompts,
+                    adapter=str(md.get("active_adapter") or ""))
 
     async def _submit(self, msg: Message) -> Message:
         req = self._parse(msg)
@@ -532,7 +539,7 @@ class StageConnectionHandler:
         prompts = [r.prompts for r in batch] if any(r.prompts is not None for r in batch) else None
         with torch.inference_mode(), self.timer(phase), ex.exec_lock:
             out = ex.forward(seqs, x, reset=[r.reset for r in batch], starts=[r.start for r in batch], max_length=ml,
-                             prompts=prompts)
+                             prompts=prompts, adapters=[r.adapter for r in batch])
             self.stats["batches"] += 1
             self.stats["tokens"] += int(x.shape[0])
             if self.final_stage:

@@ -42,7 +42,7 @@ import torch
 from .comm.registry import DHT, get_dht_time
 from .comm.rpc import DEFAULT_MAX_MSG_SIZE, MAX_UNARY_PAYLOAD_SIZE, RemoteError, RpcClient, get_loop
 from .comm.wire import Message
-from .dht_utils import get_module_entries, get_stage_key
+from .dht_utils import get_module_entries, get_stage_key, record_hosts_adapter
 
 logger = logging.getLogger(__name__)
 
@@ -74,8 +74,11 @@ class RpcTransport:
                  top_k: int = 50, stage_keys: Optional[List[str]] = None, routing: str = "stage",
                  model_name: str = "default", total_blocks: Optional[int] = None, start_block: int = 0,
                  dht: Optional[DHT] = None, repetition_penalty: Optional[float] = None, max_recovery_attempts: int = 3,
-                 push: bool = False):
+                 push: bool = False, active_adapter: str = ""):
         self.device = device
+        # LoRA adapter of this client's sessions (upstream ``active_adapter``): sent with every request,
+        # and only servers that announce it are routed to
+        self.active_adapter = str(active_adapter or "")
         self.stage = stage
         self.dht_port, self.rpc_port = dht_port, rpc_port
         self.timeout = timeout
@@ -134,10 +137,30 @@ class RpcTransport:
                     out.append(e)
         return out
 
+    def _with_adapter(self, cands: List[dict], what: str) -> List[dict]:
+        """The records whose server hosts this client's adapter.  Live records of which none does are
+        an error at once (a server's adapters do not change while it runs)."""
+        if not self.active_adapter or not cands:
+            return cands
+        ok = [e for e in cands if record_hosts_adapter(e, self.active_adapter)]
+        if not ok:
+            raise RuntimeError(f"no server for {what} hosts adapter {self.active_adapter!r} "
+                               f"({len(cands)} live server(s) without it)")
+        return ok
+
+    def _session_md(self, session_id: str, **fields) -> dict:
+        """Metadata of a session's request: the step's fields, the sampling parameters and the
+        session's adapter (replays and pushed hops copy it from here)."""
+        md = {"session_id": session_id, **fields, **self.sampling}
+        if self.active_adapter:
+            md["active_adapter"] = self.active_adapter
+        return md
+
     def _discover_peer(self, key: str, exclude: Set[str] = frozenset(), block: Optional[int] = None,
                        max_retries: int = 10, retry_delay: float = 1.0) -> dict:
         for attempt in range(max_retries):
             cands = [e for e in self._candidates(key, block) if str(e.get("peer_id")) not in exclude]
+            cands = self._with_adapter(cands, key)
             if cands:
                 cands.sort(key=lambda e: float(e.get("timestamp", 0.0)), reverse=True)
                 return random.choice(cands[:5])
@@ -159,6 +182,7 @@ class RpcTransport:
             cands = [e for e in self._candidates("", cur) if str(e.get("peer_id")) not in exclude]
             if not cands:
                 raise RuntimeError(f"[module routing] no server covers block={cur}")
+            cands = self._with_adapter(cands, f"block {cur}")
             cands.sort(key=lambda e: (int(e["end_block"]), float(e.get("throughput") or 0.0)), reverse=True)
             e = cands[0]
             end = int(e["end_block"])
@@ -325,8 +349,7 @@ class RpcTransport:
         if self.stage != 0:
             raise RuntimeError("send_prefill should only be called by stage0")
         self.client_cache.pop(session_id, None)
-        md = {"session_id": session_id, "seq_len": int(L), "cur_len": int(L), "is_prefill": True,
-              "max_length": int(max_length), **self.sampling}
+        md = self._session_md(session_id, seq_len=int(L), cur_len=int(L), is_prefill=True, max_length=int(max_length))
         self._get_route(session_id)
         self._last_token = self._run(self._send(session_id, hidden, md, "prefill"))
 
@@ -334,8 +357,8 @@ class RpcTransport:
                          generated_tokens: Optional[List[int]] = None):
         if self.stage != 0:
             raise RuntimeError("send_decode_step should only be called by stage0")
-        md = {"session_id": session_id, "seq_len": 1, "cur_len": int(cur_len), "is_prefill": False,
-              "max_length": int(max_length), "generated_tokens": list(generated_tokens or [])[-50:], **self.sampling}
+        md = self._session_md(session_id, seq_len=1, cur_len=int(cur_len), is_prefill=False,
+                              max_length=int(max_length), generated_tokens=list(generated_tokens or [])[-50:])
         self._get_route(session_id)
         self._last_token = self._run(self._send(session_id, hidden, md, "decode"))
 
@@ -354,8 +377,7 @@ class RpcTransport:
                 pre = int(L) == int(cur)
                 if pre:
                     self.client_cache.pop(sid, None)
-                md = {"session_id": sid, "seq_len": int(L), "cur_len": int(cur), "is_prefill": pre,
-                      "max_length": int(mx), **self.sampling}
+                md = self._session_md(sid, seq_len=int(L), cur_len=int(cur), is_prefill=pre, max_length=int(mx))
                 if not pre:
                     md["generated_tokens"] = list(gen or [])[-50:]
                 coros.append(self._send(sid, hidden, md, "prefill" if pre else "decode"))
@@ -604,6 +626,8 @@ class RpcTransport:
         p = prompts.detach().to("cpu") if prompts is not None else None
         route = list(route or self._fresh_route())
         md = {"stateless": True, "has_prompts": p is not None}
+        if self.active_adapter:  # (servers refuse it: the stateless RPCs run the base model only)
+            md["active_adapter"] = self.active_adapter
         inputs = []
         k = 0
         while k < len(route):
@@ -624,6 +648,8 @@ class RpcTransport:
         p = prompts.detach().to("cpu") if prompts is not None else None
         gp = torch.zeros_like(p) if p is not None else None
         md = {"stateless": True, "has_prompts": p is not None}
+        if self.active_adapter:  # (servers refuse it: the stateless RPCs run the base model only)
+            md["active_adapter"] = self.active_adapter
         route = list(route)
         for k in range(len(route) - 1, -1, -1):
             cur_g, inp = g, inputs[k]

@@ -67,6 +67,8 @@ class Plan:
     superblocks: Optional[torch.Tensor] = None  # [2, NSB] runs of <= 4 blocks (grouped prefill kernel)
     fablocks: Optional[torch.Tensor] = None  # [2, NBF] FA2 prefill workgroup blocks (csrc/attention_fa.hip)
     fa_waves: int = 4                   # waves per FA2 workgroup (ops.fa_plan)
+    lora_slots: Optional[np.ndarray] = None  # int32 [T] adapter slot of every row; None: a base-model step
+    _lora_dev: Optional[torch.Tensor] = None
     _dev: Optional[Tuple[torch.Tensor, torch.Tensor]] = None
     _upload: Optional[object] = None    # callable making the device copies
 
@@ -82,6 +84,12 @@ class Plan:
     @property
     def meta_i32(self) -> torch.Tensor:
         return self._device()[1]
+
+    def lora(self, device):
+        """(device slots int32 [T], host runs) of a LoRA step: what ``_forward_llama`` takes."""
+        if self._lora_dev is None:
+            self._lora_dev = torch.from_numpy(self.lora_slots).to(device, non_blocking=True)
+        return self._lora_dev, ops.lora_runs(self.lora_slots)
 
     @property
     def positions(self):
@@ -166,6 +174,16 @@ class StageExecutor:
             # fits one MI355X resident, so offload is rejected rather than half-supported.
             raise ValueError("CPU offload is not supported for MoE (Mixtral) models: serve them resident")
         self._tp = tp if (tp is not None and getattr(tp, "active", tp.size > 1)) else None
+        # LoRA adapters (StageWeights.load_adapters): dense 16-bit Llama stages, resident, one device
+        self._lora = getattr(weights, "lora", None)
+        if self._lora is not None:
+            for bad, what in ((cfg.model_type == "gpt2", "GPT-2"), (cfg.is_moe, "MoE (Mixtral) models"),
+                              (weights.fp8 or weights.w4, "fp8 or MXFP4 weights"),
+                              (self._tp is not None, "tensor parallelism"), (bool(offload), "CPU offload"),
+                              (ops.gemm_policy() == "hipblaslt", "--gemm hipblaslt (MPAMD_GEMM=hipblaslt)")):
+                if bad:
+                    raise ValueError(f"adapters with {what} are not built")
+        self._lora_graphs: Dict[tuple, "_DecodeGraph"] = {}
         self.cfg = cfg
         self.w = weights
         self.device = torch.device(device)
@@ -363,6 +381,8 @@ class StageExecutor:
                     elif weights.fp8 and weights.layers and not cfg.is_moe:
                         ops.autotune_fp8([(cfg.q_dim + 2 * cfg.kv_dim, H, 0), (H, cfg.q_dim, 0), (2 * F, H, 1),
                                           (H, F, 0)], self.device)
+        if self._lora is not None:
+            self._lora.fold_norms(weights.layers)  # A diag(g) for the layers packed with folded norms
         self._streamer, self._n_stream = None, self.n_layers
         if offload and self.device.type == "cuda":
             self._setup_offload(keep_layers_on_gpu)
@@ -382,21 +402,33 @@ class StageExecutor:
 
     # ================================================================== planning
     def plan(self, seqs: Sequence[Tuple[str, int]], *, reset: Sequence[bool] = (), max_length: Optional[int] = None,
-             starts: Optional[Sequence[int]] = None) -> Plan:
+             starts: Optional[Sequence[int]] = None, adapters: Optional[Sequence[Optional[str]]] = None) -> Plan:
         """Open/extend sessions and build device metadata for a ragged step.
 
         ``seqs``: (session_id, n_tokens) pairs.  ``reset[i]`` clears the session first
         (prefill / replay).  ``starts[i]`` (optional) rewinds a session to that position
-        (Petals' ``start_from_position``).
+        (Petals' ``start_from_position``).  ``adapters[i]``: the LoRA adapter session i runs ("" or
+        None: the base model), set when the session is opened or reset; a later step has to name the
+        same one.  Without ``adapters`` every session keeps its own.
         """
         S = len(seqs)
+        if adapters is not None and len(adapters) != S:
+            raise ValueError(f"adapters names {len(adapters)} sessions, the step has {S}")
+        want = None if adapters is None else [self.adapter_slot(a) for a in adapters]  # (before any session opens)
         sess: List[SessionState] = []
         ntoks = np.empty(S, dtype=np.int32)
         st = np.empty(S, dtype=np.int32)
         for i, (sid, n) in enumerate(seqs):
+            fresh = self.sessions.get(sid) is None
             s = self.sessions.open(sid, max_length)
             if reset and reset[i]:
                 self.sessions.reset(sid)
+                fresh = True
+            if fresh:
+                s.adapter = want[i] if want is not None else -1
+            elif want is not None and want[i] != s.adapter:
+                raise ValueError(f"session {sid[:8]} runs adapter {self.adapter_name(s.adapter)!r}: a step cannot "
+                                 f"switch it to {self.adapter_name(want[i])!r}")
             if starts is not None and starts[i] is not None and starts[i] < s.length:
                 self.sessions.rewind(s, int(starts[i]))
             self.sessions.reserve(s, s.length + int(n))
@@ -437,7 +469,27 @@ class StageExecutor:
             if self._attn_grouped:
                 sb = torch.from_numpy(ops.query_superblocks(ntoks, self.nh // self.nkv)).to(self.device,
                                                                                               non_blocking=True)
-        return Plan(sess, ntoks, st, T, max_ctx, is_decode, n64, n32, qb, sb, fb, fa_waves, _upload=upload)
+        row_slots = None
+        if self._lora is not None and any(s.adapter >= 0 for s in sess):
+            row_slots = np.repeat(np.fromiter((s.adapter for s in sess), dtype=np.int32, count=S), ntoks)
+        return Plan(sess, ntoks, st, T, max_ctx, is_decode, n64, n32, qb, sb, fb, fa_waves, lora_slots=row_slots,
+                    _upload=upload)
+
+    def adapter_slot(self, name: Optional[str]) -> int:
+        """Slot of a hosted adapter; -1 for "" / None (the base model).  Unknown: ``KeyError("adapter X not found")``."""
+        if not name:
+            return -1
+        if self._lora is None:
+            raise KeyError(f"adapter {name} not found")
+        return self._lora.slot(name)
+
+    def adapter_name(self, slot: int) -> str:
+        return self._lora.names[slot] if (self._lora is not None and slot >= 0) else ""
+
+    @property
+    def adapters(self) -> List[str]:
+        """Names of the hosted adapters, in slot order (announced by the server)."""
+        return list(self._lora.names) if self._lora is not None else []
 
     def commit(self, plan: Plan) -> None:
         for s, n in zip(plan.sessions, plan.ntoks):
@@ -488,7 +540,7 @@ class StageExecutor:
         return (torch.tensor(rows, dtype=torch.long, device=self.device),
                 torch.cat(vals, 1).to(self.device, self.dtype))
 
-    def _forward_chunked(self, seqs, x, reset: Sequence[bool] = (), starts=None, max_length=None):
+    def _forward_chunked(self, seqs, x, reset: Sequence[bool] = (), starts=None, max_length=None, adapters=None):
         C = self.max_tokens
         pieces = []  # (seq index, token offset within the seq, count, offset into x)
         xoff = 0
@@ -520,7 +572,8 @@ class StageExecutor:
             sub_reset = [bool(reset[i]) if (reset and off == 0) else False for (i, off, c, _) in ch]
             sub_starts = [(starts[i] if (starts is not None and off == 0) else None) for (i, off, c, _) in ch]
             xs = torch.cat([x[xo:xo + c] for (_, _, c, xo) in ch])
-            out = self.forward(sub, xs, reset=sub_reset, starts=sub_starts, max_length=max_length)
+            sub_ad = None if adapters is None else [adapters[i] for (i, _, _, _) in ch]
+            out = self.forward(sub, xs, reset=sub_reset, starts=sub_starts, max_length=max_length, adapters=sub_ad)
             if self.is_last:
                 for r, (i, off, c, _) in enumerate(ch):
                     if off + c == int(seqs[i][1]):
@@ -543,7 +596,17 @@ class StageExecutor:
             ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
             ev[0].record()
         self.last_graphed = self.last_hooked = False
-        if prompt is None and self.use_graphs and plan.is_decode and plan.T <= self.graph_max_batch:
+        lora = None
+        if plan.lora_slots is not None:
+            if prompt is not None:
+                raise ValueError("adapters with deep prompts are not built: a session runs one or the other")
+            lora = plan.lora  # (the device copy is made by the eager branch only: a graph stages its own)
+        if lora is not None and self.use_graphs and plan.is_decode and \
+                plan.T <= min(self.graph_max_batch, 64) and self._lora_packed_ok(self._bucket(plan.T)):
+            out = self._run_lora_graph(plan, x)
+            self.last_graphed = True
+        elif lora is None and prompt is None and self.use_graphs and plan.is_decode and \
+                plan.T <= self.graph_max_batch:
             hooked = self.graph_hook is not None and hook_owner is not None and hook_owner is self._hook_owner
             out = self._run_graph(plan, x, hooked, owner=hook_owner)
             self.last_graphed, self.last_hooked = True, hooked
@@ -556,7 +619,7 @@ class StageExecutor:
             try:
                 out = self._forward_llama(x, plan.positions, plan.slots, plan.q_seq, plan.q_ctx, plan.last_rows,
                                           plan.T, plan.max_ctx, None, qblocks=plan.qblocks, prompt=prompt,
-                                          decode=plan.is_decode)
+                                          decode=plan.is_decode, lora=lora(self.device) if lora else None)
             finally:
                 self._cur_sb = None
                 self._cur_fb = None
@@ -668,7 +731,10 @@ class StageExecutor:
         return self._attend(qkv, kc, vc, q_seq, q_ctx, out, ws, ps, np_, packed, qblocks, max_ctx)
 
     def _forward_llama(self, x, positions, slots, q_seq, q_ctx, last_rows, T, max_ctx, attn_part,
-                       bufs: Optional[dict] = None, qblocks=None, prompt=None, decode=False):
+                       bufs: Optional[dict] = None, qblocks=None, prompt=None, decode=False, lora=None):
+        """``lora``: (device slots int32 [T], host runs or None) of a step with adapter rows - the
+        packed branch (norm kernels, batched LoRA kernels after each targeted projection) up to 64
+        rows, else the row-major branch with the torch form by runs; None: a base-model step."""
         cfg, w = self.cfg, self.w
         H, eps = cfg.hidden_size, cfg.rms_norm_eps
         dev, dt = self.device, self.dtype
@@ -676,8 +742,10 @@ class StageExecutor:
         if bufs is None:
             bufs = {}
         e = lambda name, shape, dtype=dt: bufs.get(name) if name in bufs else torch.empty(shape, dtype=dtype, device=dev)  # noqa: E731
-        fp8_dec = prompt is None and self._fp8_ok(T)
-        fused_dec = (not fp8_dec and prompt is None and self._fused and self.n_layers > 0 and
+        lo = self._lora if lora is not None else None
+        lora_pk = lo is not None and prompt is None and T <= 64 and self._packed_ok(T) and self._lora_packed_ok(T)
+        fp8_dec = lo is None and prompt is None and self._fp8_ok(T)
+        fused_dec = (lo is None and not fp8_dec and prompt is None and self._fused and self.n_layers > 0 and
                      (T <= 64 and (self._w8 or self._w4_ok(T) or self._packed_ok(T)) or
                       (not self._w8 and not self._w4 and self._fused_wide_ok(T))))
         if self.is_first and not (fused_dec and self._fused_entry and x.dim() == 1 and x.is_contiguous()):
@@ -782,7 +850,7 @@ class StageExecutor:
                 gemm(xr, L, "gate_up", out=act, epilogue=1, out_packed=True, ss_in=ss_post, eps=eps)
                 gemm(act, L, "down", out=res, epilogue=3, residual=res, ap_out=xr, ss_out=ss_in, ss_zero=ss_post)
             mlp = None
-        elif prompt is None and self._moe_w8 and 0 < T <= 64:
+        elif lo is None and prompt is None and self._moe_w8 and 0 < T <= 64:
             # fp8 MoE decode path: packed activations, norm kernels with the real weights, qkv / o on
             # the W8A16 GEMM, the experts in two grouped launches (_moe_mlp_w8)
             pk = ops.packed_numel
@@ -801,13 +869,47 @@ class StageExecutor:
                 ops.linear_w8(attn, L.o_w8, L.o_ws, T, out=o)
                 ops.rmsnorm(o, L.post_norm, eps, out=xn, residual=res, mode=1, packed=True)
                 self._moe_mlp_w8(L, xn, T, mlp, act, e)
-        elif prompt is None and self._packed_ok(T):
+        elif prompt is None and self._packed_ok(T) and (lo is None or lora_pk):
             # decode path: activations feeding a GEMM stay in the packed MFMA-fragment layout
             pk = ops.packed_numel
             xn = e("xn_p", (pk(T, H),))
             attn = e("attn_p", (pk(T, cfg.q_dim),))
             act = e("act_p", (pk(T, cfg.intermediate_size),))
+
+            def lora_add(lp, xp, y, unit=False):
+                # y += B (scale A x) for the rows with an adapter: two launches, slots read on the device
+                if lp is not None:
+                    t = ops.lora_shrink(xp, lp.a_for(unit), lo.scale, lora[0], T,
+                                        out=e(f"lora_t{lp.A.shape[1]}", (T, lp.A.shape[1]), torch.float32))
+                    ops.lora_expand(t, lp.B, lora[0], y)
+
             for li, L in self._iter_layers(_PACKED_FIELDS):
+                LL = lo.layers[li] if lo is not None else None
+                if LL is not None:
+                    # a LoRA step: the same launches, plus shrink + expand on the row-major output of
+                    # every targeted projection (a targeted gate/up leaves its SwiGLU epilogue)
+                    unit = bool(getattr(L, "folded", False))
+                    g_in, g_post = (self._unit_norm(), self._unit_norm()) if unit else (L.input_norm, L.post_norm)
+                    ops.rmsnorm(h if li == 0 else mlp, g_in, eps, out=xn, residual=res, mode=2 if li == 0 else 1,
+                                packed=True)
+                    ops.linear(xn, L.qkv, out=qkv, wp=L.qkv_p, a_rows=T)
+                    lora_add(LL.qkv, xn, qkv, unit)
+                    kc, vc = self.cache.layer(li)
+                    self._rope_attend(qkv, positions, slots, kc, vc, q_seq, q_ctx, attn, ws, ps, np_, True, qblocks,
+                                      max_ctx, decode)
+                    ops.linear(attn, L.o, out=o, wp=L.o_p, a_rows=T)
+                    lora_add(LL.o, attn, o)
+                    ops.rmsnorm(o, g_post, eps, out=xn, residual=res, mode=1, packed=True)
+                    if LL.gate_up is not None:
+                        gu = ops.linear(xn, L.gate_up, out=e("gu", (T, 2 * cfg.intermediate_size)), wp=L.gate_up_p,
+                                        a_rows=T)
+                        lora_add(LL.gate_up, xn, gu, unit)
+                        ops.pack_act(ops.swiglu(gu, out=e("act", (T, cfg.intermediate_size))), out=act)
+                    else:
+                        ops.linear(xn, L.gate_up, out=act, epilogue=1, wp=L.gate_up_p, a_rows=T, out_packed=True)
+                    ops.linear(act, L.down, out=mlp, wp=L.down_p, a_rows=T)
+                    lora_add(LL.down, act, mlp)
+                    continue
                 # weights packed for the fused path (> 64 rows here) carry the norm weights in
                 # their columns: normalise with a unit weight
                 g_in, g_post = (self._unit_norm(), self._unit_norm()) if getattr(L, "folded", False) else \
@@ -833,8 +935,11 @@ class StageExecutor:
             xn = e("xn", (T, H))
             attn = e("attn", (T, cfg.q_dim))
             act = e("act", (T, cfg.intermediate_size))
-            fold_native = self._folded_native(T)
+            # (a LoRA step keeps the real norm weights and the unfolded row-major weights: its gate/up
+            # may run with epilogue 0, which the per-step fold decision does not cover)
+            fold_native = lo is None and self._folded_native(T)
             for li, L in self._iter_layers(_DENSE_FIELDS):
+                LL = lo.layers[li] if lo is not None else None
                 # W8A16 / MXFP4 layers' only weights carry the norm weights folded in (prepare_w8a16,
                 # quantize_mxfp4).
                 # bf16 layers packed for the fused path carry them in qkv_p / gate_up_p only: when
@@ -857,17 +962,28 @@ class StageExecutor:
                 # (fp8 MoE layers dequantize into the executor's dtype: an fp32 CPU stage stays fp32)
                 wdt = dt if L.moe else torch.bfloat16
                 ops.linear(xn, L.dense("qkv", wdt), out=qkv, wp=qkv_p)
+                if LL is not None and LL.qkv is not None:
+                    ops.lora_update(xn, qkv, LL.qkv.A, LL.qkv.B, lo.scale, lora[1])
                 kc, vc = self.cache.layer(li)
                 self._rope_attend(qkv, positions, slots, kc, vc, q_seq, q_ctx, attn, ws, ps, np_, False, qblocks,
                                   max_ctx, decode)
                 ops.linear(attn, L.dense("o", wdt), out=o, wp=L.o_p)
+                if LL is not None and LL.o is not None:
+                    ops.lora_update(attn, o, LL.o.A, LL.o.B, lo.scale, lora[1])
                 self._ar(o)
                 ops.rmsnorm(o, g_post, eps, out=xn, residual=res, mode=1)
                 if L.moe:
                     self._moe_mlp(L, xn, T, mlp, act, e, packed=False)
                     continue
-                ops.linear(xn, L.dense("gate_up"), out=act, epilogue=1, wp=gu_p)
+                if LL is not None and LL.gate_up is not None:  # epilogue 0, the update, then SwiGLU
+                    gu = ops.linear(xn, L.dense("gate_up"), out=e("gu", (T, 2 * cfg.intermediate_size)), wp=gu_p)
+                    ops.lora_update(xn, gu, LL.gate_up.A, LL.gate_up.B, lo.scale, lora[1])
+                    ops.swiglu(gu, out=act)
+                else:
+                    ops.linear(xn, L.dense("gate_up"), out=act, epilogue=1, wp=gu_p)
                 ops.linear(act, L.dense("down"), out=mlp, wp=L.down_p)
+                if LL is not None and LL.down is not None:
+                    ops.lora_update(act, mlp, LL.down.A, LL.down.B, lo.scale, lora[1])
                 self._ar(mlp)
         hout = res if mlp is None else ops.add(res, mlp, out=e("hout", (T, H)))
         if not self.is_last:
@@ -1223,6 +1339,14 @@ class StageExecutor:
         return all(ops.w4_gemm_ok(M, N, K, epi) for N, K, epi in
                    ((cfg.q_dim + 2 * cfg.kv_dim, H, 0), (H, cfg.q_dim, 3), (2 * F, H, 1), (H, F, 3)))
 
+    def _lora_packed_ok(self, M: int) -> bool:
+        """A LoRA step of M rows on the packed branch: the batched kernels cover every targeted projection."""
+        if self._lora is None or self.device.type != "cuda" or not 0 < M <= 64:
+            return False
+        from ..models.adapters import fused_shape
+
+        return all(ops.lora_ok(M, *fused_shape(self.cfg, p), R) for p, R in self._lora.ranks.items() if R)
+
     def _packed_ok(self, M: int) -> bool:
         """Packed-activation decode path: GPU, native GEMM allowed, all projections packed; 65..256
         rows when the balanced ring kernel covers every projection of the layer (dense Llama)."""
@@ -1326,6 +1450,20 @@ class StageExecutor:
             read.done_ev = g.done_ev
         return out
 
+    def _run_lora_graph(self, plan: Plan, x: torch.Tensor) -> torch.Tensor:
+        """Replay (capturing first) the LoRA decode graph of the step's bucket.  LoRA graphs live in
+        ``_lora_graphs`` under the same key tuple as the base graphs: one graph serves every mix of
+        adapters, since the row slots are data of the replay (the graph's metadata blob)."""
+        key = self._graph_key(plan.T, plan.max_ctx, False)
+        g = self._lora_graphs.get(key)
+        if g is None:
+            if self._graph_pool is None:
+                self._graph_pool = torch.cuda.graph_pool_handle()
+            g = self._lora_graphs[key] = _DecodeGraph(self, key[0], (key[1], key[2]), self._graph_pool, lora=True)
+        out = g.replay(plan, x)
+        g.mark_replayed()
+        return out
+
     def graph_input(self, T: int, max_ctx: int, owner=None):
         """Receive target of a stage hop (``PipelineServingEngine``): the static input of the decode
         graph the owner's NEXT step of ``T`` rows will replay, and the event after which that buffer
@@ -1418,6 +1556,7 @@ class StageExecutor:
 
     def clear_graphs(self):
         self._graphs.clear()
+        self._lora_graphs.clear()
 
 
 class _DecodeGraph:
@@ -1426,19 +1565,21 @@ class _DecodeGraph:
     Its metadata lives in ONE device blob (positions, slots | q_seq, q_ctx, last_rows) that a
     replay refills with a single host-to-device copy from a double-buffered pinned staging
     blob, padded for the bucket (padding rows: slot -1, context 0): round 1 issued six small
-    copies / fills per step (profiles/r2_decode_step_*.txt)."""
+    copies / fills per step (profiles/r2_decode_step_*.txt).  A LoRA graph (``lora``) appends the
+    rows' adapter slots, int32 [B] (padding rows: -1), to the same blob."""
 
-    def __init__(self, ex: StageExecutor, B: int, part: Tuple[int, int], pool, hook=None):
+    def __init__(self, ex: StageExecutor, B: int, part: Tuple[int, int], pool, hook=None, lora: bool = False):
         self.ex, self.B, self.part = ex, B, part
         dev, H, dt = ex.device, ex.cfg.hidden_size, ex.dtype
         if ex.is_first:
             self.x = torch.zeros(B, dtype=torch.long, device=dev)
         else:
             self.x = torch.zeros(B, H, dtype=dt, device=dev)
-        nbytes = 16 * B + 12 * B  # int64 [2, B] + int32 [3 B]
+        nbytes = 16 * B + 12 * B + (4 * B if lora else 0)  # int64 [2, B] + int32 [3 B] (+ int32 [B] slots)
         self.blob = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
         self.meta64 = self.blob[: 16 * B].view(torch.int64).view(2, B)
-        self.meta32 = self.blob[16 * B:].view(torch.int32)
+        self.meta32 = self.blob[16 * B: 28 * B].view(torch.int32)
+        self.lora_slots = self.blob[28 * B:].view(torch.int32) if lora else None
         self._stage = [torch.zeros(nbytes, dtype=torch.uint8, pin_memory=True) for _ in range(2)]
         self._stage_ev = [None, None]
         self._k = 0
@@ -1448,7 +1589,8 @@ class _DecodeGraph:
         h64[0] = 0
         h64[1] = -1
         h32[:] = 0
-        h32[2 * B:] = np.arange(B, dtype=np.int32)
+        h32[2 * B:3 * B] = np.arange(B, dtype=np.int32)
+        h32[3 * B:] = -1  # (a LoRA graph's row slots)
         self.blob.copy_(self._stage[0])
         self._stage[1].copy_(self._stage[0])
         if ex.gqa_decode_mfma or ex.gqa_decode_mfma_f8:
@@ -1457,11 +1599,12 @@ class _DecodeGraph:
         self.done_ev = None  # end of the last replay on the compute stream (graph_input)
         args = (self.x, self.meta64[0], self.meta64[1], self.meta32[:B], self.meta32[B:2 * B], self.meta32[2 * B:], B,
                 0, part)
+        kw = {"lora": (self.lora_slots, None)} if lora else {}
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
             for _ in range(2):  # warm up (allocator, hipBLASLt heuristics) outside capture
-                ex._forward_llama(*args, decode=True)
+                ex._forward_llama(*args, decode=True, **kw)
         torch.cuda.current_stream().wait_stream(s)
         self.graph = torch.cuda.CUDAGraph()
         # Python's cyclic collector must not run inside the capture: a dead executor and its graphs
@@ -1475,7 +1618,7 @@ class _DecodeGraph:
             # thread-local capture: another thread's stream work (a channel receive posted outside the
             # executor lock) neither breaks this capture nor fails because of it
             with torch.cuda.graph(self.graph, pool=pool, capture_error_mode="thread_local"):
-                self.out = ex._forward_llama(*args, decode=True)
+                self.out = ex._forward_llama(*args, decode=True, **kw)
                 if hook is not None:  # recorded only: the warm-up runs above never call it
                     hook(self.out)
         finally:
@@ -1499,6 +1642,9 @@ class _DecodeGraph:
         h32[b:B] = 0
         h32[B:B + b] = plan.h32[b:2 * b]
         h32[B + b:2 * B] = 0
+        if self.lora_slots is not None:
+            h32[3 * B:3 * B + b] = plan.lora_slots
+            h32[3 * B + b:] = -1
         self.blob.copy_(self._stage[k], non_blocking=True)
         ev = torch.cuda.Event()
         ev.record()

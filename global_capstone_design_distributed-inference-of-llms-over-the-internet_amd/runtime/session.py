@@ -37,6 +37,7 @@ class SessionState:
     last_used: float = dataclasses.field(default_factory=time.monotonic)
     generated: List[int] = dataclasses.field(default_factory=list)
     step: int = 0
+    adapter: int = -1  # LoRA adapter slot of the session (models/adapters.py); -1: the base model
 
 
 class SessionManager:
@@ -141,6 +142,7 @@ class SessionManager:
                 d.pages = list(new)
                 self._dirty = True
             d.first_page = s.first_page
+            d.adapter = s.adapter
             d.length = s.length
             d.generated = list(s.generated)
             d.last_used = time.monotonic()
