@@ -8,8 +8,17 @@ Replaces the reference's Stage0 / StageSegment / StageLast modules
 * a paged KV cache written in place by the fused RoPE kernel,
 * ragged batches: any mix of sessions, each contributing ``n_tokens`` (prefill chunks,
   decode steps, replays) executed as ONE forward over the concatenated tokens,
-* per layer 7 launches on the decode path: add+RMSNorm, QKV GEMM, RoPE+KV write,
-  paged attention, O GEMM, add+RMSNorm, gate/up GEMM with fused SwiGLU, down GEMM,
+* one layer loop per step, chosen by ``StageExecutor._step_path`` from the step's row count T (prefill chunks
+  and decode steps alike), its deep prompt and its adapters; the first that applies:
+  - "w8a8": fp8 weights under MPAMD_FP8_MODE=w8a8, T <= 64: fp8 MFMA GEMMs, activations quantized per row;
+  - "fused" (the default decode path): dense bf16 / W8A16 / MXFP4 stages, T <= 64 (bf16: up to 256 where the
+    wide kernels cover it): 5 launches per layer - qkv, RoPE + attention, o, gate/up, down; no norm kernels,
+    the GEMM epilogues carry the residual stream and its row statistics;
+  - "moe_w8": fp8 Mixtral, T <= 64: packed activations, norm kernels, W8A16 qkv / o, grouped experts;
+  - "packed": other steps of T <= 256 with every projection packed for the native GEMMs (no fused path,
+    Mixtral, 65..256 rows, LoRA steps of <= 64 rows): 7 launches per layer - add+RMSNorm, qkv, RoPE +
+    attention, o, add+RMSNorm, gate/up with SwiGLU, down - on activations in the MFMA-fragment layout;
+  - "dense": everything else (CPU, prefill, deep prompts, --gemm hipblaslt): those 7 on row-major activations;
 * decode steps replayed from hipGraphs captured per (batch bucket, context bucket);
 * the last stage applies the final norm and ``lm_head`` to the LAST token of each
   sequence only (the reference projects every prefill position, src/llama_partition.py:470).
@@ -25,6 +34,7 @@ import logging
 import math
 import os
 import threading
+import types
 import weakref
 from typing import Dict, List, Optional, Sequence, Tuple
 
@@ -52,7 +62,7 @@ class Plan:
     """Host-side description of one ragged step.
 
     ``h64`` / ``h32`` are the step's metadata in pinned host memory; the device copies
-    (``meta_i64`` / ``meta_i32``) are made on first use.  A graph-replayed decode step never
+    (``meta()``) are made on first use.  A graph-replayed decode step never
     touches them: it stages the padded metadata of its batch bucket in ONE host-to-device
     copy of its own (``_DecodeGraph.replay``)."""
     sessions: List[SessionState]
@@ -72,44 +82,52 @@ class Plan:
     _dev: Optional[Tuple[torch.Tensor, torch.Tensor]] = None
     _upload: Optional[object] = None    # callable making the device copies
 
-    def _device(self):
+    def meta(self):
+        """(positions, slots, q_seq, q_ctx, last_rows) on the device: the metadata tensors of a ``_Step``."""
         if self._dev is None:
             self._dev = self._upload()
-        return self._dev
-
-    @property
-    def meta_i64(self) -> torch.Tensor:
-        return self._device()[0]
-
-    @property
-    def meta_i32(self) -> torch.Tensor:
-        return self._device()[1]
+        (i64, i32), T = self._dev, self.T
+        return i64[0], i64[1], i32[:T], i32[T:2 * T], i32[2 * T:]
 
     def lora(self, device):
-        """(device slots int32 [T], host runs) of a LoRA step: what ``_forward_llama`` takes."""
+        """(device slots int32 [T], host runs) of a LoRA step: ``_Step.lora``."""
         if self._lora_dev is None:
             self._lora_dev = torch.from_numpy(self.lora_slots).to(device, non_blocking=True)
         return self._lora_dev, ops.lora_runs(self.lora_slots)
 
-    @property
-    def positions(self):
-        return self.meta_i64[0]
 
-    @property
-    def slots(self):
-        return self.meta_i64[1]
+@dataclasses.dataclass
+class _Step:
+    """What one forward pass of a Llama-family stage reads: built by ``run`` from a ``Plan`` and by a
+    ``_DecodeGraph`` from its static tensors.  ``_begin`` fills in ``part`` (where None) and ``ws``."""
+    x: torch.Tensor                     # token ids [T] (first stage) or hidden [T, H]
+    positions: torch.Tensor
+    slots: torch.Tensor
+    q_seq: torch.Tensor
+    q_ctx: torch.Tensor
+    last_rows: torch.Tensor
+    T: int
+    max_ctx: int
+    decode: bool
+    device: torch.device                # where, and in which dtype, ``buf`` allocates
+    dtype: torch.dtype
+    part: Optional[Tuple[int, int]] = None  # (part_size, num_parts) of the split-K attention kernels
+    ws: Optional[torch.Tensor] = None
+    qblocks: Optional[torch.Tensor] = None      # prefill steps: Plan.qblocks / superblocks / fablocks / fa_waves
+    superblocks: Optional[torch.Tensor] = None
+    fablocks: Optional[torch.Tensor] = None
+    fa_waves: int = 4
+    prompt: Optional[tuple] = None      # deep prompt (rows [R], values [n_layers, R, H])
+    lora: Optional[tuple] = None        # (device slots int32 [T], host runs or None); None: a base-model step
+    bufs: dict = dataclasses.field(default_factory=dict)  # named buffers the caller keeps (else allocated)
 
-    @property
-    def q_seq(self):
-        return self.meta_i32[: self.T]
+    def buf(self, name: str, shape, dtype=None) -> torch.Tensor:
+        if name in self.bufs:
+            return self.bufs[name]
+        return torch.empty(shape, dtype=dtype or self.dtype, device=self.device)
 
-    @property
-    def q_ctx(self):
-        return self.meta_i32[self.T: 2 * self.T]
 
-    @property
-    def last_rows(self):
-        return self.meta_i32[2 * self.T:]
+_NO_LORA = types.SimpleNamespace(qkv=None, o=None, gate_up=None, down=None)  # a base step's adapter layer: no target
 
 
 class _Pinned:
@@ -264,7 +282,6 @@ class StageExecutor:
         # prefill: up to 4 query blocks of a sequence per workgroup share each K/V step
         # (csrc/attention_mfma.hip attn_mfma_grp_kernel)
         self._attn_grouped = True
-        self._cur_sb = None
         # prefill steps with a row-major attention output: the FA2 kernel on 32x32x16 MFMA with
         # transposed LDS reads of V (csrc/attention_fa.hip); other shapes keep the 16x16 one
         self._attn_fa = self._attn_mfma_prefill and \
@@ -275,8 +292,6 @@ class StageExecutor:
         # sliding window ("attend"): row-major prefill steps past the window on the FA2 kernel's windowed
         # form (bf16 and fp8 caches); MPAMD_WINDOW_FA=0 puts them back on the flash-decoding rows
         self.window_fa = bool(self.window) and self._attn_fa and os.environ.get("MPAMD_WINDOW_FA", "1") != "0"
-        self._cur_fb = None
-        self._cur_fw = 4
         self._n_cu = torch.cuda.get_device_properties(self.device).multi_processor_count \
             if self.device.type == "cuda" else 256
         # decode steps on the flash-decoding kernel fold RoPE + the KV page write into it
@@ -613,16 +628,10 @@ class StageExecutor:
         elif self.cfg.model_type == "gpt2":
             out = self._forward_gpt2(plan, x, prompt=prompt)
         else:
-            self._cur_sb = plan.superblocks
-            self._cur_fb = plan.fablocks
-            self._cur_fw = plan.fa_waves
-            try:
-                out = self._forward_llama(x, plan.positions, plan.slots, plan.q_seq, plan.q_ctx, plan.last_rows,
-                                          plan.T, plan.max_ctx, None, qblocks=plan.qblocks, prompt=prompt,
-                                          decode=plan.is_decode, lora=lora(self.device) if lora else None)
-            finally:
-                self._cur_sb = None
-                self._cur_fb = None
+            out = self._forward_llama(_Step(
+                x, *plan.meta(), plan.T, plan.max_ctx, plan.is_decode, self.device, self.dtype, qblocks=plan.qblocks,
+                superblocks=plan.superblocks, fablocks=plan.fablocks, fa_waves=plan.fa_waves, prompt=prompt,
+                lora=lora(self.device) if lora else None))
         if ev is not None:
             ev[1].record()
             ev[1].synchronize()
@@ -635,28 +644,28 @@ class StageExecutor:
         hipGraph captures reuse the same buffer."""
         qb = self._decode_qb.get(T)
         if qb is None:
-            import numpy as np
-
             qb = torch.from_numpy(np.stack([np.arange(T), np.ones(T)]).astype(np.int32)).to(self.device)
             self._decode_qb[T] = qb
         return qb
 
-    def _attend(self, qkv, kc, vc, q_seq, q_ctx, out, ws, ps, np_, packed, qblocks, max_ctx):
-        """Paged attention: MFMA flash attention for prefill blocks (``qblocks``) and GQA decode,
-        else the flash-decoding kernel.  An fp8 KV cache has the fp8 forms of the MFMA GQA decode
+    def _attend(self, st: _Step, qkv, kc, vc, out, packed):
+        """Paged attention of step ``st``: ``qkv`` against one layer's cache pair ``kc`` / ``vc`` into ``out``
+        (``packed``: in the packed layout).  MFMA flash attention for prefill blocks (``st.qblocks``) and GQA
+        decode, else the flash-decoding kernel.  An fp8 KV cache has the fp8 forms of the MFMA GQA decode
         kernel, of the FA2 prefill kernel (row-major output) and of the flash-decoding kernel; its
         other prefill blocks (packed output, shapes outside ``fa_ok``) run on the latter as
         per-query causal rows (``qblocks`` is ignored).  Under a sliding window a prefill step with a
         row past the window runs the FA2 kernel's windowed form where FA2 covers it, else those rows."""
-        table = self.sessions.table_dev
-        f8, win, prefill = self._kv_fp8, self.window, qblocks is not None
+        (ps, np_), max_ctx = st.part, st.max_ctx
+        f8, win, prefill = self._kv_fp8, self.window, st.qblocks is not None
         # FA2 covers a prefill step with blocks (plan.fablocks) and a row-major output
-        fa = prefill and self._cur_fb is not None and not packed
+        fa = prefill and st.fablocks is not None and not packed
+        # what every attention op takes: its leading arguments, the head geometry, its trailing keywords
+        a, hs = (qkv, kc, vc, self.sessions.table_dev, st.q_seq, st.q_ctx), (self.nh, self.nkv, self.scale)
+        kw = dict(out=out, workspace=st.ws, max_ctx=max_ctx)
 
         def flash():
-            return ops.paged_attention(qkv, kc, vc, table, q_seq, q_ctx, self.nh, self.nkv, self.scale, out=out,
-                                       workspace=ws, part_size=ps, num_parts=np_, packed=packed,
-                                       window=win, max_ctx=max_ctx)
+            return ops.paged_attention(*a, *hs, part_size=ps, num_parts=np_, packed=packed, window=win, **kw)
 
         # sliding window: the decode kernels take it, and so does the FA2 prefill kernel's windowed form
         # (row-major steps it covers: window_fa).  The grouped MFMA kernel has none: a prefill step keeps
@@ -665,23 +674,18 @@ class StageExecutor:
         if win and prefill and max_ctx > win:
             if self.window_fa and fa and (self.prefill_fa_f8 if f8 else self._attn_fa):
                 op = ops.attention_fa_window_f8 if f8 else ops.attention_fa_window
-                return op(qkv, kc, vc, table, q_seq, q_ctx, self._cur_fb, self.nh, self.nkv, self.scale, win, out=out,
-                          workspace=ws, max_ctx=max_ctx, waves=self._cur_fw)
+                return op(*a, st.fablocks, *hs, win, waves=st.fa_waves, **kw)
             return flash()
         if not prefill and (self.gqa_decode_mfma_f8 if f8 else self.gqa_decode_mfma) and self.device.type == "cuda":
             ps2, np2 = self._parts128(ps, np_)
             op = ops.attention_mfma_f8 if f8 else ops.attention_mfma
-            return op(qkv, kc, vc, table, q_seq, q_ctx, self.decode_qblocks(qkv.shape[0]), self.nh, self.nkv,
-                      self.scale, out=out, workspace=ws, part_size=ps2, num_parts=np2, packed=packed, window=win,
-                      max_ctx=max_ctx)
+            return op(*a, self.decode_qblocks(qkv.shape[0]), *hs, part_size=ps2, num_parts=np2, packed=packed,
+                      window=win, **kw)
         if fa and (self.prefill_fa_f8 or not f8):
             op = ops.attention_fa_f8 if f8 else ops.attention_fa
-            return op(qkv, kc, vc, table, q_seq, q_ctx, self._cur_fb, self.nh, self.nkv, self.scale, out=out,
-                      workspace=ws, max_ctx=max_ctx, waves=self._cur_fw)
+            return op(*a, st.fablocks, *hs, waves=st.fa_waves, **kw)
         if prefill and not f8:
-            return ops.attention_mfma(qkv, kc, vc, table, q_seq, q_ctx, qblocks, self.nh, self.nkv, self.scale,
-                                      out=out, workspace=ws, max_ctx=max_ctx, packed=packed,
-                                      superblocks=self._cur_sb)
+            return ops.attention_mfma(*a, st.qblocks, *hs, packed=packed, superblocks=st.superblocks, **kw)
         return flash()
 
     @staticmethod
@@ -701,310 +705,305 @@ class StageExecutor:
         return bool(self.qkv_fold_by_bucket.get(self._bucket(T), False)) and \
             ops.rwk_split(T, cfg.q_dim + 2 * cfg.kv_dim, cfg.hidden_size, bool(self._w8)) > 0
 
-    def _rope_attend(self, qkv, positions, slots, kc, vc, q_seq, q_ctx, out, ws, ps, np_, packed, qblocks, max_ctx,
-                     decode, qkv_part=None, mx_out=None, mx_used=None):
-        """RoPE + KV write + attention.  Decode steps that run on the flash-decoding kernel do all
-        three in one launch (ops.paged_attention_rope); everything else keeps rope_kv_write.
-        ``qkv_part``: q / k / v as the qkv GEMM's split-K slabs (decode RoPE paths only).  ``mx_out``:
-        (ax, as_) MX buffers the GQA kernel writes instead of ``out`` when it can (one part, packed,
-        head_dim 128); it then appends True to ``mx_used``."""
-        if decode and qblocks is None and self._fuse_rope:
-            f8, table = self._kv_fp8, self.sessions.table_dev
-            if (self.gqa_decode_mfma_f8 if f8 else self.gqa_decode_mfma) and self.device.type == "cuda":
-                ps2, np2 = self._parts128(ps, np_)
-                kw = {}
-                if not f8:  # (an fp8 cache has no MX epilogue)
-                    kw["mx_out"] = mx_out if (mx_out is not None and np2 == 1 and packed and self.D == 128) else None
-                    if kw["mx_out"] is not None and mx_used is not None:
-                        mx_used.append(True)
-                op = ops.attention_mfma_rope_f8 if f8 else ops.attention_mfma_rope
-                return op(qkv, kc, vc, table, q_seq, q_ctx, self.decode_qblocks(qkv.shape[0]), positions, self.cos,
-                          self.sin, slots, self.nh, self.nkv, self.scale, out=out, workspace=ws, part_size=ps2,
-                          num_parts=np2, packed=packed, qkv_part=qkv_part, window=self.window, max_ctx=max_ctx, **kw)
-            return ops.paged_attention_rope(qkv, kc, vc, table, q_seq, q_ctx, positions, self.cos, self.sin, slots,
-                                            self.nh, self.nkv, self.scale, out=out, workspace=ws, part_size=ps,
-                                            num_parts=np_, packed=packed, qkv_part=qkv_part, window=self.window,
-                                            max_ctx=max_ctx)
-        if qkv_part is not None:
-            raise RuntimeError("qkv partial slabs need a fused RoPE decode attention path")
-        ops.rope_kv_write(qkv, positions, self.cos, self.sin, kc, vc, slots, self.nh, self.nkv)
-        return self._attend(qkv, kc, vc, q_seq, q_ctx, out, ws, ps, np_, packed, qblocks, max_ctx)
+    def _rope_attend(self, st: _Step, qkv, kc, vc, out, packed, qkv_part=None, mx_out=None):
+        """RoPE + KV write + attention of step ``st`` (``qkv``, ``kc`` / ``vc``, ``out``, ``packed``: as ``_attend``).
+        Decode steps do all three in one launch (ops.paged_attention_rope on the flash-decoding kernel,
+        ops.attention_mfma_rope on the MFMA GQA one); everything else keeps rope_kv_write.  ``qkv_part``: q / k / v
+        as the qkv GEMM's split-K slabs (decode RoPE paths only).  ``mx_out``: (ax, as_) MX buffers the MFMA GQA
+        kernel writes INSTEAD of ``out``: passed only where it runs and can (one part, head_dim 128)."""
+        one_launch = st.decode and st.qblocks is None and self._fuse_rope
+        f8, (ps, np_) = self._kv_fp8, st.part
+        a = (qkv, kc, vc, self.sessions.table_dev, st.q_seq, st.q_ctx)
+        rope = (st.positions, self.cos, self.sin, st.slots, self.nh, self.nkv, self.scale)
+        kw = dict(out=out, workspace=st.ws, packed=packed, qkv_part=qkv_part, window=self.window, max_ctx=st.max_ctx)
+        if one_launch and (self.gqa_decode_mfma_f8 if f8 else self.gqa_decode_mfma) and self.device.type == "cuda":
+            ps2, np2 = self._parts128(ps, np_)
+            if not f8:  # (an fp8 cache has no MX epilogue)
+                kw["mx_out"] = mx_out
+            op = ops.attention_mfma_rope_f8 if f8 else ops.attention_mfma_rope
+            return op(*a, self.decode_qblocks(qkv.shape[0]), *rope, part_size=ps2, num_parts=np2, **kw)
+        if mx_out is not None or (qkv_part is not None and not one_launch):
+            raise RuntimeError("qkv partial slabs and an MX output need a fused RoPE decode attention kernel")
+        if one_launch:
+            return ops.paged_attention_rope(*a, *rope, part_size=ps, num_parts=np_, **kw)
+        ops.rope_kv_write(qkv, st.positions, self.cos, self.sin, kc, vc, st.slots, self.nh, self.nkv)
+        return self._attend(st, qkv, kc, vc, out, packed)
 
-    def _forward_llama(self, x, positions, slots, q_seq, q_ctx, last_rows, T, max_ctx, attn_part,
-                       bufs: Optional[dict] = None, qblocks=None, prompt=None, decode=False, lora=None):
-        """``lora``: (device slots int32 [T], host runs or None) of a step with adapter rows - the
-        packed branch (norm kernels, batched LoRA kernels after each targeted projection) up to 64
-        rows, else the row-major branch with the torch form by runs; None: a base-model step."""
-        cfg, w = self.cfg, self.w
-        H, eps = cfg.hidden_size, cfg.rms_norm_eps
-        dev, dt = self.device, self.dtype
-        table = self.sessions.table_dev
-        if bufs is None:
-            bufs = {}
-        e = lambda name, shape, dtype=dt: bufs.get(name) if name in bufs else torch.empty(shape, dtype=dtype, device=dev)  # noqa: E731
-        lo = self._lora if lora is not None else None
-        lora_pk = lo is not None and prompt is None and T <= 64 and self._packed_ok(T) and self._lora_packed_ok(T)
-        fp8_dec = lo is None and prompt is None and self._fp8_ok(T)
-        fused_dec = (lo is None and not fp8_dec and prompt is None and self._fused and self.n_layers > 0 and
-                     (T <= 64 and (self._w8 or self._w4_ok(T) or self._packed_ok(T)) or
-                      (not self._w8 and not self._w4 and self._fused_wide_ok(T))))
-        if self.is_first and not (fused_dec and self._fused_entry and x.dim() == 1 and x.is_contiguous()):
-            h = ops.embedding(x, w.embed, out=e("h", (T, H)))
-        elif self.is_first:
-            h = None  # the fused path's stage-entry kernel gathers the embedding rows itself
+    def _step_path(self, T: int, prompt, lora) -> str:
+        """The layer loop a step of ``T`` rows with deep prompt ``prompt`` and adapter rows ``lora`` (or None) takes:
+        "w8a8", "fused", "moe_w8", "packed" or "dense" (module docstring).  The ONLY place that decides it."""
+        base = lora is None and prompt is None
+        # (a LoRA step goes packed only where the batched kernels cover every targeted projection)
+        lora_pk = lora is not None and prompt is None and T <= 64 and self._packed_ok(T) and self._lora_packed_ok(T)
+        if base and self._fp8_ok(T):
+            return "w8a8"
+        if base and self._fused and self.n_layers > 0 and (
+                T <= 64 and (self._w8 or self._w4_ok(T) or self._packed_ok(T)) or
+                (not self._w8 and not self._w4 and self._fused_wide_ok(T))):
+            return "fused"
+        if base and self._moe_w8 and 0 < T <= 64:
+            return "moe_w8"
+        if prompt is None and self._packed_ok(T) and (lora is None or lora_pk):
+            return "packed"
+        return "dense"
+
+    def _forward_llama(self, st: _Step) -> torch.Tensor:
+        """One forward pass over step ``st``: the layer loop of its path (``_layers_<path>``), then the head.
+        A layer loop returns (res, mlp, stream): the residual stream, the last down projection still to be
+        added to it (None: already added) and, from the fused path, what lm_head can read instead."""
+        layers = getattr(self, "_layers_" + self._step_path(st.T, st.prompt, st.lora))
+        return self._head(st, *layers(st))
+
+    def _begin(self, st: _Step, embed: bool = True):
+        """What every path starts with: the embedding (first stage; ``embed=False``: the path gathers the
+        rows itself and gets None), the attention partition and workspace, and the buffers (h, res, qkv, o, mlp)."""
+        T, H, h = st.T, self.cfg.hidden_size, st.x
+        if self.is_first:
+            h = ops.embedding(st.x, self.w.embed, out=st.buf("h", (T, H))) if embed else None
+        if st.part is None:
+            st.part = ops.attention_partition(T, self.nkv, self._attn_span(st.max_ctx), min_part=self._attn_min_part)
+        st.ws = st.buf("attn_ws", (max(1, T * self.nh * st.part[1] * (self.D + 2)),), torch.float32)
+        return (h, st.buf("res", (T, H)), st.buf("qkv", (T, self.cfg.q_dim + 2 * self.cfg.kv_dim)),
+                st.buf("o", (T, H)), st.buf("mlp", (T, H)))
+
+    def _layers_w8a8(self, st: _Step):
+        """fp8 W8A8 decode path: packed bf16 activations are quantized per row right before each GEMM
+        (csrc/fp8.hip); weights stream at 1 byte per parameter."""
+        cfg, T, eps = self.cfg, st.T, self.cfg.rms_norm_eps
+        H, F = cfg.hidden_size, cfg.intermediate_size
+        h, res, qkv, o, mlp = self._begin(st)
+        pk = ops.packed_numel
+        xn = st.buf("xn_p", (pk(T, H),))
+        # row-major: their only reader is the row quantization kernel (coalesced rows)
+        attn = st.buf("attn", (T, cfg.q_dim))
+        act = st.buf("act", (T, F))
+        a8 = st.buf("a8", (pk(T, max(H, cfg.q_dim, cfg.intermediate_size)),), torch.uint8)
+        asc = st.buf("a8_scale", (((T + 15) // 16) * 16 * 33,), torch.float32)
+        # the two norm sites emit fp8 + row scales themselves (norm.hip a8 output): only the
+        # attention output and the SwiGLU output still take a separate quantization pass
+        for li, L in enumerate(self.w.layers):
+            ops.rmsnorm(h if li == 0 else mlp, L.input_norm, eps, out=xn, residual=res, mode=2 if li == 0 else 1,
+                        packed=True, a8=a8, a8_scale=asc)
+            ops.linear_fp8(a8, asc, L.qkv_q, L.qkv_s, T, out=qkv)
+            kc, vc = self.cache.layer(li)
+            self._rope_attend(st, qkv, kc, vc, attn, False)
+            ops.quant_rows_fp8(attn, out=a8, scale=asc)
+            ops.linear_fp8(a8, asc, L.o_q, L.o_s, T, out=o)
+            self._ar(o)
+            ops.rmsnorm(o, L.post_norm, eps, out=xn, residual=res, mode=1, packed=True, a8=a8, a8_scale=asc)
+            ops.linear_fp8(a8, asc, L.gate_up_q, L.gate_up_s, T, out=act, epilogue=1)
+            ops.quant_rows_fp8(act, out=a8, scale=asc)
+            ops.linear_fp8(a8, asc, L.down_q, L.down_s, T, out=mlp)
+            self._ar(mlp)
+        return res, mlp, None
+
+    def _layers_fused(self, st: _Step):
+        """Fused-norm decode path: 5 launches per layer (qkv, attention, o, gate/up, down).  The residual stream
+        r lives row-major in ``res`` and packed in ``xr``; o / down add their product into it in their epilogue
+        and accumulate sum(r^2) per row, and qkv / gate_up (norm weights folded into their packed weights) scale
+        their rows by rsqrt(mean r^2 + eps).  ss[0] / ss[1]: input- / post-attention-norm statistics; each
+        producer clears the other buffer, whose consumer has already run."""
+        cfg, T, eps = self.cfg, st.T, self.cfg.rms_norm_eps
+        H, Q = cfg.hidden_size, cfg.q_dim
+        # first stage: the stage-entry kernel gathers the embedding rows itself (h is None)
+        h, res, qkv, _, _ = self._begin(st, embed=not (self._fused_entry and st.x.dim() == 1 and st.x.is_contiguous()))
+        pk = ops.packed_numel
+        xr = st.buf("xr_p", (pk(T, H),))
+        attn = st.buf("attn_p", (pk(T, Q),))
+        act = st.buf("act_p", (pk(T, cfg.intermediate_size),))
+        ss_in, ss_post = self._ss[0], self._ss[1]
+        if self._w8 or self._w4:  # W8A16 / W4A16: same launches, 1 byte / 4.25 bits per weight streamed
+            lin, wn, sn = (ops.linear_w8, "_w8", "_ws") if self._w8 else (ops.linear_w4, "_w4", "_s4")
+
+            def gemm(a, L, name, **kw):
+                return lin(a, getattr(L, name + wn), getattr(L, name + sn), T, **kw)
         else:
-            h = x
-        if attn_part is None:
-            attn_part = ops.attention_partition(T, self.nkv, self._attn_span(max_ctx), min_part=self._attn_min_part)
-        ps, np_ = attn_part
-        ws = e("attn_ws", (max(1, T * self.nh * np_ * (self.D + 2)),), torch.float32)
-        res = e("res", (T, H))
-        qkv = e("qkv", (T, cfg.q_dim + 2 * cfg.kv_dim))
-        o = e("o", (T, H))
-        mlp = e("mlp", (T, H))
-        if fp8_dec:
-            # fp8 W8A8 decode path: packed bf16 activations are quantized per row right before
-            # each GEMM (csrc/fp8.hip); weights stream at 1 byte per parameter
-            pk = ops.packed_numel
-            xn = e("xn_p", (pk(T, H),))
-            F = cfg.intermediate_size
-            # row-major: their only reader is the row quantization kernel (coalesced rows)
-            attn = e("attn", (T, cfg.q_dim))
-            act = e("act", (T, F))
-            a8 = e("a8", (pk(T, max(H, cfg.q_dim, cfg.intermediate_size)),), torch.uint8)
-            asc = e("a8_scale", (((T + 15) // 16) * 16 * 33,), torch.float32)
-            # the two norm sites emit fp8 + row scales themselves (norm.hip a8 output): only the
-            # attention output and the SwiGLU output still take a separate quantization pass
-            for li, L in enumerate(w.layers):
-                if li == 0:
-                    ops.rmsnorm(h, L.input_norm, eps, out=xn, residual=res, mode=2, packed=True, a8=a8, a8_scale=asc)
-                else:
-                    ops.rmsnorm(mlp, L.input_norm, eps, out=xn, residual=res, mode=1, packed=True, a8=a8,
-                                a8_scale=asc)
-                ops.linear_fp8(a8, asc, L.qkv_q, L.qkv_s, T, out=qkv)
-                kc, vc = self.cache.layer(li)
-                self._rope_attend(qkv, positions, slots, kc, vc, q_seq, q_ctx, attn, ws, ps, np_, False, qblocks,
-                                  max_ctx, decode)
-                ops.quant_rows_fp8(attn, out=a8, scale=asc)
-                ops.linear_fp8(a8, asc, L.o_q, L.o_s, T, out=o)
-                self._ar(o)
-                ops.rmsnorm(o, L.post_norm, eps, out=xn, residual=res, mode=1, packed=True, a8=a8, a8_scale=asc)
-                ops.linear_fp8(a8, asc, L.gate_up_q, L.gate_up_s, T, out=act, epilogue=1)
-                ops.quant_rows_fp8(act, out=a8, scale=asc)
-                ops.linear_fp8(a8, asc, L.down_q, L.down_s, T, out=mlp)
-                self._ar(mlp)
-        elif fused_dec:
-            # fused-norm decode path: 5 launches per layer (qkv, attention, o, gate/up, down).
-            # The residual stream r lives row-major in ``res`` and packed in ``xr``; o / down add
-            # their product into it in their epilogue and accumulate sum(r^2) per row, and qkv /
-            # gate_up (norm weights folded into their packed weights) scale their rows by
-            # rsqrt(mean r^2 + eps).  ss[0] / ss[1]: input- / post-attention-norm statistics;
-            # each producer clears the other buffer, whose consumer has already run.
-            pk = ops.packed_numel
-            xr = e("xr_p", (pk(T, H),))
-            attn = e("attn_p", (pk(T, cfg.q_dim),))
-            act = e("act_p", (pk(T, cfg.intermediate_size),))
-            ss_in, ss_post = self._ss[0], self._ss[1]
-            if self._w8:  # fp8 weights (W8A16): same launches, 1 byte per weight streamed
-                def gemm(a, L, name, **kw):
-                    return ops.linear_w8(a, getattr(L, name + "_w8"), getattr(L, name + "_ws"), T, **kw)
-            elif self._w4:  # MXFP4 weights (W4A16): same launches, 4.25 bits per weight streamed
-                def gemm(a, L, name, **kw):
-                    return ops.linear_w4(a, getattr(L, name + "_w4"), getattr(L, name + "_s4"), T, **kw)
+            def gemm(a, L, name, **kw):
+                return ops.linear(a, None, wp=getattr(L, name + "_p"), a_rows=T, **kw)
+        one_launch = st.decode and st.qblocks is None  # (RoPE + attention in one decode kernel: _rope_attend)
+        # decode steps whose qkv GEMM measured faster as split-K partial slabs: the attention
+        # kernel sums the slabs + applies the row scale on its q / k / v loads (no reduce launch)
+        fold = one_launch and self._qkv_fold(T)
+        # W8A8-MX o projection: the MFMA GQA decode kernel's epilogue writes the MX activation; it can with
+        # one context part and head_dim 128 (the partition is the step's: the same for every layer)
+        mx_o = None
+        if (self._mx and one_launch and T <= 64 and self.gqa_decode_mfma and not self._kv_fp8 and self._fuse_rope and
+                ops.rwk_split(T, H, Q, 2) > 0 and self._parts128(*st.part)[1] == 1 and self.D == 128):
+            mx_o = (st.buf(f"mx_ax{Q}", (16 * ((T + 15) // 16) * Q,), torch.uint8),
+                    st.buf(f"mx_as{Q}", (2 * Q,), torch.uint8))
+        for li, L in self._iter_layers(_PACKED_FIELDS):
+            if li == 0 and h is None:  # first stage: embedding lookup + stage entry in one launch
+                ops.embed_stage_entry(st.x, self.w.embed, xr, res, ss_in)
+            elif li == 0:
+                ops.rmsnorm(h, L.input_norm, eps, out=xr, residual=res, mode=3, packed=True, ss=ss_in)
+            qp = None
+            if fold:
+                wkw = dict(w8=L.qkv_w8, w_scale=L.qkv_ws) if self._w8 else dict(wp=L.qkv_p)
+                qp = (ops.linear_partials(xr, T, out=qkv, **wkw), ss_in, 1.0 / H, eps)
             else:
-                def gemm(a, L, name, **kw):
-                    return ops.linear(a, None, wp=getattr(L, name + "_p"), a_rows=T, **kw)
-            # decode steps whose qkv GEMM measured faster as split-K partial slabs: the attention
-            # kernel sums the slabs + applies the row scale on its q / k / v loads (no reduce launch)
-            fold = decode and qblocks is None and self._qkv_fold(T)
-            # W8A8-MX o projection: the attention epilogue writes the MX activation (GQA decode)
-            Q = cfg.q_dim
-            mx_o = None
-            if (self._mx and decode and qblocks is None and T <= 64 and self.gqa_decode_mfma and not self._kv_fp8 and
-                    self._fuse_rope and
-                    ops.rwk_split(T, H, Q, 2) > 0):
-                mx_o = (e(f"mx_ax{Q}", (16 * ((T + 15) // 16) * Q,), torch.uint8), e(f"mx_as{Q}", (2 * Q,), torch.uint8))
-            for li, L in self._iter_layers(_PACKED_FIELDS):
-                if li == 0 and h is None:  # first stage: embedding lookup + stage entry in one launch
-                    ops.embed_stage_entry(x, w.embed, xr, res, ss_in)
-                elif li == 0:
-                    ops.rmsnorm(h, L.input_norm, eps, out=xr, residual=res, mode=3, packed=True, ss=ss_in)
-                qp = None
-                if fold:
-                    if self._w8:
-                        part = ops.linear_partials(xr, T, w8=L.qkv_w8, w_scale=L.qkv_ws, out=qkv)
-                    else:
-                        part = ops.linear_partials(xr, T, wp=L.qkv_p, out=qkv)
-                    qp = (part, ss_in, 1.0 / H, eps)
-                else:
-                    gemm(xr, L, "qkv", out=qkv, ss_in=ss_in, eps=eps)
-                kc, vc = self.cache.layer(li)
-                used = []
-                self._rope_attend(qkv, positions, slots, kc, vc, q_seq, q_ctx, attn, ws, ps, np_, True, qblocks,
-                                  max_ctx, decode, qkv_part=qp, mx_out=mx_o, mx_used=used)
-                if used:
-                    ops.linear_mx(mx_o[0], mx_o[1], L.o_w8, L.o_ws, T, out=res, epilogue=3, residual=res, ap_out=xr,
-                                  ss_out=ss_post, ss_zero=ss_in)
-                else:
-                    gemm(attn, L, "o", out=res, epilogue=3, residual=res, ap_out=xr, ss_out=ss_post, ss_zero=ss_in)
-                gemm(xr, L, "gate_up", out=act, epilogue=1, out_packed=True, ss_in=ss_post, eps=eps)
-                gemm(act, L, "down", out=res, epilogue=3, residual=res, ap_out=xr, ss_out=ss_in, ss_zero=ss_post)
-            mlp = None
-        elif lo is None and prompt is None and self._moe_w8 and 0 < T <= 64:
-            # fp8 MoE decode path: packed activations, norm kernels with the real weights, qkv / o on
-            # the W8A16 GEMM, the experts in two grouped launches (_moe_mlp_w8)
-            pk = ops.packed_numel
-            xn = e("xn_p", (pk(T, H),))
-            attn = e("attn_p", (pk(T, cfg.q_dim),))
-            act = e("moe_act_p", (cfg.num_local_experts * pk(T, cfg.intermediate_size),))
-            for li, L in enumerate(w.layers):
-                if li == 0:
-                    ops.rmsnorm(h, L.input_norm, eps, out=xn, residual=res, mode=2, packed=True)
-                else:
-                    ops.rmsnorm(mlp, L.input_norm, eps, out=xn, residual=res, mode=1, packed=True)
-                ops.linear_w8(xn, L.qkv_w8, L.qkv_ws, T, out=qkv)
-                kc, vc = self.cache.layer(li)
-                self._rope_attend(qkv, positions, slots, kc, vc, q_seq, q_ctx, attn, ws, ps, np_, True, qblocks,
-                                  max_ctx, decode)
-                ops.linear_w8(attn, L.o_w8, L.o_ws, T, out=o)
-                ops.rmsnorm(o, L.post_norm, eps, out=xn, residual=res, mode=1, packed=True)
-                self._moe_mlp_w8(L, xn, T, mlp, act, e)
-        elif prompt is None and self._packed_ok(T) and (lo is None or lora_pk):
-            # decode path: activations feeding a GEMM stay in the packed MFMA-fragment layout
-            pk = ops.packed_numel
-            xn = e("xn_p", (pk(T, H),))
-            attn = e("attn_p", (pk(T, cfg.q_dim),))
-            act = e("act_p", (pk(T, cfg.intermediate_size),))
+                gemm(xr, L, "qkv", out=qkv, ss_in=ss_in, eps=eps)
+            kc, vc = self.cache.layer(li)
+            self._rope_attend(st, qkv, kc, vc, attn, True, qkv_part=qp, mx_out=mx_o)
+            if mx_o is not None:
+                ops.linear_mx(mx_o[0], mx_o[1], L.o_w8, L.o_ws, T, out=res, epilogue=3, residual=res, ap_out=xr,
+                              ss_out=ss_post, ss_zero=ss_in)
+            else:
+                gemm(attn, L, "o", out=res, epilogue=3, residual=res, ap_out=xr, ss_out=ss_post, ss_zero=ss_in)
+            gemm(xr, L, "gate_up", out=act, epilogue=1, out_packed=True, ss_in=ss_post, eps=eps)
+            gemm(act, L, "down", out=res, epilogue=3, residual=res, ap_out=xr, ss_out=ss_in, ss_zero=ss_post)
+        return res, None, (xr, ss_in)
 
-            def lora_add(lp, xp, y, unit=False):
-                # y += B (scale A x) for the rows with an adapter: two launches, slots read on the device
-                if lp is not None:
-                    t = ops.lora_shrink(xp, lp.a_for(unit), lo.scale, lora[0], T,
-                                        out=e(f"lora_t{lp.A.shape[1]}", (T, lp.A.shape[1]), torch.float32))
-                    ops.lora_expand(t, lp.B, lora[0], y)
+    def _layers_moe_w8(self, st: _Step):
+        """fp8 MoE decode path: packed activations, norm kernels with the real weights, qkv / o on
+        the W8A16 GEMM, the experts in two grouped launches (_moe_mlp_w8)."""
+        cfg, T, eps = self.cfg, st.T, self.cfg.rms_norm_eps
+        h, res, qkv, o, mlp = self._begin(st)
+        pk = ops.packed_numel
+        xn = st.buf("xn_p", (pk(T, cfg.hidden_size),))
+        attn = st.buf("attn_p", (pk(T, cfg.q_dim),))
+        act = st.buf("moe_act_p", (cfg.num_local_experts * pk(T, cfg.intermediate_size),))
+        for li, L in enumerate(self.w.layers):
+            ops.rmsnorm(h if li == 0 else mlp, L.input_norm, eps, out=xn, residual=res, mode=2 if li == 0 else 1,
+                        packed=True)
+            ops.linear_w8(xn, L.qkv_w8, L.qkv_ws, T, out=qkv)
+            kc, vc = self.cache.layer(li)
+            self._rope_attend(st, qkv, kc, vc, attn, True)
+            ops.linear_w8(attn, L.o_w8, L.o_ws, T, out=o)
+            ops.rmsnorm(o, L.post_norm, eps, out=xn, residual=res, mode=1, packed=True)
+            self._moe_mlp_w8(st, L, xn, mlp, act)
+        return res, mlp, None
 
-            for li, L in self._iter_layers(_PACKED_FIELDS):
-                LL = lo.layers[li] if lo is not None else None
-                if LL is not None:
-                    # a LoRA step: the same launches, plus shrink + expand on the row-major output of
-                    # every targeted projection (a targeted gate/up leaves its SwiGLU epilogue)
-                    unit = bool(getattr(L, "folded", False))
-                    g_in, g_post = (self._unit_norm(), self._unit_norm()) if unit else (L.input_norm, L.post_norm)
-                    ops.rmsnorm(h if li == 0 else mlp, g_in, eps, out=xn, residual=res, mode=2 if li == 0 else 1,
-                                packed=True)
-                    ops.linear(xn, L.qkv, out=qkv, wp=L.qkv_p, a_rows=T)
-                    lora_add(LL.qkv, xn, qkv, unit)
-                    kc, vc = self.cache.layer(li)
-                    self._rope_attend(qkv, positions, slots, kc, vc, q_seq, q_ctx, attn, ws, ps, np_, True, qblocks,
-                                      max_ctx, decode)
-                    ops.linear(attn, L.o, out=o, wp=L.o_p, a_rows=T)
-                    lora_add(LL.o, attn, o)
-                    ops.rmsnorm(o, g_post, eps, out=xn, residual=res, mode=1, packed=True)
-                    if LL.gate_up is not None:
-                        gu = ops.linear(xn, L.gate_up, out=e("gu", (T, 2 * cfg.intermediate_size)), wp=L.gate_up_p,
-                                        a_rows=T)
-                        lora_add(LL.gate_up, xn, gu, unit)
-                        ops.pack_act(ops.swiglu(gu, out=e("act", (T, cfg.intermediate_size))), out=act)
-                    else:
-                        ops.linear(xn, L.gate_up, out=act, epilogue=1, wp=L.gate_up_p, a_rows=T, out_packed=True)
-                    ops.linear(act, L.down, out=mlp, wp=L.down_p, a_rows=T)
-                    lora_add(LL.down, act, mlp)
-                    continue
-                # weights packed for the fused path (> 64 rows here) carry the norm weights in
-                # their columns: normalise with a unit weight
-                g_in, g_post = (self._unit_norm(), self._unit_norm()) if getattr(L, "folded", False) else \
-                    (L.input_norm, L.post_norm)
-                if li == 0:
-                    ops.rmsnorm(h, g_in, eps, out=xn, residual=res, mode=2, packed=True)
-                else:
-                    ops.rmsnorm(mlp, g_in, eps, out=xn, residual=res, mode=1, packed=True)
-                ops.linear(xn, L.qkv, out=qkv, wp=L.qkv_p, a_rows=T)
-                kc, vc = self.cache.layer(li)
-                self._rope_attend(qkv, positions, slots, kc, vc, q_seq, q_ctx, attn, ws, ps, np_, True, qblocks,
-                                  max_ctx, decode)
-                ops.linear(attn, L.o, out=o, wp=L.o_p, a_rows=T)
-                self._ar(o)
-                ops.rmsnorm(o, g_post, eps, out=xn, residual=res, mode=1, packed=True)
-                if L.moe:
-                    self._moe_mlp(L, xn, T, mlp, act, e, packed=True)
-                    continue
+    def _layers_packed(self, st: _Step):
+        """Packed decode path: activations feeding a GEMM stay in the packed MFMA-fragment layout.  A LoRA step adds
+        shrink + expand on the row-major output of every targeted projection (gate/up then leaves its epilogue)."""
+        cfg, T, eps = self.cfg, st.T, self.cfg.rms_norm_eps
+        H, F = cfg.hidden_size, cfg.intermediate_size
+        lo = self._lora if st.lora is not None else None
+        h, res, qkv, o, mlp = self._begin(st)
+        pk = ops.packed_numel
+        xn = st.buf("xn_p", (pk(T, H),))
+        attn = st.buf("attn_p", (pk(T, cfg.q_dim),))
+        act = st.buf("act_p", (pk(T, F),))
+
+        def lora_add(lp, xp, y, unit=False):
+            # y += B (scale A x) for the rows with an adapter: two launches, slots read on the device
+            if lp is not None:
+                t = ops.lora_shrink(xp, lp.a_for(unit), lo.scale, st.lora[0], T,
+                                    out=st.buf(f"lora_t{lp.A.shape[1]}", (T, lp.A.shape[1]), torch.float32))
+                ops.lora_expand(t, lp.B, st.lora[0], y)
+
+        for li, L in self._iter_layers(_PACKED_FIELDS):
+            LL = lo.layers[li] if lo is not None else _NO_LORA
+            # weights packed for the fused path (a base step of > 64 rows, a LoRA step) carry the norm
+            # weights in their columns: normalise with a unit weight
+            unit = bool(getattr(L, "folded", False))
+            g_in, g_post = (self._unit_norm(), self._unit_norm()) if unit else (L.input_norm, L.post_norm)
+            ops.rmsnorm(h if li == 0 else mlp, g_in, eps, out=xn, residual=res, mode=2 if li == 0 else 1, packed=True)
+            ops.linear(xn, L.qkv, out=qkv, wp=L.qkv_p, a_rows=T)
+            lora_add(LL.qkv, xn, qkv, unit)
+            kc, vc = self.cache.layer(li)
+            self._rope_attend(st, qkv, kc, vc, attn, True)
+            ops.linear(attn, L.o, out=o, wp=L.o_p, a_rows=T)
+            lora_add(LL.o, attn, o)
+            self._ar(o)
+            ops.rmsnorm(o, g_post, eps, out=xn, residual=res, mode=1, packed=True)
+            if L.moe:
+                self._moe_mlp(st, L, xn, mlp, act, packed=True)
+                continue
+            if LL.gate_up is not None:
+                gu = ops.linear(xn, L.gate_up, out=st.buf("gu", (T, 2 * F)), wp=L.gate_up_p, a_rows=T)
+                lora_add(LL.gate_up, xn, gu, unit)
+                ops.pack_act(ops.swiglu(gu, out=st.buf("act", (T, F))), out=act)
+            else:
                 ops.linear(xn, L.gate_up, out=act, epilogue=1, wp=L.gate_up_p, a_rows=T, out_packed=True)
-                ops.linear(act, L.down, out=mlp, wp=L.down_p, a_rows=T)
-                self._ar(mlp)
-        else:
-            xn = e("xn", (T, H))
-            attn = e("attn", (T, cfg.q_dim))
-            act = e("act", (T, cfg.intermediate_size))
-            # (a LoRA step keeps the real norm weights and the unfolded row-major weights: its gate/up
-            # may run with epilogue 0, which the per-step fold decision does not cover)
-            fold_native = lo is None and self._folded_native(T)
-            for li, L in self._iter_layers(_DENSE_FIELDS):
-                LL = lo.layers[li] if lo is not None else None
-                # W8A16 / MXFP4 layers' only weights carry the norm weights folded in (prepare_w8a16,
-                # quantize_mxfp4).
-                # bf16 layers packed for the fused path carry them in qkv_p / gate_up_p only: when
-                # the native GEMM would pick those up, normalise with a unit weight; otherwise
-                # keep the real norm weights and hand the GEMM the unfolded row-major weight only
-                quant = L.w8 or L.w4
-                folded_bf16 = L.folded and not quant
-                unit = (L.folded and quant) or (folded_bf16 and fold_native)
-                g_in, g_post = (self._unit_norm(), self._unit_norm()) if unit else (L.input_norm, L.post_norm)
-                qkv_p = None if (folded_bf16 and not fold_native) else L.qkv_p
-                gu_p = None if (folded_bf16 and not fold_native) else L.gate_up_p
-                if prompt is not None:  # deep prompt: the block input (residual stream) += prompt[li]
-                    cur = h.clone() if li == 0 else ops.add(res, mlp)
-                    cur.index_add_(0, prompt[0], prompt[1][li])
-                    ops.rmsnorm(cur, g_in, eps, out=xn, residual=res, mode=2)
-                elif li == 0:
-                    ops.rmsnorm(h, g_in, eps, out=xn, residual=res, mode=2)
-                else:
-                    ops.rmsnorm(mlp, g_in, eps, out=xn, residual=res, mode=1)
-                # (fp8 MoE layers dequantize into the executor's dtype: an fp32 CPU stage stays fp32)
-                wdt = dt if L.moe else torch.bfloat16
-                ops.linear(xn, L.dense("qkv", wdt), out=qkv, wp=qkv_p)
-                if LL is not None and LL.qkv is not None:
-                    ops.lora_update(xn, qkv, LL.qkv.A, LL.qkv.B, lo.scale, lora[1])
-                kc, vc = self.cache.layer(li)
-                self._rope_attend(qkv, positions, slots, kc, vc, q_seq, q_ctx, attn, ws, ps, np_, False, qblocks,
-                                  max_ctx, decode)
-                ops.linear(attn, L.dense("o", wdt), out=o, wp=L.o_p)
-                if LL is not None and LL.o is not None:
-                    ops.lora_update(attn, o, LL.o.A, LL.o.B, lo.scale, lora[1])
-                self._ar(o)
-                ops.rmsnorm(o, g_post, eps, out=xn, residual=res, mode=1)
-                if L.moe:
-                    self._moe_mlp(L, xn, T, mlp, act, e, packed=False)
-                    continue
-                if LL is not None and LL.gate_up is not None:  # epilogue 0, the update, then SwiGLU
-                    gu = ops.linear(xn, L.dense("gate_up"), out=e("gu", (T, 2 * cfg.intermediate_size)), wp=gu_p)
-                    ops.lora_update(xn, gu, LL.gate_up.A, LL.gate_up.B, lo.scale, lora[1])
-                    ops.swiglu(gu, out=act)
-                else:
-                    ops.linear(xn, L.dense("gate_up"), out=act, epilogue=1, wp=gu_p)
-                ops.linear(act, L.dense("down"), out=mlp, wp=L.down_p)
-                if LL is not None and LL.down is not None:
-                    ops.lora_update(act, mlp, LL.down.A, LL.down.B, lo.scale, lora[1])
-                self._ar(mlp)
-        hout = res if mlp is None else ops.add(res, mlp, out=e("hout", (T, H)))
+            ops.linear(act, L.down, out=mlp, wp=L.down_p, a_rows=T)
+            lora_add(LL.down, act, mlp)
+            self._ar(mlp)
+        return res, mlp, None
+
+    def _layers_dense(self, st: _Step):
+        """Row-major path: any row count, any device; deep prompts, and LoRA steps with the torch form of
+        the update by runs of rows (``ops.lora_update``)."""
+        cfg, T, eps, prompt = self.cfg, st.T, self.cfg.rms_norm_eps, st.prompt
+        H, F = cfg.hidden_size, cfg.intermediate_size
+        lo, runs = (self._lora, st.lora[1]) if st.lora is not None else (None, None)
+        h, res, qkv, o, mlp = self._begin(st)
+        xn = st.buf("xn", (T, H))
+        attn = st.buf("attn", (T, cfg.q_dim))
+        act = st.buf("act", (T, F))
+        # (a LoRA step keeps the real norm weights and the unfolded row-major weights: its gate/up
+        # may run with epilogue 0, which the per-step fold decision does not cover)
+        fold_native = lo is None and self._folded_native(T)
+        for li, L in self._iter_layers(_DENSE_FIELDS):
+            LL = lo.layers[li] if lo is not None else _NO_LORA
+            # W8A16 / MXFP4 layers' only weights carry the norm weights folded in (prepare_w8a16,
+            # quantize_mxfp4).
+            # bf16 layers packed for the fused path carry them in qkv_p / gate_up_p only: when
+            # the native GEMM would pick those up, normalise with a unit weight; otherwise
+            # keep the real norm weights and hand the GEMM the unfolded row-major weight only
+            quant = L.w8 or L.w4
+            folded_bf16 = L.folded and not quant
+            unit = (L.folded and quant) or (folded_bf16 and fold_native)
+            g_in, g_post = (self._unit_norm(), self._unit_norm()) if unit else (L.input_norm, L.post_norm)
+            qkv_p = None if (folded_bf16 and not fold_native) else L.qkv_p
+            gu_p = None if (folded_bf16 and not fold_native) else L.gate_up_p
+            if prompt is not None:  # deep prompt: the block input (residual stream) += prompt[li]
+                cur = h.clone() if li == 0 else ops.add(res, mlp)
+                cur.index_add_(0, prompt[0], prompt[1][li])
+                ops.rmsnorm(cur, g_in, eps, out=xn, residual=res, mode=2)
+            else:
+                ops.rmsnorm(h if li == 0 else mlp, g_in, eps, out=xn, residual=res, mode=2 if li == 0 else 1)
+            # (fp8 MoE layers dequantize into the executor's dtype: an fp32 CPU stage stays fp32)
+            wdt = self.dtype if L.moe else torch.bfloat16
+            ops.linear(xn, L.dense("qkv", wdt), out=qkv, wp=qkv_p)
+            if LL.qkv is not None:
+                ops.lora_update(xn, qkv, LL.qkv.A, LL.qkv.B, lo.scale, runs)
+            kc, vc = self.cache.layer(li)
+            self._rope_attend(st, qkv, kc, vc, attn, False)
+            ops.linear(attn, L.dense("o", wdt), out=o, wp=L.o_p)
+            if LL.o is not None:
+                ops.lora_update(attn, o, LL.o.A, LL.o.B, lo.scale, runs)
+            self._ar(o)
+            ops.rmsnorm(o, g_post, eps, out=xn, residual=res, mode=1)
+            if L.moe:
+                self._moe_mlp(st, L, xn, mlp, act, packed=False)
+                continue
+            if LL.gate_up is not None:  # epilogue 0, the update, then SwiGLU
+                gu = ops.linear(xn, L.dense("gate_up"), out=st.buf("gu", (T, 2 * F)), wp=gu_p)
+                ops.lora_update(xn, gu, LL.gate_up.A, LL.gate_up.B, lo.scale, runs)
+                ops.swiglu(gu, out=act)
+            else:
+                ops.linear(xn, L.dense("gate_up"), out=act, epilogue=1, wp=gu_p)
+            ops.linear(act, L.dense("down"), out=mlp, wp=L.down_p)
+            if LL.down is not None:
+                ops.lora_update(act, mlp, LL.down.A, LL.down.B, lo.scale, runs)
+            self._ar(mlp)
+        return res, mlp, None
+
+    def _head(self, st: _Step, res, mlp, stream) -> torch.Tensor:
+        """What every path ends with: the last residual add (``mlp`` None: done already), then (last stage) the
+        final norm and ``lm_head`` on every sequence's last row.  ``stream``: the fused path's (xr, ss_in)."""
+        cfg, w, T, eps = self.cfg, self.w, st.T, self.cfg.rms_norm_eps
+        H, V = cfg.hidden_size, cfg.vocab_size
+        hout = res if mlp is None else ops.add(res, mlp, out=st.buf("hout", (T, H)))
         if not self.is_last:
             return hout
-        S = last_rows.numel()
-        V = cfg.vocab_size
+        S = st.last_rows.numel()
         if w.lm_head_p is not None and self._head_packed_ok(S):
             Vp = 16 * w.lm_head_p.shape[0]
-            if w.lm_head_folded and mlp is None and S == T:
+            if w.lm_head_folded and stream is not None and S == T:
                 # fused-norm path, every row a last row (decode): lm_head (final norm folded in)
                 # reads the packed residual stream the last down GEMM left in ``xr`` and scales
                 # each row by its rsqrt(mean r^2 + eps) from ``ss_in`` - no final norm launch
-                logits = ops.linear(xr, None, out=e("logits", (S, Vp)), wp=w.lm_head_p, a_rows=S, ss_in=ss_in,
-                                    eps=eps)
+                logits = ops.linear(stream[0], None, out=st.buf("logits", (S, Vp)), wp=w.lm_head_p, a_rows=S,
+                                    ss_in=stream[1], eps=eps)
                 return logits[:, :V]
             fn = ops.rmsnorm(hout, self._unit_norm() if w.lm_head_folded else w.final_norm, eps,
-                             out=e("fn_p", (ops.packed_numel(S, H),)), rows=last_rows, packed=True)
-            logits = ops.linear(fn, None, out=e("logits", (S, Vp)), wp=w.lm_head_p, a_rows=S)
+                             out=st.buf("fn_p", (ops.packed_numel(S, H),)), rows=st.last_rows, packed=True)
+            logits = ops.linear(fn, None, out=st.buf("logits", (S, Vp)), wp=w.lm_head_p, a_rows=S)
             return logits[:, :V]
-        fn = ops.rmsnorm(hout, w.final_norm, eps, out=e("fn", (S, H)), rows=last_rows)
-        return ops.linear(fn, w.lm_head, out=e("logits", (S, V)))
+        fn = ops.rmsnorm(hout, w.final_norm, eps, out=st.buf("fn", (S, H)), rows=st.last_rows)
+        return ops.linear(fn, w.lm_head, out=st.buf("logits", (S, V)))
 
     def warmup(self, sizes: Optional[Sequence[int]] = None) -> None:
         """Run throwaway prefill steps at start-up so the first real request does not pay the
@@ -1177,14 +1176,14 @@ class StageExecutor:
             u = self._ones = torch.ones(self.cfg.hidden_size, dtype=self.dtype, device=self.device)
         return u
 
-    def _moe_mlp_w8(self, L, xn, T, mlp, act, e) -> None:
+    def _moe_mlp_w8(self, st: _Step, L, xn, mlp, act) -> None:
         """Sparse-MoE MLP of a <= 64-row step over fp8 experts into ``mlp``: the bf16 router, the
         routing math (ops/moe.py), then two grouped launches for all experts - gate/up + SwiGLU into
         E packed slabs of ``act``, down + combine (channel scales and routing weights in fp32, one
         bf16 rounding).  Experts no row is routed to are skipped on the device by ``cnt``: no host
         sync, the step stays graph-capturable.  MPAMD_MOE_GROUPED=0 (and shapes the grouped kernels
         do not cover): every expert through ops.linear_w8 + addcmul_, nothing skipped."""
-        cfg = self.cfg
+        cfg, T, e = self.cfg, st.T, st.buf
         E, k, H, F = cfg.num_local_experts, cfg.num_experts_per_tok, cfg.hidden_size, cfg.intermediate_size
         logits = ops.linear(xn, None, out=e("moe_logits", (T, 16 * L.router_p.shape[0])), wp=L.router_p,
                             a_rows=T)[:, :E]
@@ -1205,11 +1204,11 @@ class StageExecutor:
             acc.addcmul_(y, wd[:, j:j + 1])
         mlp.copy_(acc)
 
-    def _moe_mlp(self, L, xn, T, mlp, act, e, packed: bool) -> None:
+    def _moe_mlp(self, st: _Step, L, xn, mlp, act, packed: bool) -> None:
         """Mixtral sparse-MoE MLP into ``mlp`` (ops/moe.py has the routing math and the
         decode-vs-prefill strategy).  Decode steps run every expert on the whole batch with a
         dense combine matrix: no host sync, so the step stays graph-capturable."""
-        cfg = self.cfg
+        cfg, T, e = self.cfg, st.T, st.buf
         E, k, H = cfg.num_local_experts, cfg.num_experts_per_tok, cfg.hidden_size
         if packed:
             logits = ops.linear(xn, None, out=e("moe_logits", (T, 16 * L.router_p.shape[0])), wp=L.router_p,
@@ -1370,10 +1369,11 @@ class StageExecutor:
     def _forward_gpt2(self, plan: Plan, x, prompt=None):
         cfg, w = self.cfg, self.w
         F = torch.nn.functional
-        T, H = plan.T, cfg.hidden_size
+        H = cfg.hidden_size
+        positions, slots, q_seq, q_ctx, last_rows = plan.meta()
         table = self.sessions.table_dev
         if self.is_first:
-            h = w.embed[x.long()] + w.pos_embed[plan.positions]
+            h = w.embed[x.long()] + w.pos_embed[positions]
         else:
             h = x
         for li, L in self._iter_layers(_GPT2_FIELDS):
@@ -1383,8 +1383,8 @@ class StageExecutor:
             qkv = F.linear(a, L.attn_w, L.attn_b)
             q, k, v = qkv.split(H, dim=1)
             kc, vc = self.cache.layer(li)
-            ops.kv_write(k.contiguous(), v.contiguous(), kc, vc, plan.slots)
-            att = ops.paged_attention(q.contiguous(), kc, vc, table, plan.q_seq, plan.q_ctx, self.nh, self.nkv,
+            ops.kv_write(k.contiguous(), v.contiguous(), kc, vc, slots)
+            att = ops.paged_attention(q.contiguous(), kc, vc, table, q_seq, q_ctx, self.nh, self.nkv,
                                       self.scale, max_ctx=plan.max_ctx)
             h = h + F.linear(att, L.proj_w, L.proj_b)
             m = F.layer_norm(h, (H,), L.ln2_w, L.ln2_b, cfg.layer_norm_eps)
@@ -1392,7 +1392,7 @@ class StageExecutor:
             h = h + F.linear(m, L.fc2_w, L.fc2_b)
         if not self.is_last:
             return h
-        hl = h.index_select(0, plan.last_rows.long())
+        hl = h.index_select(0, last_rows.long())
         hl = F.layer_norm(hl, (H,), w.final_norm, w.final_norm_b, cfg.layer_norm_eps)
         return F.linear(hl, w.lm_head)
 
@@ -1423,13 +1423,16 @@ class StageExecutor:
         part = ops.attention_partition(B, self.nkv, ctxb, min_part=self._attn_min_part)
         return (B, part[0], part[1], self._qkv_fold(B), bool(hooked), int(tag), int(slot))
 
-    def _graph(self, key: tuple) -> "_DecodeGraph":
-        g = self._graphs.get(key)
+    def _graph(self, key: tuple, lora: bool = False) -> "_DecodeGraph":
+        """The decode graph of ``key``, captured on first use.  LoRA graphs live in ``_lora_graphs`` under the same key
+        tuple: one serves every mix of adapters, since the row slots are data of the replay (the metadata blob)."""
+        graphs = self._lora_graphs if lora else self._graphs
+        g = graphs.get(key)
         if g is None:
             if self._graph_pool is None:
                 self._graph_pool = torch.cuda.graph_pool_handle()
-            g = _DecodeGraph(self, key[0], (key[1], key[2]), self._graph_pool, hook=self.graph_hook if key[4] else None)
-            self._graphs[key] = g
+            g = graphs[key] = _DecodeGraph(self, key[0], (key[1], key[2]), self._graph_pool,
+                                           hook=self.graph_hook if key[4] else None, lora=lora)
         return g
 
     def _run_graph(self, plan: Plan, x: torch.Tensor, hooked: bool = False, owner=None) -> torch.Tensor:
@@ -1451,15 +1454,7 @@ class StageExecutor:
         return out
 
     def _run_lora_graph(self, plan: Plan, x: torch.Tensor) -> torch.Tensor:
-        """Replay (capturing first) the LoRA decode graph of the step's bucket.  LoRA graphs live in
-        ``_lora_graphs`` under the same key tuple as the base graphs: one graph serves every mix of
-        adapters, since the row slots are data of the replay (the graph's metadata blob)."""
-        key = self._graph_key(plan.T, plan.max_ctx, False)
-        g = self._lora_graphs.get(key)
-        if g is None:
-            if self._graph_pool is None:
-                self._graph_pool = torch.cuda.graph_pool_handle()
-            g = self._lora_graphs[key] = _DecodeGraph(self, key[0], (key[1], key[2]), self._graph_pool, lora=True)
+        g = self._graph(self._graph_key(plan.T, plan.max_ctx, False), lora=True)
         out = g.replay(plan, x)
         g.mark_replayed()
         return out
@@ -1597,14 +1592,16 @@ class _DecodeGraph:
             ex.decode_qblocks(B)  # allocated outside the capture
         self.bufs: dict = {}
         self.done_ev = None  # end of the last replay on the compute stream (graph_input)
-        args = (self.x, self.meta64[0], self.meta64[1], self.meta32[:B], self.meta32[B:2 * B], self.meta32[2 * B:], B,
-                0, part)
-        kw = {"lora": (self.lora_slots, None)} if lora else {}
+        def step():  # (a fresh one per pass: each allocates its own workspace)
+            return _Step(self.x, self.meta64[0], self.meta64[1], self.meta32[:B], self.meta32[B:2 * B],
+                         self.meta32[2 * B:], B, 0, True, dev, dt, part=part, bufs=self.bufs,
+                         lora=(self.lora_slots, None) if lora else None)
+
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
             for _ in range(2):  # warm up (allocator, hipBLASLt heuristics) outside capture
-                ex._forward_llama(*args, decode=True, **kw)
+                ex._forward_llama(step())
         torch.cuda.current_stream().wait_stream(s)
         self.graph = torch.cuda.CUDAGraph()
         # Python's cyclic collector must not run inside the capture: a dead executor and its graphs
@@ -1618,7 +1615,7 @@ class _DecodeGraph:
             # thread-local capture: another thread's stream work (a channel receive posted outside the
             # executor lock) neither breaks this capture nor fails because of it
             with torch.cuda.graph(self.graph, pool=pool, capture_error_mode="thread_local"):
-                self.out = ex._forward_llama(*args, decode=True, **kw)
+                self.out = ex._forward_llama(step())
                 if hook is not None:  # recorded only: the warm-up runs above never call it
                     hook(self.out)
         finally:

@@ -235,10 +235,10 @@ def _spy(monkeypatch, ex):
         monkeypatch.setattr(ops, name, wrapped)
     real_attend = ex._attend
 
-    def attend(qkv, kc, vc, q_seq, q_ctx, out, ws, ps, np_, packed, qblocks, max_ctx):
-        log.append(dict(prefill=qblocks is not None, packed=bool(packed), max_ctx=int(max_ctx), op=None,
-                        fb=getattr(ex, "_cur_fb", None) is not None))
-        return real_attend(qkv, kc, vc, q_seq, q_ctx, out, ws, ps, np_, packed, qblocks, max_ctx)
+    def attend(st, qkv, kc, vc, out, packed):
+        log.append(dict(prefill=st.qblocks is not None, packed=bool(packed), max_ctx=int(st.max_ctx), op=None,
+                        fb=st.fablocks is not None))
+        return real_attend(st, qkv, kc, vc, out, packed)
 
     monkeypatch.setattr(ex, "_attend", attend)
     return log
