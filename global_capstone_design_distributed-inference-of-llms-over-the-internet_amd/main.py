@@ -50,6 +50,7 @@ from .partition import parse_splits, resolve_splits, stage_ranges  # noqa: F401 
 from .rpc_handler import StageConnectionHandler
 from .rpc_transport import RpcTransport
 from .runtime.executor import StageExecutor
+from .runtime.speculative import DRAFTERS, speculative_generate
 from .throughput_measurement import FALLBACK_THROUGHPUT, get_server_throughput
 from .utils import setup_logging
 
@@ -141,6 +142,11 @@ def build_parser() -> argparse.ArgumentParser:
                    help="LB server: concurrent one-token steps of the compute-throughput probe (tokens/s)")
     p.add_argument("--num_sessions", type=int, default=1,
                    help="client: generate this many sessions concurrently (prompt repeated, distinct seeds)")
+    p.add_argument("--speculative_tokens", type=int, default=0,
+                   help="client: draft this many tokens per step and have the last stage verify them in one "
+                        "multi-token step (0 = the plain one-token loop); the output is the plain loop's")
+    p.add_argument("--draft", choices=sorted(DRAFTERS), default="ngram",
+                   help="client: the drafter of --speculative_tokens (ngram: prompt lookup)")
     p.add_argument("--dump_tokens", type=str, default=None,
                    help="client: write every session's generated token ids (JSON) here (harnesses, fault tests)")
     p.add_argument("--max_replicas", type=int, default=0,
@@ -210,11 +216,37 @@ def _start_dht(args) -> DHT:
 
 
 # ================================================================================ client
+def _check_speculative(args, cfg) -> int:
+    """--speculative_tokens K, or a ValueError naming the combination it is not built with."""
+    k = int(getattr(args, "speculative_tokens", 0) or 0)
+    if k < 0:
+        raise ValueError(f"--speculative_tokens {k}: expected >= 0")
+    if k == 0:
+        return 0
+    if args.push:
+        raise ValueError("--speculative_tokens with --push is not built (a pushed chain returns one token)")
+    if int(args.num_sessions) > 1:
+        raise ValueError("--speculative_tokens with --num_sessions > 1 is not built (one session per client)")
+    if args.device_channel == "on":
+        raise ValueError("--speculative_tokens with the device channel (--device_channel on) is not built: "
+                         "its engine steps one token per session")
+    if cfg.sliding_window and getattr(args, "sliding_window", "cap") == "attend":
+        raise ValueError("--speculative_tokens with a sliding-window model in --sliding_window attend mode is not "
+                         "built: a rewind after a verify step can need a page the rolling window has released")
+    return k
+
+
 @torch.inference_mode()
-def run_rank0(args, device, cuts: List[int], on_token=None, results: Optional[list] = None):
+def run_rank0(args, device, cuts: List[int], on_token=None, results: Optional[list] = None, drafter=None,
+              on_step=None, session_id: Optional[str] = None):
     """``on_token(request, token)`` / ``results`` (filled with every session's tokens) are
-    hooks for embedding the client (tests, fault-injection harnesses) on the device-channel path."""
+    hooks for embedding the client (tests, fault-injection harnesses) on the device-channel path.
+    ``drafter`` replaces the ``--draft`` one of ``--speculative_tokens``; ``on_step(i)`` runs before its
+    i-th decode / verify step; ``results``, when given, also receives that loop's ``SpecStats``.
+    ``session_id`` names the TCP session (default: a fresh uuid); the last stage's sampling seeds derive
+    from it, so two runs with the same one draw the same tokens."""
     cfg = resolve_model(args.model)
+    spec_k = _check_speculative(args, cfg)
     L = cfg.num_hidden_layers
     stage0_end = cuts[0]
     n_servers = len(cuts)
@@ -238,11 +270,14 @@ def run_rank0(args, device, cuts: List[int], on_token=None, results: Optional[li
                       push=args.push, active_adapter=adapter)
     ids = tok(args.prompt, return_tensors="pt").input_ids.reshape(-1)
     Lp = int(ids.numel())
-    sid = str(uuid.uuid4())
+    sid = session_id or str(uuid.uuid4())
     max_length = Lp + args.max_new_tokens
     if args.device_channel != "off":
         route = tx._get_route(sid)
         if args.device_channel == "on" or tx.device_channel_possible(route, device):
+            if spec_k:  # (--device_channel auto found every hop on this machine)
+                raise ValueError("--speculative_tokens with the device channel is not built: its engine steps one "
+                                 "token per session (pass --device_channel off for the TCP path)")
             return _run_rank0_channel(args, device, ex, tok, tx, route, ids, on_token=on_token, results=results)
         logger.info("device channel not possible (a hop is on another machine or did not announce one): TCP path")
     if int(args.num_sessions) > 1:
@@ -258,26 +293,46 @@ def run_rank0(args, device, cuts: List[int], on_token=None, results: Optional[li
     cur_len = Lp + 1
     repeat, last = 0, None
     t1 = time.perf_counter()
-    for _ in range(args.max_new_tokens - 1):
-        if eos is not None and next_id == eos:
-            logger.info("EOS token generated, stopping generation")
-            break
-        hidden = ex.forward([(sid, 1)], torch.tensor([next_id], device=device), starts=[cur_len - 1],
-                            adapters=[adapter])
-        tx.send_decode_step(cur_len, hidden, session_id=sid, max_length=max_length, generated_tokens=generated)
-        next_id = tx.recv_token()
-        if eos is not None and next_id == eos:
-            logger.info("EOS token generated, stopping generation")
-            break
-        if next_id == last:
-            repeat += 1
-            if repeat >= 5:
-                logger.warning(f"Consecutive repetition detected (token {next_id}), stopping generation")
+    if spec_k:
+        def decode_step(token, cur, gen):
+            h = ex.forward([(sid, 1)], torch.tensor([token], device=device), starts=[cur - 1], adapters=[adapter])
+            tx.send_decode_step(cur, h, session_id=sid, max_length=max_length, generated_tokens=gen)
+            return tx.recv_token()
+
+        def verify_step(tokens, cur, gen):
+            # the first blocks run the block on top of the session's KV; ``starts`` rewinds the client's
+            # own session past the rows of an earlier block that were not kept
+            h = ex.forward([(sid, len(tokens))], torch.tensor(tokens, device=device), starts=[cur - len(tokens)],
+                           adapters=[adapter])
+            return tx.send_verify_step(cur, h, sid, max_length, gen, tokens[1:])
+
+        generated, stats = speculative_generate(
+            next_id, ids.tolist(), args.max_new_tokens, spec_k, drafter or DRAFTERS[args.draft](), decode_step,
+            verify_step, eos=eos, max_length=max_length, on_step=on_step, log=logger)
+        logger.info(stats.summary())
+        if results is not None:
+            results.append(stats)
+    else:
+        for _ in range(args.max_new_tokens - 1):
+            if eos is not None and next_id == eos:
+                logger.info("EOS token generated, stopping generation")
                 break
-        else:
-            repeat, last = 0, next_id
-        generated.append(next_id)
-        cur_len += 1
+            hidden = ex.forward([(sid, 1)], torch.tensor([next_id], device=device), starts=[cur_len - 1],
+                                adapters=[adapter])
+            tx.send_decode_step(cur_len, hidden, session_id=sid, max_length=max_length, generated_tokens=generated)
+            next_id = tx.recv_token()
+            if eos is not None and next_id == eos:
+                logger.info("EOS token generated, stopping generation")
+                break
+            if next_id == last:
+                repeat += 1
+                if repeat >= 5:
+                    logger.warning(f"Consecutive repetition detected (token {next_id}), stopping generation")
+                    break
+            else:
+                repeat, last = 0, next_id
+            generated.append(next_id)
+            cur_len += 1
     t2 = time.perf_counter()
     text = tok.decode(generated, skip_special_tokens=True)
     print(f"\n{'=' * 80}\nPROMPT: {args.prompt}\nGENERATED: {text}\n{'=' * 80}\n", flush=True)

@@ -1102,6 +1102,46 @@ def sample(logits, temps, top_ps, top_ks, rep_pens, recent, recent_len, seeds, w
     return out
 
 
+def sample_verify_workspace(R: int, V: int, cap: int) -> int:
+    """fp32 elements of workspace ``sample_verify`` needs for R rows of a V-wide vocabulary and
+    histories of ``cap`` ids: the samplers' R * V, then the per-row arguments it expands."""
+    return int(torch.ops.mpamd.sample_verify_ws(int(R), int(V), int(cap))) if native_available() else 1
+
+
+def sample_verify(logits, row_start, draft, temps, top_ps, top_ks, rep_pens, recent, recent_len, seeds,
+                  workspace=None, tokens=None, count=None, update_history: bool = False, all_greedy: bool = False):
+    """Speculative verify.  Session s owns the logits rows ``row_start[s] .. row_start[s + 1] - 1``
+    (K_s + 1 of them); row j is drawn as ``sample`` would draw it with the history
+    ``(h_s + draft[0..j-1])[-cap:]``, seed ``seeds[row]`` and s as the random number's row term,
+    and checked against ``draft[row]`` (-1 on the session's last row).  ``tokens`` gets the
+    session's leading draws that equal their draft and the one after them, -1 behind;
+    ``count[s]`` how many that is.  ``update_history`` pushes exactly those into ``recent[s]``.
+    ``all_greedy``: the caller knows every temperature is <= 0 (argmax rows, no sampler).
+    Returns (tokens int64 [R], count int32 [S])."""
+    R, V = logits.shape
+    S = row_start.numel() - 1
+    if not _native(logits):
+        t, c = ref.sample_verify(logits, row_start, draft, temps, top_ps, top_ks, rep_pens, recent, recent_len, seeds,
+                                 update_history=update_history)
+        if tokens is not None:
+            tokens[:R].copy_(t)
+            t = tokens
+        if count is not None:
+            count[:S].copy_(c)
+            c = count
+        return t, c
+    if tokens is None:
+        tokens = torch.empty(R, dtype=torch.long, device=logits.device)
+    if count is None:
+        count = torch.empty(S, dtype=torch.int32, device=logits.device)
+    if workspace is None:
+        workspace = torch.empty(sample_verify_workspace(R, V, recent.shape[1]), dtype=torch.float32,
+                                device=logits.device)
+    torch.ops.mpamd.sample_verify(logits, row_start, draft, temps, top_ps, top_ks, rep_pens, recent, recent_len,
+                                  seeds, workspace, tokens, count, int(bool(update_history)), int(bool(all_greedy)))
+    return tokens, count
+
+
 _RW_OK = {}
 
 

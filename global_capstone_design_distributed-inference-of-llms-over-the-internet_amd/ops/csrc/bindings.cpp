@@ -591,6 +591,53 @@ void sample(const at::Tensor& logits, const at::Tensor& temps, const at::Tensor&
                "sample");
 }
 
+int64_t sample_verify_ws(int64_t R, int64_t V, int64_t cap) { return mp_sample_verify_ws_words(R, V, cap); }
+
+void sample_verify(const at::Tensor& logits, const at::Tensor& row_start, const at::Tensor& draft,
+                   const at::Tensor& temps, const at::Tensor& top_ps, const at::Tensor& top_ks,
+                   const at::Tensor& rep_pens, at::Tensor& recent, at::Tensor& recent_len, const at::Tensor& seeds,
+                   at::Tensor& workspace, at::Tensor& tokens, at::Tensor& count, int64_t update, int64_t all_greedy) {
+  check_bf16_cuda(logits, "logits");
+  check_rows(logits, "logits");
+  const int R = logits.size(0), V = logits.size(1);
+  const int S = (int)row_start.numel() - 1;
+  MP_CHECK(row_start.scalar_type() == at::kInt && row_start.is_cuda() && row_start.is_contiguous() && S >= 0,
+           "row_start int32 [S + 1]");
+  MP_CHECK(draft.scalar_type() == at::kInt && draft.is_cuda() && draft.is_contiguous() && draft.numel() == R,
+           "draft int32 [R]");
+  MP_CHECK(temps.scalar_type() == at::kFloat && temps.is_cuda() && temps.is_contiguous() && temps.numel() == S,
+           "temps");
+  MP_CHECK(top_ps.scalar_type() == at::kFloat && top_ps.is_cuda() && top_ps.is_contiguous() && top_ps.numel() == S,
+           "top_ps");
+  MP_CHECK(top_ks.scalar_type() == at::kInt && top_ks.is_cuda() && top_ks.is_contiguous() && top_ks.numel() == S,
+           "top_ks");
+  MP_CHECK(rep_pens.scalar_type() == at::kFloat && rep_pens.is_cuda() && rep_pens.is_contiguous() &&
+               rep_pens.numel() == S,
+           "rep_pens");
+  MP_CHECK(recent.scalar_type() == at::kInt && recent.is_cuda() && recent.dim() == 2 && recent.size(0) == S &&
+               recent.size(1) >= 1 && recent.is_contiguous(),
+           "recent int32 [S, n]");
+  MP_CHECK(recent_len.scalar_type() == at::kInt && recent_len.is_cuda() && recent_len.is_contiguous() &&
+               recent_len.numel() == S,
+           "recent_len");
+  MP_CHECK(seeds.scalar_type() == at::kLong && seeds.is_cuda() && seeds.is_contiguous() && seeds.numel() == R,
+           "seeds int64 [R]");
+  MP_CHECK(workspace.scalar_type() == at::kFloat && workspace.is_cuda() && workspace.is_contiguous() &&
+               workspace.numel() >= mp_sample_verify_ws_words(R, V, recent.size(1)),
+           "workspace (sample_verify_ws floats)");
+  MP_CHECK(tokens.scalar_type() == at::kLong && tokens.is_cuda() && tokens.is_contiguous() && tokens.numel() >= R,
+           "tokens int64 [R]");
+  MP_CHECK(count.scalar_type() == at::kInt && count.is_cuda() && count.is_contiguous() && count.numel() >= S,
+           "count int32 [S]");
+  check_launch(mp_sample_verify(logits.data_ptr(), logits.stride(0), R, S, V, row_start.data_ptr<int32_t>(),
+                                draft.data_ptr<int32_t>(), temps.data_ptr<float>(), top_ps.data_ptr<float>(),
+                                top_ks.data_ptr<int32_t>(), rep_pens.data_ptr<float>(), recent.data_ptr<int32_t>(),
+                                recent.size(1), recent_len.data_ptr<int32_t>(), seeds.data_ptr<int64_t>(),
+                                workspace.data_ptr<float>(), tokens.data_ptr<int64_t>(), count.data_ptr<int32_t>(),
+                                (int)update, (int)all_greedy, cur_stream()),
+               "sample_verify");
+}
+
 // The decode GEMM arguments every gemm* op shares, after its checks (the caller sets x_stride, wsc,
 // as, gate where it has them)
 static mp::GemmArgs gemm_args(const void* x, const void* w, void* y, int64_t y_stride, const void* res,
@@ -1060,6 +1107,11 @@ TORCH_LIBRARY(mpamd, m) {
   m.def(
       "sample(Tensor logits, Tensor temps, Tensor top_ps, Tensor top_ks, Tensor rep_pens, Tensor(c!) recent, "
       "Tensor(d!) recent_len, Tensor seeds, Tensor(a!) workspace, Tensor(b!) out, int update=0) -> ()");
+  m.def("sample_verify_ws(int R, int V, int cap) -> int", &sample_verify_ws);
+  m.def(
+      "sample_verify(Tensor logits, Tensor row_start, Tensor draft, Tensor temps, Tensor top_ps, Tensor top_ks, "
+      "Tensor rep_pens, Tensor(c!) recent, Tensor(d!) recent_len, Tensor seeds, Tensor(a!) workspace, "
+      "Tensor(b!) tokens, Tensor(e!) count, int update=0, int all_greedy=0) -> ()");
   m.def(
       "gemm(Tensor x, Tensor wp, Tensor(a!) y, Tensor? residual, int epilogue, int M, int flags, "
       "Tensor(b!)? workspace=None, Tensor? gate=None, Tensor(c!)? ap=None, Tensor(d!)? ss_out=None, "
@@ -1109,6 +1161,7 @@ TORCH_LIBRARY_IMPL(mpamd, CUDA, m) {
   m.impl("add", &add);
   m.impl("argmax", &argmax);
   m.impl("sample", &sample);
+  m.impl("sample_verify", &sample_verify);
   m.impl("gemm", &gemm);
   m.impl("gemm_w8", &gemm_w8);
   m.impl("gemm_w4", &gemm_w4);

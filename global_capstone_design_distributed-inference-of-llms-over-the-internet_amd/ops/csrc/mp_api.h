@@ -179,6 +179,14 @@ int mp_argmax(const void* logits, int64_t stride, int R, int V, int64_t* out, hi
 int mp_sample(const void* logits, int64_t stride, int R, int V, const float* temps, const float* top_ps,
               const int32_t* top_ks, const float* rep_pens, int32_t* recent, int recent_stride, int32_t* recent_len,
               const int64_t* seeds, float* ws, int64_t* out, int update, hipStream_t stream);
+// Speculative verify: sample the R rows of S sessions (session s: rows row_start[s] .. row_start[s + 1] - 1,
+// each against the history its accepted drafts would leave), keep every session's leading draws that
+// equal their draft plus one more, -1 after; count[s] kept ids.  ws holds mp_sample_verify_ws_words words.
+int64_t mp_sample_verify_ws_words(int R, int V, int cap);
+int mp_sample_verify(const void* logits, int64_t stride, int R, int S, int V, const int32_t* row_start,
+                     const int32_t* draft, const float* temps, const float* top_ps, const int32_t* top_ks,
+                     const float* rep_pens, int32_t* recent, int cap, int32_t* recent_len, const int64_t* seeds,
+                     float* ws, int64_t* tokens, int32_t* count, int update, int all_greedy, hipStream_t stream);
 // gemm.hip, gemm_wide.hip.  The GEMM entry points return 0, 1 when no form covers the shape (nothing
 // launched), < 0 for a bad call, else the HIP error.
 int mp_gemm_ss_elems();

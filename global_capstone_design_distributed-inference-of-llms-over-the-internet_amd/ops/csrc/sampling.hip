@@ -33,6 +33,10 @@ __device__ __forceinline__ uint64_t splitmix64(uint64_t x) {
   return x ^ (x >> 31);
 }
 
+// a row's random number is splitmix64(seed * SEED_MUL + row term); the term is the launch row
+// (mp_sample_verify turns it into the session index through the seed, see SEED_MUL_INV)
+constexpr uint64_t SEED_MUL = 0x9E3779B97F4A7C15ull;
+
 typedef unsigned long long u64;
 constexpr int SB = 1024;   // threads per block
 
@@ -359,7 +363,7 @@ __global__ __launch_bounds__(SB) void sample_kernel(const bf16_t* __restrict__ l
   MP_PROF(4);
   const int k = top_ks[row];
   const float tp = top_ps[row];
-  const uint64_t rnd = splitmix64((uint64_t)seeds[row] * 0x9E3779B97F4A7C15ull + (uint64_t)row);
+  const uint64_t rnd = splitmix64((uint64_t)seeds[row] * SEED_MUL + (uint64_t)row);
   const float u01 = (float)((double)(rnd >> 11) * (1.0 / 9007199254740992.0));
 
   if (k > 0 && k < V) {
@@ -1043,7 +1047,7 @@ __global__ __launch_bounds__(64) void sample_split_merge_kernel(
   }
   const float t2 = __shfl(inc2, 63, 64);
   const float ex2 = inc2 - q;
-  const uint64_t rnd = splitmix64((uint64_t)seeds[row] * 0x9E3779B97F4A7C15ull + (uint64_t)row);
+  const uint64_t rnd = splitmix64((uint64_t)seeds[row] * SEED_MUL + (uint64_t)row);
   const float u01 = (float)((double)(rnd >> 11) * (1.0 / 9007199254740992.0));
   const float uu = u01 * t2;
   const unsigned long long hit = __ballot(q > 0.f && uu >= ex2 && uu < ex2 + q);
@@ -1054,7 +1058,143 @@ __global__ __launch_bounds__(64) void sample_split_merge_kernel(
   }
 }
 
+// ---------------------------------------------------------------------------------------
+// Speculative verify (mp_sample_verify): session s owns the K_s + 1 contiguous logits rows
+// row_start[s] .. row_start[s + 1] - 1, and row j is checked against draft[row_start[s] + j].
+//   1. verify_expand_kernel gives every row the arguments a one-token step of its session would
+//      sample it with: the session's parameters, the history window (h + draft[0..j-1])[-cap:], and
+//      a seed that makes the samplers' row term the SESSION index (below);
+//   2. the sample kernels above draw all R rows, unchanged and without touching the histories;
+//   3. verify_accept_kernel, one wave per session, counts the leading draws that equal their
+//      draft, keeps those and the first that does not, pads with -1 and pushes the kept ids.
+// The samplers draw from splitmix64(seed * MUL + row) with the launch row.  MUL is odd, so it has
+// an inverse INV mod 2^64, and seed' = seed + (s - row) * INV gives seed' * MUL + row == seed * MUL
+// + s: the row draws what row s of a one-token step draws, with the samplers as they are.
+constexpr uint64_t SEED_MUL_INV = 0xF1DE83E19937733Dull;
+static_assert(SEED_MUL * SEED_MUL_INV == 1ull, "SEED_MUL_INV inverts the samplers' seed multiplier");
+
+// a session's row range, clamped into [0, R] (row_start is device data that no host check sees)
+__device__ __forceinline__ void verify_rows(const int32_t* row_start, int s, int R, int* lo, int* hi) {
+  const int a = min(max(row_start[s], 0), R);
+  *lo = a;
+  *hi = min(max(row_start[s + 1], a), R);
+}
+
+__global__ __launch_bounds__(64) void verify_expand_kernel(
+    int R, const int32_t* __restrict__ row_start, const int32_t* __restrict__ draft, const float* __restrict__ temps,
+    const float* __restrict__ top_ps, const int32_t* __restrict__ top_ks, const float* __restrict__ rep_pens,
+    const int32_t* __restrict__ recent, int cap, const int32_t* __restrict__ recent_len,
+    const int64_t* __restrict__ seeds, float* __restrict__ x_temps, float* __restrict__ x_top_ps,
+    int32_t* __restrict__ x_top_ks, float* __restrict__ x_rep_pens, int32_t* __restrict__ x_recent,
+    int32_t* __restrict__ x_len, int64_t* __restrict__ x_seeds) {
+  const int s = blockIdx.x, l = threadIdx.x;
+  int lo, hi;
+  verify_rows(row_start, s, R, &lo, &hi);
+  const int n = min(max(recent_len[s], 0), cap);
+  const int32_t* h = recent + (int64_t)s * cap;
+  const float temp = temps[s], tp = top_ps[s], rp = rep_pens[s];
+  const int tk = top_ks[s];
+  for (int row = lo; row < hi; ++row) {
+    const int j = row - lo;                    // drafts before this row
+    const int w = min(n + j, cap), skip = n + j - w;  // the window: the last w of h + draft[0..j-1]
+    for (int i = l; i < w; i += 64) {
+      const int p = skip + i;
+      x_recent[(int64_t)row * cap + i] = p < n ? h[p] : draft[lo + p - n];
+    }
+    if (l == 0) {
+      x_temps[row] = temp;
+      x_top_ps[row] = tp;
+      x_top_ks[row] = tk;
+      x_rep_pens[row] = rp;
+      x_len[row] = w;
+      x_seeds[row] = (int64_t)((uint64_t)seeds[row] + (uint64_t)(int64_t)(s - row) * SEED_MUL_INV);
+    }
+  }
+}
+
+__global__ __launch_bounds__(64) void verify_accept_kernel(
+    int R, const int32_t* __restrict__ row_start, const int32_t* __restrict__ draft, const int64_t* __restrict__ x_tok,
+    int32_t* __restrict__ recent, int cap, int32_t* __restrict__ recent_len, int64_t* __restrict__ tokens,
+    int32_t* __restrict__ count, int update) {
+  __shared__ int32_t s_old[SB];  // the session's history before the push (cap <= SB)
+  const int s = blockIdx.x, l = threadIdx.x;
+  int lo, hi;
+  verify_rows(row_start, s, R, &lo, &hi);
+  const int nrow = hi - lo;
+  if (nrow <= 0) {
+    if (l == 0) count[s] = 0;
+    return;
+  }
+  const int K = nrow - 1;
+  int miss = K;  // the first row whose draw is not its draft (K: every draft accepted)
+  for (int j = l; j < K; j += 64)
+    if (x_tok[lo + j] != (int64_t)draft[lo + j]) { miss = j; break; }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) miss = min(miss, __shfl_xor(miss, o, 64));
+  const int keep = miss + 1;
+  for (int j = l; j < nrow; j += 64) tokens[lo + j] = j < keep ? x_tok[lo + j] : (int64_t)-1;
+  if (l == 0) count[s] = keep;
+  if (!update) return;
+  // push the kept ids: the history becomes the last min(n + keep, cap) of h + t_0..t_miss
+  int32_t* h = recent + (int64_t)s * cap;
+  const int n = min(max(recent_len[s], 0), cap);
+  for (int i = l; i < n; i += 64) s_old[i] = h[i];
+  __syncthreads();
+  const int w = min(n + keep, cap), skip = n + keep - w;
+  for (int i = l; i < w; i += 64) {
+    const int p = skip + i;
+    h[i] = p < n ? s_old[p] : (int32_t)x_tok[lo + p - n];
+  }
+  if (l == 0) recent_len[s] = w;
+}
+
 }  // namespace mp
+
+// 4-byte words of workspace mp_sample_verify needs: the samplers' R * V, then per row the two
+// 8-byte columns (seed, drawn id), the five 4-byte ones and the history window
+extern "C" int64_t mp_sample_verify_ws_words(int R, int V, int cap) {
+  return (((int64_t)R * V + 3) & ~(int64_t)3) + (int64_t)R * (9 + cap);
+}
+
+extern "C" int mp_sample_verify(const void* logits, int64_t stride, int R, int S, int V, const int32_t* row_start,
+                                const int32_t* draft, const float* temps, const float* top_ps,
+                                const int32_t* top_ks, const float* rep_pens, int32_t* recent, int cap,
+                                int32_t* recent_len, const int64_t* seeds, float* ws, int64_t* tokens,
+                                int32_t* count, int update, int all_greedy, hipStream_t stream) {
+  (void)hipGetLastError();
+  using namespace mp;
+  if (S == 0) return 0;
+  if (R < 0 || cap > SB || cap < 1) return -1;
+  // the per-row columns, behind the samplers' workspace (16-byte aligned: ws is, R * V is rounded up)
+  float* base = ws + (((int64_t)R * V + 3) & ~(int64_t)3);
+  int64_t* x_seeds = reinterpret_cast<int64_t*>(base);
+  int64_t* x_tok = x_seeds + R;
+  float* x_temps = reinterpret_cast<float*>(x_tok + R);
+  float* x_top_ps = x_temps + R;
+  int32_t* x_top_ks = reinterpret_cast<int32_t*>(x_top_ps + R);
+  float* x_rep_pens = reinterpret_cast<float*>(x_top_ks + R);
+  int32_t* x_len = reinterpret_cast<int32_t*>(x_rep_pens + R);
+  int32_t* x_recent = x_len + R;
+  if (R > 0) {
+    if (all_greedy) {  // every row an argmax row: no sampler, as BatchSampler does for a plain step
+      const int e = mp_argmax(logits, stride, R, V, x_tok, stream);
+      if (e) return e;
+    } else {
+      // rows that no session owns sample as greedy rows with an empty history (temperature 0)
+      hipError_t e = hipMemsetAsync(base, 0, sizeof(float) * (size_t)R * (9 + cap), stream);
+      if (e != hipSuccess) return (int)e;
+      hipLaunchKernelGGL(verify_expand_kernel, dim3(S), dim3(64), 0, stream, R, row_start, draft, temps, top_ps,
+                         top_ks, rep_pens, recent, cap, recent_len, seeds, x_temps, x_top_ps, x_top_ks, x_rep_pens,
+                         x_recent, x_len, x_seeds);
+      const int e2 = mp_sample(logits, stride, R, V, x_temps, x_top_ps, x_top_ks, x_rep_pens, x_recent, cap, x_len,
+                               x_seeds, ws, x_tok, 0, stream);
+      if (e2) return e2;
+    }
+  }
+  hipLaunchKernelGGL(verify_accept_kernel, dim3(S), dim3(64), 0, stream, R, row_start, draft, x_tok, recent, cap,
+                     recent_len, tokens, count, update);
+  return (int)hipGetLastError();
+}
 
 extern "C" int mp_sample(const void* logits, int64_t stride, int R, int V, const float* temps, const float* top_ps,
                          const int32_t* top_ks, const float* rep_pens, int32_t* recent, int recent_stride,

@@ -414,6 +414,42 @@ def sample(logits, temps, top_ps, top_ks, rep_pens, recent, recent_len, seeds, w
     return res
 
 
+def sample_verify(logits, row_start, draft, temps, top_ps, top_ks, rep_pens, recent, recent_len, seeds,
+                  update_history: bool = False):
+    """Speculative verify, the semantics of ``ops.sample_verify``.  Session s owns the rows
+    ``row_start[s] .. row_start[s + 1] - 1``; row j is drawn by ``sample_row`` with the history
+    ``(h_s + draft[0..j-1])[-cap:]`` and a generator seeded with ``seeds[row]``.  n_s = the leading
+    rows whose draw equals their draft; the session keeps t_0 .. t_{n_s}.  Returns
+    (tokens int64 [R]: the kept ids, -1 behind them; count int32 [S] = n_s + 1)."""
+    R = logits.shape[0]
+    S = row_start.numel() - 1
+    cap = recent.shape[1]
+    tokens = torch.full((R,), -1, dtype=torch.long, device=logits.device)
+    count = torch.zeros(S, dtype=torch.int32, device=logits.device)
+    rs = [int(v) for v in row_start.tolist()]
+    for s in range(S):
+        lo, hi = rs[s], rs[s + 1]
+        if hi <= lo:
+            continue
+        hist = [int(t) for t in recent[s, : int(recent_len[s])].tolist()]
+        kept = 0
+        for row in range(lo, hi):
+            g = torch.Generator(device="cpu")
+            g.manual_seed(int(seeds[row]) & 0x7FFFFFFFFFFFFFFF)
+            t = sample_row(logits[row].cpu(), float(temps[s]), float(top_ps[s]), int(top_ks[s]), float(rep_pens[s]),
+                           hist[-cap:], generator=g)
+            tokens[row] = t
+            kept += 1
+            if row == hi - 1 or t != int(draft[row]):
+                break
+            hist.append(t)
+        count[s] = kept
+        if update_history:
+            for t in tokens[lo:lo + kept].tolist():
+                push_history(recent[s:s + 1], recent_len[s:s + 1], [t])
+    return tokens, count
+
+
 # ------------------------------------------------------------------ fp8 (OCP e4m3fn) W8A8
 FP8_MAX = 448.0
 

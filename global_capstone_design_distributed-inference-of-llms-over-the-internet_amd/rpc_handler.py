@@ -27,6 +27,13 @@ reply format, and changes the engine underneath:
 Metadata keys: session_id, seq_len, cur_len, is_prefill, is_replay, max_length, temperature,
 top_p, top_k, repetition_penalty (default 1.5), generated_tokens.  Final-stage replies carry
 ``token_id`` (and an int64 [[token]] tensor); others return hidden [1, T, H].
+
+Speculative verify: a request with ``draft_tokens`` = [d_1..d_K] carries K + 1 rows (the last
+accepted token's, then the drafts'), ``cur_len`` counting all of them.  Other stages run it as
+the multi-token step it is; the final stage samples every row against the history its accepted
+drafts would leave (``BatchSampler.verify``) and replies ``token_ids`` = [t_0..t_n] (the accepted
+drafts and the token after them), ``token_id`` = t_0 and an int64 [1, n + 1] tensor.  The session
+is left at ``start + K + 1``; the next request's ``cur_len`` rewinds it.
 """
 from __future__ import annotations
 
@@ -74,6 +81,7 @@ class _Req:
     priority: float = 2.0
     prompts: Optional[torch.Tensor] = None  # deep prompts [n_blocks, P, H] for this step
     adapter: str = ""        # metadata["active_adapter"] (upstream _get_active_adapter); "": the base model
+    drafts: Optional[List[int]] = None  # metadata["draft_tokens"]: a speculative verify step (x: K + 1 rows)
 
 
 class StageConnectionHandler:
@@ -440,6 +448,18 @@ class StageConnectionHandler:
         params = SamplingParams(float(md.get("temperature", self._default.temperature)),
                                 float(md.get("top_p", self._default.top_p)), int(md.get("top_k", self._default.top_k)),
                                 float(md.get("repetition_penalty", self._default.repetition_penalty)))
+        drafts = md.get("draft_tokens")
+        if drafts is not None:
+            drafts = [int(t) for t in drafts]
+            if getattr(self.executor, "window", 0):
+                raise ValueError("draft_tokens with --sliding_window attend is not built: the rewind after a "
+                                 "speculative verify step can need a page the rolling window has released")
+            V = int(self.executor.cfg.vocab_size)
+            if any(not 0 <= d < V for d in drafts):
+                raise ValueError(f"draft_tokens outside the vocabulary [0, {V})")
+            if len(drafts) != T - 1:
+                raise ValueError(f"draft_tokens names {len(drafts)} drafts, the request has {T} rows "
+                                 f"(the last accepted token's and one per draft)")
         prompts = None
         if md.get("has_prompts") and len(msg.tensors) > 1:
             # upstream layout [n_blocks, B(=1), P, H]; one session per request here
@@ -448,7 +468,7 @@ class StageConnectionHandler:
                 prompts = prompts[:, 0]
         return _Req(sid, x, start, reset, params, list(md.get("generated_tokens", []) or []),
                     md.get("max_length"), None, time.perf_counter(), prompts=prompts,
-                    adapter=str(md.get("active_adapter") or ""))
+                    adapter=str(md.get("active_adapter") or ""), drafts=drafts)
 
     async def _submit(self, msg: Message) -> Message:
         req = self._parse(msg)
@@ -537,11 +557,16 @@ class StageConnectionHandler:
         ml = max((int(r.max_length) for r in batch if r.max_length), default=None)
         phase = "handler.prefill" if any(r.x.shape[0] > 1 for r in batch) else "handler.decode"
         prompts = [r.prompts for r in batch] if any(r.prompts is not None for r in batch) else None
+        # speculative verify (final stage): such a request wants the logits of all its K + 1 rows
+        verify = self.final_stage and any(r.drafts is not None for r in batch)
+        plan_kw = {"logit_rows": [len(r.drafts) + 1 if r.drafts is not None else 1 for r in batch]} if verify else {}
         with torch.inference_mode(), self.timer(phase), ex.exec_lock:
             out = ex.forward(seqs, x, reset=[r.reset for r in batch], starts=[r.start for r in batch], max_length=ml,
-                             prompts=prompts, adapters=[r.adapter for r in batch])
+                             prompts=prompts, adapters=[r.adapter for r in batch], **plan_kw)
             self.stats["batches"] += 1
             self.stats["tokens"] += int(x.shape[0])
+            if verify:
+                return self._verify_replies(batch, out)
             if self.final_stage:
                 seeds = [session_seed(r.sid, r.start + r.x.shape[0], self.seed) for r in batch]
                 toks = self._sampler(out, [r.params for r in batch], [r.generated for r in batch], seeds).tolist()
@@ -569,6 +594,25 @@ class StageConnectionHandler:
             if amax > 100:
                 logger.warning(f"[{r.sid[:8]}] large activation values detected (|x|max={amax:.2f})")
             res.append(Message({"session_id": r.sid}, [h.unsqueeze(0)]))
+        return res
+
+    def _verify_replies(self, batch: List[_Req], logits: torch.Tensor) -> List[Message]:
+        """Final stage of a step with verify requests: one ``BatchSampler.verify`` call over every request
+        (a plain one is a session without drafts).  The row that yields the token at position p is
+        seeded with ``session_seed(sid, p)``, as a one-token step's is."""
+        drafts = [r.drafts or [] for r in batch]
+        seeds = [[session_seed(r.sid, r.start + r.x.shape[0] - len(d) + j, self.seed) for j in range(len(d) + 1)]
+                 for r, d in zip(batch, drafts)]
+        kept = self._sampler.verify(logits, drafts, [r.params for r in batch], [r.generated for r in batch], seeds)
+        self.stats["verify_steps"] = self.stats.get("verify_steps", 0) + sum(r.drafts is not None for r in batch)
+        res = []
+        for r, toks in zip(batch, kept):
+            md = {"token_id": int(toks[0]), "session_id": r.sid}
+            if r.drafts is not None:
+                md["token_ids"] = [int(t) for t in toks]
+                res.append(Message(md, [torch.tensor([toks], dtype=torch.long)]))
+            else:
+                res.append(Message(md, [torch.tensor([[int(toks[0])]], dtype=torch.long)]))
         return res
 
     def shutdown(self):

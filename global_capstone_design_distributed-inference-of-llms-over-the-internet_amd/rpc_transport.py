@@ -317,7 +317,8 @@ class RpcTransport:
                     tail = await asyncio.get_running_loop().run_in_executor(None, self._route_tail, route, k, exclude)
                     route = route[:k] + tail
                     self.session_routes[session_id] = route
-                    base = {kk: v for kk, v in md.items() if kk not in ("seq_len", "cur_len", "is_prefill")}
+                    base = {kk: v for kk, v in md.items()
+                            if kk not in ("seq_len", "cur_len", "is_prefill", "draft_tokens")}
                     await self._replay_tail(session_id, route, k, base)
                 except RECOVERABLE + (RuntimeError,) as re:
                     logger.error(f"recovery attempt failed: {re}")
@@ -334,7 +335,8 @@ class RpcTransport:
             return self._finish(which, times, t_all, resp)
         raise RuntimeError("No final stage returned a token")
 
-    def _finish(self, which: str, times, t_all: float, resp: Message) -> int:
+    def _finish(self, which: str, times, t_all: float, resp: Message):
+        """The step's token (``which`` "verify": the list of tokens a speculative block kept)."""
         total = time.perf_counter() - t_all
         if which == "prefill":
             self.last_prefill_stage_times, self.last_prefill_total = times, total
@@ -342,6 +344,14 @@ class RpcTransport:
             self.last_decode_stage_times, self.last_decode_total = times, total
             self.decode_stage_history.append(times)
             self.decode_total_times.append(total)
+        if which == "verify":
+            ids = resp.metadata.get("token_ids")
+            if not ids:
+                # a final stage that does not know draft_tokens sampled the block's LAST row only: its
+                # token_id belongs to another position than t_0
+                raise RuntimeError("the final stage's reply to a verify step carries no token_ids: it does not "
+                                   "serve speculative verify steps (run without --speculative_tokens)")
+            return [int(t) for t in ids]
         return self._token_of(resp)
 
     # ------------------------------------------------------------------ public API
@@ -361,6 +371,35 @@ class RpcTransport:
                               max_length=int(max_length), generated_tokens=list(generated_tokens or [])[-50:])
         self._get_route(session_id)
         self._last_token = self._run(self._send(session_id, hidden, md, "decode"))
+
+    def send_verify_step(self, cur_len: int, hidden: torch.Tensor, session_id: str, max_length: int,
+                         generated_tokens: Optional[List[int]], draft_tokens: Sequence[int]) -> List[int]:
+        """One speculative verify step: ``hidden`` [K + 1, H] holds the row of the last accepted token
+        and the rows of the K ``draft_tokens``; ``cur_len`` counts all of them.  Returns the tokens the
+        final stage kept, [t_0..t_n]: its draws for the n accepted drafts and the token after them.
+        The inputs recorded for failover replay are trimmed to the kept n + 1 rows at every
+        hop, so a replay (``_replay_tail``) rebuilds exactly the accepted sequence."""
+        if self.stage != 0:
+            raise RuntimeError("send_verify_step should only be called by stage0")
+        if self.push:
+            raise ValueError("speculative verify steps with push are not built")
+        K = len(draft_tokens)
+        md = self._session_md(session_id, seq_len=K + 1, cur_len=int(cur_len), is_prefill=False,
+                              max_length=int(max_length), generated_tokens=list(generated_tokens or [])[-50:],
+                              draft_tokens=[int(t) for t in draft_tokens])
+        self._get_route(session_id)
+        toks = self._run(self._send(session_id, hidden, md, "verify"))
+        keep = len(toks)
+        if not 1 <= keep <= K + 1:
+            raise RuntimeError(f"verify step of {K + 1} rows returned {keep} tokens")
+        # every hop of the route the step completed on recorded its input last: keep the accepted rows
+        hist = self.client_cache.get(session_id, {})
+        for hop in self.session_routes[session_id]:
+            xs = hist.get(hop.start)
+            if keep < K + 1 and xs and xs[-1].shape[1] == K + 1:
+                xs[-1] = xs[-1][:, :keep].clone()
+        self._last_token = toks[-1]
+        return toks
 
     def send_steps(self, steps: Sequence[Tuple[str, torch.Tensor, int, int, int, Optional[List[int]]]]) -> List[int]:
         """Concurrent sessions over TCP: one step (prefill when ``seq_len == cur_len``, else

@@ -78,6 +78,10 @@ class Plan:
     fablocks: Optional[torch.Tensor] = None  # [2, NBF] FA2 prefill workgroup blocks (csrc/attention_fa.hip)
     fa_waves: int = 4                   # waves per FA2 workgroup (ops.fa_plan)
     lora_slots: Optional[np.ndarray] = None  # int32 [T] adapter slot of every row; None: a base-model step
+    # ``logit_rows`` steps: (rows whose logits the step returns, in output order; where the sequences' last
+    # rows sit in that order; where the other rows sit)
+    extra: Optional[Tuple[np.ndarray, np.ndarray, np.ndarray]] = None
+    _extra_dev: Optional[tuple] = None
     _lora_dev: Optional[torch.Tensor] = None
     _dev: Optional[Tuple[torch.Tensor, torch.Tensor]] = None
     _upload: Optional[object] = None    # callable making the device copies
@@ -88,6 +92,19 @@ class Plan:
             self._dev = self._upload()
         (i64, i32), T = self._dev, self.T
         return i64[0], i64[1], i32[:T], i32[T:2 * T], i32[2 * T:]
+
+    def extra_rows(self, device):
+        """``_Step.extra`` of a ``logit_rows`` step: (the rows besides the last rows, int32; output positions of
+        the last rows; of the other rows; every returned row in output order), on the device."""
+        if self.extra is None:
+            return None
+        if self._extra_dev is None:
+            rows, lp, ep = self.extra
+            parts = (rows[ep], lp, ep, rows)
+            blob = torch.from_numpy(np.concatenate(parts)).to(device)  # one host-to-device copy
+            more, lp_d, ep_d, rows_d = torch.split(blob, [len(a) for a in parts])
+            self._extra_dev = (more.to(torch.int32), lp_d, ep_d, rows_d)
+        return self._extra_dev
 
     def lora(self, device):
         """(device slots int32 [T], host runs) of a LoRA step: ``_Step.lora``."""
@@ -119,6 +136,7 @@ class _Step:
     fa_waves: int = 4
     prompt: Optional[tuple] = None      # deep prompt (rows [R], values [n_layers, R, H])
     lora: Optional[tuple] = None        # (device slots int32 [T], host runs or None); None: a base-model step
+    extra: Optional[tuple] = None       # ``Plan.extra_rows``: more logit rows than the last ones (verify steps)
     bufs: dict = dataclasses.field(default_factory=dict)  # named buffers the caller keeps (else allocated)
 
     def buf(self, name: str, shape, dtype=None) -> torch.Tensor:
@@ -417,16 +435,28 @@ class StageExecutor:
 
     # ================================================================== planning
     def plan(self, seqs: Sequence[Tuple[str, int]], *, reset: Sequence[bool] = (), max_length: Optional[int] = None,
-             starts: Optional[Sequence[int]] = None, adapters: Optional[Sequence[Optional[str]]] = None) -> Plan:
+             starts: Optional[Sequence[int]] = None, adapters: Optional[Sequence[Optional[str]]] = None,
+             logit_rows: Optional[Sequence[int]] = None) -> Plan:
         """Open/extend sessions and build device metadata for a ragged step.
 
         ``seqs``: (session_id, n_tokens) pairs.  ``reset[i]`` clears the session first
         (prefill / replay).  ``starts[i]`` (optional) rewinds a session to that position
         (Petals' ``start_from_position``).  ``adapters[i]``: the LoRA adapter session i runs ("" or
         None: the base model), set when the session is opened or reset; a later step has to name the
-        same one.  Without ``adapters`` every session keeps its own.
+        same one.  Without ``adapters`` every session keeps its own.  ``logit_rows[i]`` (last stage): the
+        number of trailing rows of sequence i whose logits the step returns (default 1, its last row;
+        a speculative verify step asks for all of them).
         """
         S = len(seqs)
+        if logit_rows is not None:
+            if len(logit_rows) != S:
+                raise ValueError(f"logit_rows names {len(logit_rows)} sequences, the step has {S}")
+            for (sid, n), lr in zip(seqs, logit_rows):
+                if not 1 <= int(lr) <= max(int(n), 1):
+                    raise ValueError(f"logit_rows {int(lr)} of session {sid[:8]}: a {int(n)}-token sequence has "
+                                     f"1..{max(int(n), 1)} trailing rows")
+            if all(int(lr) == 1 for lr in logit_rows):
+                logit_rows = None  # every sequence's last row: the plain step
         if adapters is not None and len(adapters) != S:
             raise ValueError(f"adapters names {len(adapters)} sessions, the step has {S}")
         want = None if adapters is None else [self.adapter_slot(a) for a in adapters]  # (before any session opens)
@@ -459,6 +489,13 @@ class StageExecutor:
         n32 = h32[: 2 * T + S].numpy()
         native.build_meta(rows, st, ntoks, self.sessions.table, self.cache.page_size, n64[0], n64[1], n32[:T],
                           n32[T:2 * T], n32[2 * T:])
+        extra = None
+        if logit_rows is not None:
+            # sequence i's trailing logit_rows[i] rows, in sequence order; the last rows stay what they are
+            ends = np.cumsum(ntoks)
+            lrows = np.concatenate([np.arange(e - int(lr), e) for e, lr in zip(ends, logit_rows)]).astype(np.int64)
+            is_last = np.concatenate([np.arange(int(lr)) == int(lr) - 1 for lr in logit_rows])
+            extra = (lrows, np.flatnonzero(is_last), np.flatnonzero(~is_last))
         self.sessions.sync_table()
         max_ctx = int((st + ntoks).max()) if S else 0
         is_decode = bool(S and (ntoks == 1).all())
@@ -488,7 +525,7 @@ class StageExecutor:
         if self._lora is not None and any(s.adapter >= 0 for s in sess):
             row_slots = np.repeat(np.fromiter((s.adapter for s in sess), dtype=np.int32, count=S), ntoks)
         return Plan(sess, ntoks, st, T, max_ctx, is_decode, n64, n32, qb, sb, fb, fa_waves, lora_slots=row_slots,
-                    _upload=upload)
+                    extra=extra, _upload=upload)
 
     def adapter_slot(self, name: Optional[str]) -> int:
         """Slot of a hosted adapter; -1 for "" / None (the base model).  Unknown: ``KeyError("adapter X not found")``."""
@@ -516,7 +553,9 @@ class StageExecutor:
     def forward(self, seqs: Sequence[Tuple[str, int]], x: torch.Tensor, **plan_kw) -> torch.Tensor:
         """One ragged step.  ``x``: token ids [T] (first stage) or hidden [T, H].
 
-        Returns hidden [T, H] (non-last stage) or last-token logits [S, V] (last stage).
+        Returns hidden [T, H] (non-last stage) or last-token logits [S, V] (last stage; with
+        ``logit_rows`` the logits of every sequence's trailing ``logit_rows[i]`` rows, in sequence
+        order: [sum(logit_rows), V]).
         Steps larger than ``max_tokens_per_step`` run as consecutive chunks (chunked prefill,
         upstream Petals TransformerBackend.inference_step): a long prompt is split at token
         boundaries, later pieces attend to the KV the earlier pieces wrote.
@@ -555,8 +594,11 @@ class StageExecutor:
         return (torch.tensor(rows, dtype=torch.long, device=self.device),
                 torch.cat(vals, 1).to(self.device, self.dtype))
 
-    def _forward_chunked(self, seqs, x, reset: Sequence[bool] = (), starts=None, max_length=None, adapters=None):
+    def _forward_chunked(self, seqs, x, reset: Sequence[bool] = (), starts=None, max_length=None, adapters=None,
+                         logit_rows=None):
         C = self.max_tokens
+        if logit_rows is not None and len(logit_rows) != len(seqs):
+            raise ValueError(f"logit_rows names {len(logit_rows)} sequences, the step has {len(seqs)}")
         pieces = []  # (seq index, token offset within the seq, count, offset into x)
         xoff = 0
         for i, (sid, n) in enumerate(seqs):
@@ -581,6 +623,13 @@ class StageExecutor:
             used += take[2]
         if cur:
             chunks.append(cur)
+        if logit_rows is not None:
+            # a sequence's trailing rows come from its last piece alone (checked before any chunk runs)
+            for ch in chunks:
+                for (i, off, c, _) in ch:
+                    if off + c == int(seqs[i][1]) and int(logit_rows[i]) > c:
+                        raise ValueError(f"logit_rows {int(logit_rows[i])} of session {seqs[i][0][:8]} reach past "
+                                         f"the last chunk ({c} rows) of a chunked step")
         hidden, logits = [], [None] * len(seqs)
         for ch in chunks:
             sub = [(seqs[i][0], c) for (i, off, c, _) in ch]
@@ -588,14 +637,23 @@ class StageExecutor:
             sub_starts = [(starts[i] if (starts is not None and off == 0) else None) for (i, off, c, _) in ch]
             xs = torch.cat([x[xo:xo + c] for (_, _, c, xo) in ch])
             sub_ad = None if adapters is None else [adapters[i] for (i, _, _, _) in ch]
-            out = self.forward(sub, xs, reset=sub_reset, starts=sub_starts, max_length=max_length, adapters=sub_ad)
+            sub_lr = None
+            if logit_rows is not None:
+                sub_lr = [int(logit_rows[i]) if off + c == int(seqs[i][1]) else 1 for (i, off, c, _) in ch]
+            out = self.forward(sub, xs, reset=sub_reset, starts=sub_starts, max_length=max_length, adapters=sub_ad,
+                               logit_rows=sub_lr)
             if self.is_last:
+                o = 0
                 for r, (i, off, c, _) in enumerate(ch):
+                    n = 1 if sub_lr is None else sub_lr[r]
                     if off + c == int(seqs[i][1]):
-                        logits[i] = out[r]
+                        logits[i] = out[o] if logit_rows is None else out[o:o + n]
+                    o += n
             else:
                 hidden.append(out)
         if self.is_last:
+            if logit_rows is not None:
+                return torch.cat(logits)
             return torch.stack(logits)
         return torch.cat(hidden)
 
@@ -631,7 +689,7 @@ class StageExecutor:
             out = self._forward_llama(_Step(
                 x, *plan.meta(), plan.T, plan.max_ctx, plan.is_decode, self.device, self.dtype, qblocks=plan.qblocks,
                 superblocks=plan.superblocks, fablocks=plan.fablocks, fa_waves=plan.fa_waves, prompt=prompt,
-                lora=lora(self.device) if lora else None))
+                lora=lora(self.device) if lora else None, extra=plan.extra_rows(self.device)))
         if ev is not None:
             ev[1].record()
             ev[1].synchronize()
@@ -983,12 +1041,27 @@ class StageExecutor:
     def _head(self, st: _Step, res, mlp, stream) -> torch.Tensor:
         """What every path ends with: the last residual add (``mlp`` None: done already), then (last stage) the
         final norm and ``lm_head`` on every sequence's last row.  ``stream``: the fused path's (xr, ss_in)."""
-        cfg, w, T, eps = self.cfg, self.w, st.T, self.cfg.rms_norm_eps
-        H, V = cfg.hidden_size, cfg.vocab_size
+        T, H, V = st.T, self.cfg.hidden_size, self.cfg.vocab_size
         hout = res if mlp is None else ops.add(res, mlp, out=st.buf("hout", (T, H)))
         if not self.is_last:
             return hout
-        S = st.last_rows.numel()
+        logits = self._lm_head(st, hout, stream, st.last_rows)
+        if st.extra is None:
+            return logits
+        # a ``logit_rows`` step: the other rows go through the head in a launch of their own, so the last
+        # rows' logits are the plain step's bit for bit (a decode GEMM's row bits can depend on its row count)
+        rows, last_pos, extra_pos, _ = st.extra
+        more = self._lm_head(st, hout, None, rows)
+        out = torch.empty(last_pos.numel() + extra_pos.numel(), V, dtype=logits.dtype, device=logits.device)
+        out[last_pos] = logits
+        out[extra_pos] = more
+        return out
+
+    def _lm_head(self, st: _Step, hout, stream, rows) -> torch.Tensor:
+        """Final norm and ``lm_head`` on ``rows`` of the residual stream ``hout``."""
+        cfg, w, T, eps = self.cfg, self.w, st.T, self.cfg.rms_norm_eps
+        H, V = cfg.hidden_size, cfg.vocab_size
+        S = rows.numel()
         if w.lm_head_p is not None and self._head_packed_ok(S):
             Vp = 16 * w.lm_head_p.shape[0]
             if w.lm_head_folded and stream is not None and S == T:
@@ -999,10 +1072,10 @@ class StageExecutor:
                                     ss_in=stream[1], eps=eps)
                 return logits[:, :V]
             fn = ops.rmsnorm(hout, self._unit_norm() if w.lm_head_folded else w.final_norm, eps,
-                             out=st.buf("fn_p", (ops.packed_numel(S, H),)), rows=st.last_rows, packed=True)
+                             out=st.buf("fn_p", (ops.packed_numel(S, H),)), rows=rows, packed=True)
             logits = ops.linear(fn, None, out=st.buf("logits", (S, Vp)), wp=w.lm_head_p, a_rows=S)
             return logits[:, :V]
-        fn = ops.rmsnorm(hout, w.final_norm, eps, out=st.buf("fn", (S, H)), rows=st.last_rows)
+        fn = ops.rmsnorm(hout, w.final_norm, eps, out=st.buf("fn", (S, H)), rows=rows)
         return ops.linear(fn, w.lm_head, out=st.buf("logits", (S, V)))
 
     def warmup(self, sizes: Optional[Sequence[int]] = None) -> None:
@@ -1392,7 +1465,8 @@ class StageExecutor:
             h = h + F.linear(m, L.fc2_w, L.fc2_b)
         if not self.is_last:
             return h
-        hl = h.index_select(0, last_rows.long())
+        extra = plan.extra_rows(self.device)
+        hl = h.index_select(0, last_rows.long() if extra is None else extra[3])
         hl = F.layer_norm(hl, (H,), w.final_norm, w.final_norm_b, cfg.layer_norm_eps)
         return F.linear(hl, w.lm_head)
 

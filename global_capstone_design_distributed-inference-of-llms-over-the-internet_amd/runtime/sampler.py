@@ -47,6 +47,8 @@ class BatchSampler:
         self._i = torch.empty(2 + RECENT, max_rows, dtype=torch.int32, pin_memory=pin)
         self._s = torch.empty(max_rows, dtype=torch.int64, pin_memory=pin)
         self._ws: Optional[torch.Tensor] = None
+        self._vws: Optional[torch.Tensor] = None  # workspace of ``verify``
+        self._vi: Optional[torch.Tensor] = None   # pinned int32 staging of ``verify``
 
     def __call__(self, logits: torch.Tensor, params: Sequence[SamplingParams], histories: Sequence[Sequence[int]],
                  seeds: Sequence[int]) -> torch.Tensor:
@@ -91,3 +93,66 @@ class BatchSampler:
         if dev.type == "cuda":
             torch.cuda.current_stream().synchronize()  # pinned staging is reused by the next call
         return out
+
+    def verify(self, logits: torch.Tensor, drafts: Sequence[Sequence[int]], params: Sequence[SamplingParams],
+               histories: Sequence[Sequence[int]], seeds: Sequence[Sequence[int]]) -> List[List[int]]:
+        """Speculative verify of one step (``ops.sample_verify``).  Session s owns the next
+        ``len(drafts[s]) + 1`` rows of ``logits``: the row of its last accepted token, then one per
+        drafted token; ``seeds[s]`` has one seed per row.  Returns, per session, the tokens it keeps:
+        the draws that equal their draft, and the first one that does not (or the bonus token after
+        the last draft).  A session without drafts gets what ``__call__`` gives it."""
+        S = len(drafts)
+        assert S == len(params) == len(histories) == len(seeds)
+        nrow = [len(d) + 1 for d in drafts]
+        R, V = logits.shape
+        assert R == sum(nrow) and all(len(sd) == n for sd, n in zip(seeds, nrow))
+        if S == 0:
+            return []
+        if S > self.max_rows or R > self.max_rows:
+            raise ValueError(f"verify step of {S} sessions / {R} rows exceeds the sampler's {self.max_rows} rows")
+        dev = logits.device
+        # staged like ``__call__``: pinned buffers, one copy each for the floats, the int32s and the seeds.
+        # int32 layout: row_start [S + 1] | draft [R] | top_k [S] | recent_len [S] | recent [S, RECENT]
+        if self._vi is None:
+            pin = self.device.type == "cuda"
+            n = self.max_rows
+            self._vi = torch.empty((n + 1) + n + 2 * n + n * RECENT, dtype=torch.int32, pin_memory=pin)
+        o_draft, o_k, o_len, o_rec = S + 1, S + 1 + R, 2 * S + 1 + R, 3 * S + 1 + R
+        n_int = o_rec + S * RECENT
+        ii = self._vi[:n_int].numpy()
+        ii[0] = 0
+        ii[1:S + 1] = np.cumsum(nrow)
+        row_start = ii[:S + 1]
+        ii[o_draft:o_k] = -1
+        for s, d in enumerate(drafts):
+            if len(d):
+                ii[o_draft + row_start[s]:o_draft + row_start[s] + len(d)] = d
+        ii[o_k:o_len] = [p.top_k for p in params]
+        rec = ii[o_rec:n_int].reshape(S, RECENT)
+        rec[:] = 0
+        for s, h in enumerate(histories):
+            h = list(h)[-RECENT:]
+            ii[o_len + s] = len(h)
+            if h:
+                rec[s, :len(h)] = h
+        f = self._f[:, :S].numpy()
+        f[0] = [p.temperature for p in params]
+        f[1] = [p.top_p for p in params]
+        f[2] = [p.repetition_penalty for p in params]
+        self._s[:R].numpy()[:] = [int(v) & 0x7FFFFFFFFFFFFFFF for row in seeds for v in row]
+        fd = self._f[:, :S].to(dev, non_blocking=True)
+        idv = self._vi[:n_int].to(dev, non_blocking=True)
+        seeds_d = self._s[:R].to(dev, non_blocking=True)
+        ws = None
+        if dev.type == "cuda":
+            need = ops.sample_verify_workspace(R, V, RECENT)
+            if self._vws is None or self._vws.numel() < need:
+                self._vws = torch.empty(need, dtype=torch.float32, device=dev)
+            ws = self._vws
+        toks, cnt = ops.sample_verify(
+            logits, idv[:o_draft], idv[o_draft:o_k], fd[0].contiguous(), fd[1].contiguous(), idv[o_k:o_len],
+            fd[2].contiguous(), idv[o_rec:].view(S, RECENT), idv[o_len:o_rec], seeds_d, workspace=ws,
+            all_greedy=all(p.temperature <= 0 for p in params))
+        row_start = [int(v) for v in row_start]  # (the pinned staging is reused by the next call)
+        toks, cnt = toks.tolist(), cnt.tolist()
+        return [toks[row_start[s]:row_start[s] + int(cnt[s])] for s in range(S)]
