@@ -342,12 +342,11 @@ def linear(x, w, out=None, epilogue=0, residual=None, ss_in=None, inv_k=0.0, eps
     return y
 
 
-def sample_row(logits_row: torch.Tensor, temperature: float, top_p: float, top_k: int,
-               repetition_penalty: float = 1.5, generated_tokens=None, generator=None) -> int:
-    """One-row sampler with the reference semantics (reference src/rpc_handler.py:327-403)."""
+def sample_probs(logits_row: torch.Tensor, temperature: float, top_p: float, top_k: int,
+                 repetition_penalty: float = 1.5, generated_tokens=None) -> torch.Tensor:
+    """The filtered, renormalised distribution [1, V] a sampled row (temperature > 0) draws from:
+    repetition penalty, softmax, top-k, top-p (reference src/rpc_handler.py:345-401)."""
     logits = logits_row.detach().float().clone().view(1, -1)
-    if temperature <= 0.0:
-        return int(torch.argmax(logits, dim=-1).item())
     temp = max(temperature, 1e-5)
     V = logits.shape[-1]
     if repetition_penalty != 1.0 and generated_tokens:
@@ -382,7 +381,15 @@ def sample_row(logits_row: torch.Tensor, temperature: float, top_p: float, top_k
         filt = sp * keep
         filt = filt / filt.sum(dim=-1, keepdim=True)
         probs = torch.zeros_like(probs).scatter(-1, si, filt)
-    probs = probs / probs.sum(dim=-1, keepdim=True)
+    return probs / probs.sum(dim=-1, keepdim=True)
+
+
+def sample_row(logits_row: torch.Tensor, temperature: float, top_p: float, top_k: int,
+               repetition_penalty: float = 1.5, generated_tokens=None, generator=None) -> int:
+    """One-row sampler with the reference semantics (reference src/rpc_handler.py:327-403)."""
+    if temperature <= 0.0:
+        return int(torch.argmax(logits_row.detach().float().view(1, -1), dim=-1).item())
+    probs = sample_probs(logits_row, temperature, top_p, top_k, repetition_penalty, generated_tokens)
     return int(torch.multinomial(probs, 1, generator=generator).item())
 
 
