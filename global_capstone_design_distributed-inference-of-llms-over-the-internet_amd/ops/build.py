@@ -27,6 +27,10 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # ablation builds: extra device-compile flags (e.g. "-DMP_RW_WAVES=8") go to their own object
 # directory and library name (``--out``), never over the default library
 EXTRA = os.environ.get("MPAMD_HIPCC_EXTRA", "").split()
+# kernarg preload: the leading kernel-argument dwords arrive in user SGPRs, so a wave forms its first
+# load addresses without a scalar load of the argument buffer (docs/KERNARG_PRELOAD.md: at most 14
+# dwords, and only the pointers and scalars ahead of the first by-value struct)
+PRELOAD = ["-mllvm", "-amdgpu-kernarg-preload-count=16"]
 
 
 def _torch_paths():
@@ -67,7 +71,7 @@ def build(force: bool = False, jobs: int = 0, verbose: bool = False, out: str = 
         raise SystemExit("MPAMD_HIPCC_EXTRA builds need --out (the default library stays the default build)")
     LIB_PATH = os.path.abspath(out) if out else globals()["LIB_PATH"]
     BUILD = globals()["BUILD"] + ("_" + hashlib.sha256(xtag.encode()).hexdigest()[:8] if xtag else "")
-    tag = _digest(hips + [binding] + headers, extra=ARCH + HIPCC + xtag)
+    tag = _digest(hips + [binding] + headers, extra=ARCH + HIPCC + " ".join(PRELOAD) + xtag)
     stamp = os.path.join(BUILD, "stamp")
     if not force and os.path.exists(LIB_PATH) and os.path.exists(stamp):
         with open(stamp) as f:
@@ -75,10 +79,10 @@ def build(force: bool = False, jobs: int = 0, verbose: bool = False, out: str = 
                 return LIB_PATH
     os.makedirs(BUILD, exist_ok=True)
     inc, libdir = _torch_paths()
-    common = ["-O3", "-fPIC", "-std=c++17", f"--offload-arch={ARCH}", "-I" + CSRC] + EXTRA
+    common = ["-O3", "-fPIC", "-std=c++17", f"--offload-arch={ARCH}", "-I" + CSRC] + PRELOAD + EXTRA
     objs = []
     cmds = []
-    hdr_tag = _digest(headers, extra=ARCH + HIPCC + xtag)
+    hdr_tag = _digest(headers, extra=ARCH + HIPCC + " ".join(PRELOAD) + xtag)
 
     def stale(src, obj):
         # per-object stamp: the source + every csrc header (a kernel edit rebuilds one object)

@@ -172,11 +172,14 @@ __device__ __forceinline__ void split_combine(int* cnt_slot, int NP, const float
 // values - what every later step will read.
 template <int D, int NREP, bool ROPE, int NW, bool PIPE, int U = 4, bool F8 = false>
 __global__ __launch_bounds__(NW * 64, MP_ATTN_MINW) void paged_attn1_kernel(
-    const bf16_t* __restrict__ q, int64_t q_stride, const bf16_t* __restrict__ kc,
-    const bf16_t* __restrict__ vc, const int32_t* __restrict__ block_tables, int bt_stride,
-    const int32_t* __restrict__ q_seq, const int32_t* __restrict__ q_ctx, bf16_t* __restrict__ out,
-    float* __restrict__ part_o, float* __restrict__ part_ml, int nkv, int nh, int page_log2, int PS, int NP,
-    float scale_log2, int packed_mt, RopeFuse rf, int* __restrict__ cnt, KvF8 f8, int window) {
+    const bf16_t* __restrict__ kc, const bf16_t* __restrict__ vc, const int32_t* __restrict__ block_tables,
+    const int32_t* __restrict__ q_seq, const int32_t* __restrict__ q_ctx, int bt_stride, int window,
+    unsigned pk_heads, unsigned pk_geom, const bf16_t* __restrict__ q, int64_t q_stride, bf16_t* __restrict__ out,
+    float* __restrict__ part_o, float* __restrict__ part_ml, float scale_log2, int packed_mt, RopeFuse rf,
+    int* __restrict__ cnt, KvF8 f8) {
+  // the 14 leading dwords (up to pk_geom) are everything a wave's first K / V load needs (attn_common.h)
+  const int nkv = attn_pk_nkv(pk_heads), nh = attn_pk_nh(pk_heads);
+  const int PS = attn_pk_ps(pk_geom), page_log2 = attn_pk_page_log2(pk_geom), NP = attn_pk_np(pk_geom);
   using kvreg_t = std::conditional_t<F8, KvF8Reg, u16x8>;
   constexpr int LPT = D / 8;
   constexpr int TPI = 64 / LPT;
@@ -519,14 +522,18 @@ __global__ void paged_attn_reduce_kernel(const float* __restrict__ part_o, const
 }
 
 template <int D, int NREP, int NW, bool F8>
-static void launch_attn_nw(const AttnArgs& a, int page_log2, const RopeFuse& rf, int* cnt, KvF8 f8,
+static void launch_attn_nw(const AttnArgs& a, const AttnPacked& pk, const RopeFuse& rf, int* cnt, KvF8 f8,
                            hipStream_t stream) {
   const size_t lds = (size_t)(NW * NREP * D + 2 * NW * NREP + 4) * sizeof(float);
+  // paged_attn1_kernel's argument list, each value next to its parameter's name
   auto go = [&](auto kern) {
-    hipLaunchKernelGGL(kern, dim3(a.NP, a.nh / NREP, a.T), dim3(64 * NW), lds, stream, (const bf16_t*)a.q, a.q_stride,
-                       (const bf16_t*)a.kc, (const bf16_t*)a.vc, a.bt, a.bt_stride, a.q_seq, a.q_ctx, (bf16_t*)a.out,
-                       a.workspace, attn_ws_ml(a), a.nkv, a.nh, page_log2, a.PS, a.NP, attn_scale_log2(a), a.packed_mt,
-                       rf, cnt, f8, a.window);
+    hipLaunchKernelGGL(kern, dim3(a.NP, a.nh / NREP, a.T), dim3(64 * NW), lds, stream,
+                       /* kc */ (const bf16_t*)a.kc, /* vc */ (const bf16_t*)a.vc, /* block_tables */ a.bt,
+                       /* q_seq */ a.q_seq, /* q_ctx */ a.q_ctx, /* bt_stride */ a.bt_stride, /* window */ a.window,
+                       /* pk_heads */ pk.heads, /* pk_geom */ pk.geom, /* q */ (const bf16_t*)a.q,
+                       /* q_stride */ a.q_stride, /* out */ (bf16_t*)a.out, /* part_o */ a.workspace,
+                       /* part_ml */ attn_ws_ml(a), /* scale_log2 */ attn_scale_log2(a), /* packed_mt */ a.packed_mt,
+                       /* rf */ rf, /* cnt */ cnt, /* f8 */ f8);
   };
   if (rf.pos) go(paged_attn1_kernel<D, NREP, true, NW, true, 4, F8>);
   else go(paged_attn1_kernel<D, NREP, false, NW, true, 4, F8>);
@@ -538,11 +545,12 @@ static void launch_attn_nw(const AttnArgs& a, int page_log2, const RopeFuse& rf,
 // grid 4-wave ones.  (2-wave workgroups, the 64-session step's 2048 in one round of residency,
 // measured 36.5 -> 38.1 us cold at 64 x 170: profiles/r6attn.)
 template <int D, int NREP, bool F8>
-static void launch_attn(const AttnArgs& a, int page_log2, const RopeFuse& rf, int* cnt, KvF8 f8, hipStream_t stream) {
+static void launch_attn(const AttnArgs& a, const AttnPacked& pk, const RopeFuse& rf, int* cnt, KvF8 f8,
+                        hipStream_t stream) {
   const int64_t wgs = (int64_t)a.NP * (a.nh / NREP) * a.T;
   const int nw = MP_ATTN_NW ? MP_ATTN_NW : (wgs <= 128 ? 8 : 4);
-  if (nw == 8) launch_attn_nw<D, NREP, 8, F8>(a, page_log2, rf, cnt, f8, stream);
-  else if (nw == 4) launch_attn_nw<D, NREP, 4, F8>(a, page_log2, rf, cnt, f8, stream);
+  if (nw == 8) launch_attn_nw<D, NREP, 8, F8>(a, pk, rf, cnt, f8, stream);
+  else if (nw == 4) launch_attn_nw<D, NREP, 4, F8>(a, pk, rf, cnt, f8, stream);
 }
 
 }  // namespace mp
@@ -563,6 +571,8 @@ extern "C" int mp_paged_attention(const mp::AttnArgs* args, int* counters, int n
   if (a.nh % a.nkv != 0 || a.PS % 64 != 0 || a.PS > 2048 || a.NP < 1 || a.window < 0) return -1;
   const int page_log2 = attn_page_log2(a);
   if (page_log2 < 0) return -2;
+  AttnPacked pk;
+  if (!attn_pack(a.nkv, a.nh, a.PS, page_log2, a.NP, pk)) return -5;  // a value does not fit its packed field
   const int nrep = a.nh / a.nkv;
   // heads per workgroup: at most 4 of a GQA group (register budget), a divisor of nrep
   constexpr int hpb_max = 4;
@@ -572,8 +582,8 @@ extern "C" int mp_paged_attention(const mp::AttnArgs* args, int* counters, int n
   int* cnt = (a.NP > 1 && counters != nullptr && (int64_t)a.T * (a.nh / hpb) <= n_counters) ? counters : nullptr;
 #define MP_ATTN_CASE(DD, RR)                                                                  \
   if (a.D == DD && hpb == RR) {                                                               \
-    if (f8.ks != nullptr) launch_attn<DD, RR, true>(a, page_log2, rf, cnt, f8, stream);       \
-    else launch_attn<DD, RR, false>(a, page_log2, rf, cnt, f8, stream);                       \
+    if (f8.ks != nullptr) launch_attn<DD, RR, true>(a, pk, rf, cnt, f8, stream);              \
+    else launch_attn<DD, RR, false>(a, pk, rf, cnt, f8, stream);                              \
     goto launched;                                                                            \
   }
   MP_ATTN_CASE(128, 1)

@@ -79,11 +79,15 @@ constexpr int VT_PITCH = 36;  // bf16 per LDS row of the transposed V tile (32 t
 // codes and the two scale bytes.
 template <int D, int HB, bool ROPE, bool FOLD = false, bool F8 = false>
 __global__ __launch_bounds__(256, 2) void attn_mfma_kernel(
-    const bf16_t* __restrict__ q, int64_t q_stride, const bf16_t* __restrict__ kc, const bf16_t* __restrict__ vc,
-    const int32_t* __restrict__ block_tables, int bt_stride, const int32_t* __restrict__ q_seq,
-    const int32_t* __restrict__ q_ctx, const int32_t* __restrict__ qb_tok0, const int32_t* __restrict__ qb_ntok,
-    bf16_t* __restrict__ out, float* __restrict__ part_o, float* __restrict__ part_ml, int nkv, int nh,
-    int page_log2, int PS, int NP, float scale_log2, int packed_mt, RopeFuseM rf, int window) {
+    const bf16_t* __restrict__ kc, const bf16_t* __restrict__ vc, const int32_t* __restrict__ block_tables,
+    const int32_t* __restrict__ q_seq, const int32_t* __restrict__ q_ctx, int bt_stride, int window,
+    unsigned pk_heads, unsigned pk_geom, const int32_t* __restrict__ qb_tok0, const int32_t* __restrict__ qb_ntok,
+    const bf16_t* __restrict__ q, int64_t q_stride, bf16_t* __restrict__ out, float* __restrict__ part_o,
+    float* __restrict__ part_ml, float scale_log2, int packed_mt, RopeFuseM rf) {
+  // the 14 leading dwords (up to pk_geom) are what a decode block's first page-id and K / V loads
+  // need (attn_common.h); query blocks of several tokens also read qb_tok0 / qb_ntok
+  const int nkv = attn_pk_nkv(pk_heads), nh = attn_pk_nh(pk_heads);
+  const int PS = attn_pk_ps(pk_geom), page_log2 = attn_pk_page_log2(pk_geom), NP = attn_pk_np(pk_geom);
   constexpr int TB = 16 / HB;
   constexpr int KD = D / 32;  // k-chunks of the QK^T product
   constexpr int DT = D / 16;  // 16-column tiles of O
@@ -691,7 +695,8 @@ __global__ __launch_bounds__(NWG * 64) void attn_mfma_grp_kernel(
 // F8: the fp8 cache form - decode blocks only (one token per block), so no superblocks (the grouped
 // kernel has no fp8 form; mp_attention_mfma refuses them); HB 4 / 8 / 16.
 template <int D, int HB, bool F8>
-static void launch_attn_mfma(const AttnArgs& a, int page_log2, const RopeFuseM& rf, const int32_t* qb_tok0,
+static void launch_attn_mfma(const AttnArgs& a, int page_log2, const AttnPacked& pk, const RopeFuseM& rf,
+                             const int32_t* qb_tok0,
                              const int32_t* qb_ntok, int NB, const int32_t* sb_first, const int32_t* sb_n, int NSB,
                              hipStream_t stream) {
   const bf16_t *q = (const bf16_t*)a.q, *kc = (const bf16_t*)a.kc, *vc = (const bf16_t*)a.vc;
@@ -704,10 +709,14 @@ static void launch_attn_mfma(const AttnArgs& a, int page_log2, const RopeFuseM& 
                        a.packed_mt);
     return;
   }
+  // attn_mfma_kernel's argument list, each value next to its parameter's name
   auto go = [&](auto kern) {
-    hipLaunchKernelGGL(kern, dim3(NB, a.nh / HB, a.NP), dim3(256), 0, stream, q, a.q_stride, kc, vc, a.bt,
-                       a.bt_stride, a.q_seq, a.q_ctx, qb_tok0, qb_ntok, (bf16_t*)a.out, a.workspace, ws_ml, a.nkv,
-                       a.nh, page_log2, a.PS, a.NP, scale_log2, a.packed_mt, rf, a.window);
+    hipLaunchKernelGGL(kern, dim3(NB, a.nh / HB, a.NP), dim3(256), 0, stream,
+                       /* kc */ kc, /* vc */ vc, /* block_tables */ a.bt, /* q_seq */ a.q_seq, /* q_ctx */ a.q_ctx,
+                       /* bt_stride */ a.bt_stride, /* window */ a.window, /* pk_heads */ pk.heads,
+                       /* pk_geom */ pk.geom, /* qb_tok0 */ qb_tok0, /* qb_ntok */ qb_ntok, /* q */ q,
+                       /* q_stride */ a.q_stride, /* out */ (bf16_t*)a.out, /* part_o */ a.workspace,
+                       /* part_ml */ ws_ml, /* scale_log2 */ scale_log2, /* packed_mt */ a.packed_mt, /* rf */ rf);
   };
   if (rf.pos && rf.qp.part) go(attn_mfma_kernel<D, HB, true, true, F8>);
   else if (rf.pos) go(attn_mfma_kernel<D, HB, true, false, F8>);
@@ -750,6 +759,8 @@ extern "C" int mp_attention_mfma(const mp::AttnArgs* args, const int32_t* qb_tok
   if (a.nh % a.nkv != 0 || a.PS % 128 != 0 || a.NP < 1 || a.page_size % 32 != 0) return -1;
   const int page_log2 = attn_page_log2(a);
   if (page_log2 < 0) return -2;
+  AttnPacked pk;
+  if (!attn_pack(a.nkv, a.nh, a.PS, page_log2, a.NP, pk)) return -5;  // a value does not fit its packed field
   const int nrep = a.nh / a.nkv;
   // the whole GQA group of a kv head in one workgroup's MFMA rows (spreading a group's heads over
   // several workgroups that re-read the same K / V measured 1.6-2.7x slower, profiles/r4k)
@@ -758,7 +769,7 @@ extern "C" int mp_attention_mfma(const mp::AttnArgs* args, const int32_t* qb_tok
   if (f8 && hb != 4 && hb != 8 && hb != 16) return -10;
 #define MP_AM_CASE(DD, HH, F8)                                                                              \
   if (a.D == DD && hb == HH && f8 == F8) {                                                                  \
-    launch_attn_mfma<DD, HH, F8>(a, page_log2, rf, qb_tok0, qb_ntok, NB, sb_first, sb_n, NSB, stream);      \
+    launch_attn_mfma<DD, HH, F8>(a, page_log2, pk, rf, qb_tok0, qb_ntok, NB, sb_first, sb_n, NSB, stream);  \
     goto launched;                                                                                          \
   }
   MP_AM_CASE(128, 1, false)  // (heads per block 1 and 2 have no fp8 form: -10 above)

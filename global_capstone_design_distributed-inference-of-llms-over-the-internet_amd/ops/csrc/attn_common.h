@@ -43,6 +43,44 @@ __device__ __forceinline__ u16x8 rope8(u16x8 me, u16x8 ot, f32x4 ca, f32x4 cb, f
   return r;
 }
 
+// The decode kernels' small geometry arguments, packed into two kernel-argument dwords so that they
+// fit, with the cache / block-table / context pointers, into the 14 leading dwords that kernarg
+// preload delivers in SGPRs (docs/KERNARG_PRELOAD.md): every one of them is on the address chain of
+// a wave's first K / V load.
+//   heads: nkv | nh << 16          geom: PS / 64 | page_log2 << 12 | NP << 17
+// (PS, the context-slice length, is a multiple of 64 in every decode launcher)
+constexpr int ATTN_PK_NKV_BITS = 16, ATTN_PK_NH_BITS = 16;
+constexpr int ATTN_PK_PS_BITS = 12, ATTN_PK_PLOG_BITS = 5, ATTN_PK_NP_BITS = 15;
+static_assert(ATTN_PK_NKV_BITS + ATTN_PK_NH_BITS == 32, "heads dword");
+static_assert(ATTN_PK_PS_BITS + ATTN_PK_PLOG_BITS + ATTN_PK_NP_BITS == 32, "geom dword");
+static_assert(2048 / 64 < (1 << ATTN_PK_PS_BITS), "PS <= 2048 (mp_paged_attention) fits its field");
+static_assert(31 < (1 << ATTN_PK_PLOG_BITS), "any int page size's log2 fits its field");
+struct AttnPacked {
+  unsigned heads, geom;
+};
+// false when a value does not fit its field (the launcher then returns an error: never truncated)
+inline bool attn_pack(int nkv, int nh, int PS, int page_log2, int NP, AttnPacked& pk) {
+  auto fits = [](int v, int bits) { return v >= 0 && v < (1 << bits); };
+  if (!fits(nkv, ATTN_PK_NKV_BITS) || !fits(nh, ATTN_PK_NH_BITS) || PS % 64 ||
+      !fits(PS / 64, ATTN_PK_PS_BITS) || !fits(page_log2, ATTN_PK_PLOG_BITS) || !fits(NP, ATTN_PK_NP_BITS))
+    return false;
+  pk.heads = (unsigned)nkv | (unsigned)nh << ATTN_PK_NKV_BITS;
+  pk.geom = (unsigned)(PS / 64) | (unsigned)page_log2 << ATTN_PK_PS_BITS |
+            (unsigned)NP << (ATTN_PK_PS_BITS + ATTN_PK_PLOG_BITS);
+  return true;
+}
+__device__ __forceinline__ int attn_pk_nkv(unsigned heads) { return (int)(heads & ((1u << ATTN_PK_NKV_BITS) - 1)); }
+__device__ __forceinline__ int attn_pk_nh(unsigned heads) { return (int)(heads >> ATTN_PK_NKV_BITS); }
+__device__ __forceinline__ int attn_pk_ps(unsigned geom) {
+  return (int)(geom & ((1u << ATTN_PK_PS_BITS) - 1)) * 64;
+}
+__device__ __forceinline__ int attn_pk_page_log2(unsigned geom) {
+  return (int)(geom >> ATTN_PK_PS_BITS & ((1u << ATTN_PK_PLOG_BITS) - 1));
+}
+__device__ __forceinline__ int attn_pk_np(unsigned geom) {
+  return (int)(geom >> (ATTN_PK_PS_BITS + ATTN_PK_PLOG_BITS));
+}
+
 // Combine split-K partials (defined in attention.hip; launched by all three attention launchers when NP > 1)
 __global__ void paged_attn_reduce_kernel(const float* __restrict__ part_o, const float* __restrict__ part_ml,
                                          bf16_t* __restrict__ out, int NP, int D, int nh, int packed_mt);

@@ -170,11 +170,20 @@ __device__ __forceinline__ f32x4 mfma_mx(const u32x8& a, const u32x8& b, unsigne
 
 __device__ __forceinline__ u64 fx_sq(float f) { return (u64)__float2ull_rn(f * f * SS_FX); }
 
-__device__ __forceinline__ void clear_other(const EpiArgs& ep) {
-  if (ep.ss_zero != nullptr && blockIdx.x == 0) {
-    for (int i = threadIdx.x; i < SS_NSH * SS_ROWS; i += blockDim.x) ep.ss_zero[i] = 0ull;
+// KERNARG ORDER.  The library is built with kernarg preload (ops/build.py, docs/KERNARG_PRELOAD.md):
+// the first 14 argument dwords of a kernel arrive in SGPRs, up to the first by-value struct.  So every
+// decode GEMM kernel below lists first, as plain pointers and scalars, what a wave needs to form its
+// first weight / activation load addresses - x, wp, the shape, the ring's row-tile count and k
+// rotation - and ``ss_zero``, which clear_other tests ahead of those loads; outputs, strides, the
+// residual and the EpiArgs struct follow.  mt_out / rot / ss_zero are copies of the EpiArgs fields
+// (the epilogues keep reading the struct).  Each kernel family has ONE launch helper (*_launch) that
+// writes the argument list with every value next to its parameter's name.
+__device__ __forceinline__ void clear_other(u64* ss_zero) {
+  if (ss_zero != nullptr && blockIdx.x == 0) {
+    for (int i = threadIdx.x; i < SS_NSH * SS_ROWS; i += blockDim.x) ss_zero[i] = 0ull;
   }
 }
+__device__ __forceinline__ void clear_other(const EpiArgs& ep) { clear_other(ep.ss_zero); }
 
 // Consumer side (EPI 0 / 1 only; compiled out of the producer epilogues), in two halves around
 // the main loop: thread t owns row t % R and shard group t / R (R: the step's row window, G =
@@ -281,12 +290,13 @@ __device__ __forceinline__ int rw_krot(int n, int on) {
 constexpr int GU_MAX = 4;  // k-slices (of 32) per wave group (x 16 B per lane per column tile)
 
 template <int MT, int NT, int EPI, bool APK, bool OPK>
-__global__ __launch_bounds__(512) void gemm_packed_kernel(const bf16_t* __restrict__ x, int64_t x_stride,
-                                                          const bf16_t* __restrict__ wp, bf16_t* __restrict__ y,
-                                                          int64_t y_stride, const bf16_t* __restrict__ res,
-                                                          int64_t res_stride, int M, int N, int K,
-                                                          const int* __restrict__ gate, const EpiArgs ep) {
-  clear_other(ep);
+__global__ __launch_bounds__(512) void gemm_packed_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ wp,
+                                                          const int* __restrict__ gate, u64* __restrict__ ss_zero,
+                                                          int64_t x_stride, int M, int N, int K, int rot,
+                                                          bf16_t* __restrict__ y, int64_t y_stride,
+                                                          const bf16_t* __restrict__ res, int64_t res_stride,
+                                                          const EpiArgs ep) {
+  clear_other(ss_zero);
   __shared__ u64 rs_part[SS_PG][SS_ROWS];
   __shared__ float rs_lds[SS_ROWS];
   RowScale<EPI < 2> rsc;
@@ -344,7 +354,7 @@ __global__ __launch_bounds__(512) void gemm_packed_kernel(const bf16_t* __restri
   // A fragments of group g issued BEFORE the prefetch of group g+8: vmcnt retires loads in
   // issue order, so waiting for A leaves the weight prefetch in flight across the MFMAs.
   u16x8 b0[NT][GU], b1[NT][GU], a[MT][GU];
-  const int grot = rw_krot(ngroups, ep.rot);
+  const int grot = rw_krot(ngroups, rot);
 #define MP_LOAD_B(dst, grp)                                                                                   \
   _Pragma("unroll") for (int t = 0; t < NT; ++t) _Pragma("unroll") for (int u = 0; u < GU; ++u) dst[t][u] =    \
       __builtin_nontemporal_load(reinterpret_cast<const u16x8*>(wbase[t] + (int64_t)(rw_rot(grp, grot, ngroups) * GU + u) * 512));
@@ -431,16 +441,24 @@ __global__ __launch_bounds__(512) void gemm_packed_kernel(const bf16_t* __restri
   }
 }
 
+// gemm_packed_kernel's argument list, each value next to its parameter's name (KERNARG ORDER above)
+template <class Kern>
+static inline void packed_launch(Kern kern, int G, hipStream_t stream, const GemmArgs& a, const EpiArgs& ep) {
+  hipLaunchKernelGGL(kern, dim3(G), dim3(512), 0, stream,
+                     /* x */ (const bf16_t*)a.x, /* wp */ (const bf16_t*)a.w, /* gate */ a.gate,
+                     /* ss_zero */ ep.ss_zero, /* x_stride */ a.x_stride, /* M */ a.M, /* N */ a.N, /* K */ a.K,
+                     /* rot */ ep.rot, /* y */ (bf16_t*)a.y, /* y_stride */ a.y_stride,
+                     /* res */ (const bf16_t*)a.res, /* res_stride */ a.res_stride, /* ep */ ep);
+}
+
 template <int MT>
 static int launch_gemm(const GemmArgs& a, const EpiArgs& ep, hipStream_t stream) {
   const int ntiles = a.N / 16, epi = a.epilogue;
   // two column tiles per wave when there are enough workgroups to fill the 256 CUs
   const bool two = epi == 1 || (ntiles % 2 == 0 && ntiles / 2 >= 256);
   const bool apk = a.flags & GEMM_A_PACKED, opk = a.flags & GEMM_OUT_PACKED;
-#define MP_LAUNCH(NT_, EPI_, APK_, OPK_)                                                                       \
-  hipLaunchKernelGGL((gemm_packed_kernel<MT, NT_, EPI_, APK_, OPK_>), dim3(ntiles / NT_), dim3(512), 0, stream, \
-                     (const bf16_t*)a.x, a.x_stride, (const bf16_t*)a.w, (bf16_t*)a.y, a.y_stride,              \
-                     (const bf16_t*)a.res, a.res_stride, a.M, a.N, a.K, a.gate, ep)
+#define MP_LAUNCH(NT_, EPI_, APK_, OPK_) \
+  packed_launch(gemm_packed_kernel<MT, NT_, EPI_, APK_, OPK_>, ntiles / NT_, stream, a, ep)
   // Only the packed-activation form is instantiated: row-major callers pack x first
   // (mp_pack_act).  The row-major-A variant miscompiled at MT=1/NT=1 (ROCm 7.2, wrong
   // results with several k-groups per wave) and loses to the packed form anyway.
@@ -550,10 +568,11 @@ __device__ __forceinline__ void sk_epilogue(int qd, int g, const f32x4& v, const
 // every wave runs the same barrier sequence.
 template <int MT, int NT, int CH, int EPI, bool OPK>
 __global__ __launch_bounds__(512) void gemm_lds_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ wp,
+                                                       u64* __restrict__ ss_zero, int M, int N, int K, int rot,
                                                        bf16_t* __restrict__ y, int64_t ys,
-                                                       const bf16_t* __restrict__ res, int64_t rs, int M, int N,
-                                                       int K, const EpiArgs ep) {
-  clear_other(ep);
+                                                       const bf16_t* __restrict__ res, int64_t rs,
+                                                       const EpiArgs ep) {
+  clear_other(ss_zero);
   __shared__ u64 rs_part[SS_PG][SS_ROWS];
   __shared__ float rs_lds[SS_ROWS];
   RowScale<EPI < 2> rsc;
@@ -596,7 +615,7 @@ __global__ __launch_bounds__(512) void gemm_lds_kernel(const bf16_t* __restrict_
     for (int t = 0; t < NT; ++t) acc[mt][t] = (f32x4)(0.f);
 
   u16x8 st[FH], b0[NT][GU], b1[NT][GU], a[MT][GU];
-  const int grot = rw_krot(ngroups, ep.rot);
+  const int grot = rw_krot(ngroups, rot);
 #define MP_GRP(it) rw_rot(min((it) * KS + ksp, ngroups - 1), grot, ngroups)
 #define MP_LDA(it)                                                                                            \
   _Pragma("unroll") for (int f = 0; f < FH; ++f) st[f] =                                                     \
@@ -667,6 +686,15 @@ __global__ __launch_bounds__(512) void gemm_lds_kernel(const bf16_t* __restrict_
   }
 }
 
+// gemm_lds_kernel's argument list, each value next to its parameter's name (KERNARG ORDER above)
+template <class Kern>
+static inline void lds_launch(Kern kern, dim3 grid, hipStream_t stream, const GemmArgs& a, const EpiArgs& ep) {
+  hipLaunchKernelGGL(kern, grid, dim3(512), 0, stream,
+                     /* x */ (const bf16_t*)a.x, /* wp */ (const bf16_t*)a.w, /* ss_zero */ ep.ss_zero,
+                     /* M */ a.M, /* N */ a.N, /* K */ a.K, /* rot */ ep.rot, /* y */ (bf16_t*)a.y,
+                     /* ys */ a.y_stride, /* res */ (const bf16_t*)a.res, /* rs */ a.res_stride, /* ep */ ep);
+}
+
 template <int MT, int NT, int CH>
 static int launch_gemm_lds_cfg(const GemmArgs& a, const EpiArgs& ep, hipStream_t stream) {
   if constexpr ((2 * MT) % CH != 0) {
@@ -676,10 +704,7 @@ static int launch_gemm_lds_cfg(const GemmArgs& a, const EpiArgs& ep, hipStream_t
     const bool opk = a.flags & GEMM_OUT_PACKED;
     if (ntiles % (CH * NT) || a.K % 64) return 1;
     const dim3 grid(ntiles / (CH * NT));
-#define MP_LL(EPI_, OPK_)                                                                                      \
-  hipLaunchKernelGGL((gemm_lds_kernel<MT, NT, CH, EPI_, OPK_>), grid, dim3(512), 0, stream, (const bf16_t*)a.x, \
-                     (const bf16_t*)a.w, (bf16_t*)a.y, a.y_stride, (const bf16_t*)a.res, a.res_stride, a.M, a.N, \
-                     a.K, ep)
+#define MP_LL(EPI_, OPK_) lds_launch(gemm_lds_kernel<MT, NT, CH, EPI_, OPK_>, grid, stream, a, ep)
     return with_epilogue(epi, opk, [&](auto e, auto o) {
       if constexpr (e() == 1 && NT % 2 != 0) {
         return 1;  // gate/up tile pairs must sit in one wave
@@ -705,10 +730,11 @@ static int launch_gemm_lds(const GemmArgs& a, const EpiArgs& ep, hipStream_t str
 
 template <int MT, int NT, int D, int EPI, bool OPK>
 __global__ __launch_bounds__(512) void gemm_sk_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ wp,
-                                                      bf16_t* __restrict__ y, int64_t ys, const bf16_t* __restrict__ res,
-                                                      int64_t rs, int M, int N, int K, int* __restrict__ cnt,
-                                                      f32x4* __restrict__ slab, int remap, const EpiArgs ep) {
-  clear_other(ep);
+                                                      int* __restrict__ cnt, u64* __restrict__ ss_zero, int M,
+                                                      int N, int K, int remap, bf16_t* __restrict__ y, int64_t ys,
+                                                      const bf16_t* __restrict__ res, int64_t rs,
+                                                      f32x4* __restrict__ slab, const EpiArgs ep) {
+  clear_other(ss_zero);
   __shared__ u64 rs_part[SS_PG][SS_ROWS];
   __shared__ float rs_lds[SS_ROWS];
   RowScale<EPI < 2> rsc;
@@ -927,6 +953,17 @@ static int sk_num_cus() {
   return n[dev];
 }
 
+// gemm_sk_kernel's argument list, each value next to its parameter's name (KERNARG ORDER above);
+// ``cnt`` leads too: the ring's zero A fragment sits behind the counters
+template <class Kern>
+static inline void sk_launch(Kern kern, int G, hipStream_t stream, const GemmArgs& a, const EpiArgs& ep, int* cnt,
+                             f32x4* slab) {
+  hipLaunchKernelGGL(kern, dim3(G), dim3(512), 0, stream,
+                     /* x */ (const bf16_t*)a.x, /* wp */ (const bf16_t*)a.w, /* cnt */ cnt, /* ss_zero */ ep.ss_zero,
+                     /* M */ a.M, /* N */ a.N, /* K */ a.K, /* remap */ 1, /* y */ (bf16_t*)a.y, /* ys */ a.y_stride,
+                     /* res */ (const bf16_t*)a.res, /* rs */ a.res_stride, /* slab */ slab, /* ep */ ep);
+}
+
 template <int MT, int NT, int D>
 static int launch_gemm_sk_cfg(const GemmArgs& a, const EpiArgs& ep, hipStream_t stream, int G) {
   const int nks = a.K / 32, epi = a.epilogue;
@@ -940,10 +977,7 @@ static int launch_gemm_sk_cfg(const GemmArgs& a, const EpiArgs& ep, hipStream_t 
   int* cnt = (int*)a.ws;  // [SK_MAX_GROUPS] counters, [SK_ZERO_BYTES] zeros, slabs
   f32x4* slab = (f32x4*)((char*)a.ws + SK_MAX_GROUPS * sizeof(int) + SK_ZERO_BYTES);
   const bool opk = a.flags & GEMM_OUT_PACKED;
-#define MP_SK(EPI_, OPK_)                                                                                         \
-  hipLaunchKernelGGL((gemm_sk_kernel<MT, NT, D, EPI_, OPK_>), dim3(G), dim3(512), 0, stream, (const bf16_t*)a.x,   \
-                     (const bf16_t*)a.w, (bf16_t*)a.y, a.y_stride, (const bf16_t*)a.res, a.res_stride, a.M, a.N,   \
-                     a.K, cnt, slab, 1, ep)
+#define MP_SK(EPI_, OPK_) sk_launch(gemm_sk_kernel<MT, NT, D, EPI_, OPK_>, G, stream, a, ep, cnt, slab)
   return with_epilogue(epi, opk, [&](auto e, auto o) {
     if constexpr (e() == 1 && NT % 2 != 0) {
       return 1;
@@ -1040,8 +1074,8 @@ constexpr int mx_depth() {
 template <int MT, int NT, int EPI, bool OPK, bool F8 = false, bool NTW = true>
 __device__ __forceinline__ void rw_body(const bf16_t* __restrict__ x, const bf16_t* __restrict__ wp,
                                         bf16_t* __restrict__ y, int64_t ys, const bf16_t* __restrict__ res, int64_t rs,
-                                        int M, int K, int tile0, const EpiArgs& ep, f32x4* red, u64 (*rs_part)[SS_ROWS],
-                                        float* rs_lds, int mt0 = 0, int mta = MT) {
+                                        int M, int K, int tile0, int rot, const EpiArgs& ep, f32x4* red,
+                                        u64 (*rs_part)[SS_ROWS], float* rs_lds, int mt0 = 0, int mta = MT) {
   constexpr int R = rw_depth2<MT, NT, F8>();
   constexpr int Q = MT * NT;
   constexpr int NQ = (Q + RW_WAVES - 1) / RW_WAVES;  // epilogue quads per wave
@@ -1049,7 +1083,7 @@ __device__ __forceinline__ void rw_body(const bf16_t* __restrict__ x, const bf16
   const int lane = threadIdx.x & 63, wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int nks = K >> 5;
   const int cnt = (nks + RW_WAVES - 1) / RW_WAVES;  // ring steps of the busiest wave
-  const int krot = rw_krot(nks, ep.rot);
+  const int krot = rw_krot(nks, rot);
   // F8: the same fragment order at 1 byte per weight (offsets below count elements)
   using WT = std::conditional_t<F8, uint8_t, bf16_t>;
   using BT = std::conditional_t<F8, u32x2, u16x8>;
@@ -1155,20 +1189,32 @@ __device__ __forceinline__ void rw_body(const bf16_t* __restrict__ x, const bf16
 
 template <int MT, int NTB, int NTS, int EPI, bool OPK, bool F8 = false>
 __global__ __launch_bounds__(RW_WAVES * 64) void gemm_rw_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ wp,
-                                                      bf16_t* __restrict__ y, int64_t ys,
-                                                      const bf16_t* __restrict__ res, int64_t rs, int M, int K,
-                                                      int n_big, const EpiArgs ep) {
-  clear_other(ep);
+                                                      u64* __restrict__ ss_zero, int M, int K, int n_big,
+                                                      int mt_out, int rot, bf16_t* __restrict__ y, int64_t ys,
+                                                      const bf16_t* __restrict__ res, int64_t rs,
+                                                      const EpiArgs ep) {
+  clear_other(ss_zero);
   __shared__ u64 rs_part[SS_PG][SS_ROWS];
   __shared__ float rs_lds[SS_ROWS];
   __shared__ __attribute__((aligned(16))) f32x4 red[RW_WAVES * (MT * NTB < RW_QC ? MT * NTB : RW_QC) * 64];
   const int b = blockIdx.x;
   if (b < n_big) {
-    rw_body<MT, NTB, EPI, OPK, F8>(x, wp, y, ys, res, rs, M, K, b * NTB, ep, red, rs_part, rs_lds, 0, ep.mt_out);
+    rw_body<MT, NTB, EPI, OPK, F8>(x, wp, y, ys, res, rs, M, K, b * NTB, rot, ep, red, rs_part, rs_lds, 0, mt_out);
   } else {
-    rw_body<MT, NTS, EPI, OPK, F8>(x, wp, y, ys, res, rs, M, K, n_big * NTB + (b - n_big) * NTS, ep, red, rs_part,
-                                   rs_lds, 0, ep.mt_out);
+    rw_body<MT, NTS, EPI, OPK, F8>(x, wp, y, ys, res, rs, M, K, n_big * NTB + (b - n_big) * NTS, rot, ep, red,
+                                   rs_part, rs_lds, 0, mt_out);
   }
+}
+
+// The one place that writes gemm_rw_kernel's argument list (see KERNARG ORDER above): each value
+// next to the name of the parameter it lands in.
+template <class Kern>
+static inline void rw_launch(Kern kern, int G, hipStream_t stream, const GemmArgs& a, const EpiArgs& ep, int n_big) {
+  hipLaunchKernelGGL(kern, dim3(G), dim3(RW_WAVES * 64), 0, stream,
+                     /* x */ (const bf16_t*)a.x, /* wp */ (const bf16_t*)a.w, /* ss_zero */ ep.ss_zero,
+                     /* M */ a.M, /* K */ a.K, /* n_big */ n_big, /* mt_out */ ep.mt_out, /* rot */ ep.rot,
+                     /* y */ (bf16_t*)a.y, /* ys */ a.y_stride, /* res */ (const bf16_t*)a.res,
+                     /* rs */ a.res_stride, /* ep */ ep);
 }
 
 template <int MT, int NTB, int NTS, bool F8 = false>
@@ -1176,10 +1222,7 @@ static int launch_gemm_rw_cfg(const GemmArgs& a, const EpiArgs& ep, hipStream_t 
   const int epi = a.epilogue;
   const bool opk = a.flags & GEMM_OUT_PACKED;
   // every instantiation takes the same kernel arguments
-#define MP_RW(EPI_, OPK_)                                                                                          \
-  hipLaunchKernelGGL((gemm_rw_kernel<MT, NTB, NTS, EPI_, OPK_, F8>), dim3(G), dim3(RW_WAVES * 64), 0, stream,      \
-                     (const bf16_t*)a.x, (const bf16_t*)a.w, (bf16_t*)a.y, a.y_stride, (const bf16_t*)a.res,       \
-                     a.res_stride, a.M, a.K, n_big, ep)
+#define MP_RW(EPI_, OPK_) rw_launch(gemm_rw_kernel<MT, NTB, NTS, EPI_, OPK_, F8>, G, stream, a, ep, n_big)
   if constexpr (F8) {
     // fp8-weight (W8A16) forms, M <= 64: the fused-norm decode epilogues (0 with row scale,
     // packed SwiGLU, residual-stream producer)
@@ -1283,17 +1326,28 @@ static int launch_gemm_rw(const GemmArgs& a, const EpiArgs& ep, hipStream_t stre
 // load policy (non-temporal or default).  Placement only - never correctness.
 template <int MTH, int NT, int EPI, bool NTW>
 __global__ __launch_bounds__(RW_WAVES * 64) void gemm_rwr_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ wp,
+                                                       u64* __restrict__ ss_zero, int M, int K, int rot,
                                                        bf16_t* __restrict__ y, int64_t ys,
-                                                       const bf16_t* __restrict__ res, int64_t rs, int M, int K,
+                                                       const bf16_t* __restrict__ res, int64_t rs,
                                                        const EpiArgs ep) {
-  clear_other(ep);
+  clear_other(ss_zero);
   __shared__ u64 rs_part[SS_PG][SS_ROWS];
   __shared__ float rs_lds[SS_ROWS];
   __shared__ __attribute__((aligned(16))) f32x4 red[RW_WAVES * (MTH * NT < RW_QC ? MTH * NT : RW_QC) * 64];
   const int xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
   const int half = j & 1, g = (j >> 1) * 8 + xcd;
-  rw_body<MTH, NT, EPI, false, false, NTW>(x, wp, y, ys, res, rs, M, K, g * NT, ep, red, rs_part, rs_lds, half * MTH,
-                                           2 * MTH);
+  rw_body<MTH, NT, EPI, false, false, NTW>(x, wp, y, ys, res, rs, M, K, g * NT, rot, ep, red, rs_part, rs_lds,
+                                           half * MTH, 2 * MTH);
+}
+
+// gemm_rwr_kernel's argument list, each value next to its parameter's name (KERNARG ORDER above).
+// The packed activation's row-tile count is not an argument: the kernel's 2 x MTH is ep.mt_out.
+template <class Kern>
+static inline void rwr_launch(Kern kern, int G, hipStream_t stream, const GemmArgs& a, const EpiArgs& ep) {
+  hipLaunchKernelGGL(kern, dim3(G), dim3(RW_WAVES * 64), 0, stream,
+                     /* x */ (const bf16_t*)a.x, /* wp */ (const bf16_t*)a.w, /* ss_zero */ ep.ss_zero,
+                     /* M */ a.M, /* K */ a.K, /* rot */ ep.rot, /* y */ (bf16_t*)a.y, /* ys */ a.y_stride,
+                     /* res */ (const bf16_t*)a.res, /* rs */ a.res_stride, /* ep */ ep);
 }
 
 // Grid = 2 x (tiles / NT) = #CUs (a multiple of 16); epilogues 0 / 2 / 3, MT even.  Returns 1
@@ -1308,10 +1362,7 @@ static int launch_gemm_rwr(const GemmArgs& a, const EpiArgs& ep, hipStream_t str
     if (epi == 1 || (a.flags & GEMM_OUT_PACKED) || C0 % 16 || (2 * tiles) % C0) return 1;
     const int nt = 2 * tiles / C0;
     const bool ntw = !(a.flags & GEMM_ROW_SPLIT_DEFAULT_CACHE);
-#define MP_RWR_W(NT_, EPI_, NTW_)                                                                                  \
-  hipLaunchKernelGGL((gemm_rwr_kernel<MTH, NT_, EPI_, NTW_>), dim3(C0), dim3(RW_WAVES * 64), 0, stream,            \
-                     (const bf16_t*)a.x, (const bf16_t*)a.w, (bf16_t*)a.y, a.y_stride, (const bf16_t*)a.res,       \
-                     a.res_stride, a.M, a.K, ep)
+#define MP_RWR_W(NT_, EPI_, NTW_) rwr_launch(gemm_rwr_kernel<MTH, NT_, EPI_, NTW_>, C0, stream, a, ep)
 #define MP_RWR(NT_, EPI_) \
   { if (ntw) MP_RWR_W(NT_, EPI_, true); else MP_RWR_W(NT_, EPI_, false); }
 #define MP_RWR_E(NT_) \
@@ -1361,11 +1412,12 @@ constexpr int64_t RWK_SLAB_BYTES = (int64_t)32 << 20;  // S x M x N fp32 partial
 // MFMA instructions, no cvt.
 template <int MT, int NT, bool F8 = false, int INL = -1, bool MX = false>
 __global__ __launch_bounds__(RW_WAVES * 64) void gemm_rwk_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ wp,
-                                                       float* __restrict__ part, int M, int N, int K, int S,
+                                                       u64* __restrict__ ss_zero, int M, int N, int K, int S,
+                                                       int mt_out, int rot, float* __restrict__ part,
                                                        const EpiArgs ep, bf16_t* __restrict__ y, int64_t ys,
                                                        const bf16_t* __restrict__ res, int64_t rs,
                                                        int* __restrict__ tick) {
-  clear_other(ep);
+  clear_other(ss_zero);
   static_assert(!MX || (F8 && INL < 0), "MX: fp8 weights, reduce launch");
   constexpr int R = MX ? mx_depth<MT, NT>() : rw_depth2<MT, NT, F8>();
   using WT = std::conditional_t<F8, uint8_t, bf16_t>;
@@ -1394,7 +1446,7 @@ __global__ __launch_bounds__(RW_WAVES * 64) void gemm_rwk_kernel(const bf16_t* _
   const int nst = nks / KS;  // ring steps over all of K
   const int ks0 = (int)((int64_t)sp * nst / S), ks1 = (int)((int64_t)(sp + 1) * nst / S);
   const int cnt = (ks1 - ks0 + RW_WAVES - 1) / RW_WAVES;
-  const int krot = rw_krot(ks1 - ks0, ep.rot);
+  const int krot = rw_krot(ks1 - ks0, rot);
   const WT* wb = reinterpret_cast<const WT*>(wp) + ((int64_t)tile0 * nks) * 512 + lane * 8;
   const bf16_t* xl = x + lane * 8;
   const uint8_t* xm = reinterpret_cast<const uint8_t*>(x) + lane * 16;  // MX: this lane's 2 x 16 bytes
@@ -1437,7 +1489,7 @@ __global__ __launch_bounds__(RW_WAVES * 64) void gemm_rwk_kernel(const bf16_t* _
         rb[s][t] = (u32x8){w0[0], w0[1], w1[0], w1[1], w2[0], w2[1], w3[0], w3[1]};                          \
       }                                                                                                      \
       _Pragma("unroll") for (int mt = 0; mt < MT; ++mt) {                                                    \
-        const int64_t o_ = (int64_t)k_ * ep.mt_out + min(mt, ep.mt_out - 1);                                 \
+        const int64_t o_ = (int64_t)k_ * mt_out + min(mt, mt_out - 1);                                       \
         const u32x4 a0 = *reinterpret_cast<const u32x4*>(xm + (o_ << 11)),                                   \
                     a1 = *reinterpret_cast<const u32x4*>(xm + (o_ << 11) + 1024);                            \
         ra[s][mt] = (u32x8){a0[0], a0[1], a0[2], a0[3], a1[0], a1[1], a1[2], a1[3]};                         \
@@ -1447,7 +1499,7 @@ __global__ __launch_bounds__(RW_WAVES * 64) void gemm_rwk_kernel(const bf16_t* _
       _Pragma("unroll") for (int t = 0; t < NT; ++t) rb[s][t] =                                              \
           __builtin_nontemporal_load(reinterpret_cast<const BT*>(wb + (((int64_t)t * nks + k_) << 9)));     \
       _Pragma("unroll") for (int mt = 0; mt < MT; ++mt) ra[s][mt] =                                          \
-          load_a_rows(xl + (((int64_t)k_ * ep.mt_out + min(mt, ep.mt_out - 1)) << 9), lane,                \
+          load_a_rows(xl + (((int64_t)k_ * mt_out + min(mt, mt_out - 1)) << 9), lane,                      \
                       mt * 16 + (lane & 15) < M);                                                            \
     }                                                                                                        \
   }
@@ -1753,6 +1805,21 @@ static inline int rwk_comb(int flags) {
   return (flags & GEMM_SPLITK_INLINE) ? 1 : 0;
 }
 
+// gemm_rwk_kernel's argument list, each value next to its parameter's name (KERNARG ORDER above).
+// ``tick`` null: the slab-only form (reduce launch or GEMM_PARTIALS), which takes no output or
+// residual arguments; non-null: the in-launch combine, which runs the epilogue itself.
+template <class Kern>
+static inline void rwk_launch(Kern kern, dim3 grid, hipStream_t stream, const GemmArgs& a, const EpiArgs& ep,
+                              float* part, int S, int* tick) {
+  const bool inl = tick != nullptr;
+  hipLaunchKernelGGL(kern, grid, dim3(RW_WAVES * 64), 0, stream,
+                     /* x */ (const bf16_t*)a.x, /* wp */ (const bf16_t*)a.w, /* ss_zero */ ep.ss_zero,
+                     /* M */ a.M, /* N */ a.N, /* K */ a.K, /* S */ S, /* mt_out */ ep.mt_out, /* rot */ ep.rot,
+                     /* part */ part, /* ep */ ep, /* y */ inl ? (bf16_t*)a.y : nullptr,
+                     /* ys */ inl ? a.y_stride : (int64_t)0, /* res */ inl ? (const bf16_t*)a.res : nullptr,
+                     /* rs */ inl ? a.res_stride : (int64_t)0, /* tick */ tick);
+}
+
 template <int MT, bool F8 = false, bool MX = false>
 static int launch_gemm_rwk(const GemmArgs& a, const EpiArgs& ep, hipStream_t stream, int comb = 0) {
   const bool inl = comb > 0 && !MX;
@@ -1773,10 +1840,7 @@ static int launch_gemm_rwk(const GemmArgs& a, const EpiArgs& ep, hipStream_t str
   if (inl && MT <= 4 && nt >= 2 && tiles / nt <= SK_MAX_GROUPS / 8 - 1 &&
       (int64_t)tiles * MT * S * 1024 <= RWK_SLAB_BYTES) {
     if constexpr (MT <= 4 && !MX) {  // the MX form has no in-launch combine (inl is false there)
-#define MP_RWKI(NT_, E_)                                                                                       \
-  hipLaunchKernelGGL((gemm_rwk_kernel<MT, NT_, F8, E_>), g1, dim3(RW_WAVES * 64), 0, stream, (const bf16_t*)a.x,  \
-                     (const bf16_t*)a.w, part, M, N, a.K, S, ep, (bf16_t*)a.y, a.y_stride, (const bf16_t*)a.res,   \
-                     a.res_stride, tick)
+#define MP_RWKI(NT_, E_) rwk_launch(gemm_rwk_kernel<MT, NT_, F8, E_>, g1, stream, a, ep, part, S, tick)
 #define MP_RWKI_E(NT_) \
   { if (epi == 3) MP_RWKI(NT_, 3); else if (epi == 2) MP_RWKI(NT_, 2); else MP_RWKI(NT_, 0); }
       switch (nt) {
@@ -1790,11 +1854,8 @@ static int launch_gemm_rwk(const GemmArgs& a, const EpiArgs& ep, hipStream_t str
       return 0;
     }
   }
-#define MP_RWKS(NT_)                                                                                           \
-  if constexpr (NT_ <= nt_max)                                                                                 \
-    hipLaunchKernelGGL((gemm_rwk_kernel<MT, NT_, F8, -1, MX>), g1, dim3(RW_WAVES * 64), 0, stream,             \
-                       (const bf16_t*)a.x, (const bf16_t*)a.w, part, M, N, a.K, S, ep, nullptr, 0, nullptr, 0,    \
-                       nullptr)
+#define MP_RWKS(NT_) \
+  if constexpr (NT_ <= nt_max) rwk_launch(gemm_rwk_kernel<MT, NT_, F8, -1, MX>, g1, stream, a, ep, part, S, nullptr)
   switch (nt) {
     case 1: MP_RWKS(1); break;
     case 2: MP_RWKS(2); break;

@@ -64,10 +64,11 @@ __global__ __launch_bounds__(RW_WAVES * 64) void moe_gate_up_kernel(const bf16_t
   bf16_t* ye = act + (int64_t)e * MT * 16 * (N / 2);
   const int b = blockIdx.x;
   if (b < n_big) {
-    rw_body<MT, NTB, 1, true, true>(x, wp, ye, 0, nullptr, 0, M, K, b * NTB, epe, red, rs_part, rs_lds, 0, MT);
+    rw_body<MT, NTB, 1, true, true>(x, wp, ye, 0, nullptr, 0, M, K, b * NTB, ep.rot, epe, red, rs_part, rs_lds, 0,
+                                    MT);
   } else {
-    rw_body<MT, NTS, 1, true, true>(x, wp, ye, 0, nullptr, 0, M, K, n_big * NTB + (b - n_big) * NTS, epe, red,
-                                    rs_part, rs_lds, 0, MT);
+    rw_body<MT, NTS, 1, true, true>(x, wp, ye, 0, nullptr, 0, M, K, n_big * NTB + (b - n_big) * NTS, ep.rot, epe,
+                                    red, rs_part, rs_lds, 0, MT);
   }
 }
 
