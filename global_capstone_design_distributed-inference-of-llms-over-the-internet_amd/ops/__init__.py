@@ -1644,6 +1644,121 @@ def moe_down_w8(act, w8, w_scale, cnt, wd, a_rows: int, out=None):
 
 
 # ---------------------------------------------------------------------------------------
+# The same MLP ABOVE 64 rows (csrc/gemm_moe_rows.hip): the T * k routed (token, expert) pairs are
+# grouped by expert on the device (``moe_group``: no host sync), then each expert's GEMMs run over the
+# rows routed to it only - gate/up gathers its rows from the row-major ``x`` through ``tok``, down adds
+# its weighted rows into the tokens' output rows in ascending expert order (fp32, one bf16 rounding, no
+# atomics: the same bits on every run).  Activations are row-major bf16; weights as above.
+def moe_rows_ok(T: int, E: int, k: int, H: int, F: int) -> bool:
+    """Whether the three row-gathered launches cover the shape (a dry dispatch, as ``moe_w8_ok``)."""
+    key = ("rows", int(T), int(E), int(k), int(H), int(F))
+    if key not in _MOE_OK:
+        _MOE_OK[key] = bool(native_available() and torch.ops.mpamd.moe_rows_ok(*key[1:]))
+    return _MOE_OK[key]
+
+
+def moe_group(idx: torch.Tensor, w: torch.Tensor, E: int):
+    """Top-k routing (``moe.route``'s ``idx`` int64 [T, k], ``w`` fp32 [T, k]) -> (off int32 [E + 1], tok
+    int32 [T k], wsel fp32 [T k]): the pairs in (expert, token) order - the stable counting sort, equal to
+    ``argsort(idx.reshape(-1), stable=True)`` - with ``off`` the exclusive prefix sums of the expert counts."""
+    if idx.dim() != 2 or idx.dtype != torch.int64 or w.shape != idx.shape or w.dtype != torch.float32:
+        raise ValueError("moe_group takes idx int64 [T, k] and w fp32 [T, k]")
+    T, k = idx.shape
+    if not 1 <= k <= E or T < 1:
+        raise ValueError(f"moe_group: T >= 1 and 1 <= k <= E, got T={T} k={k} E={E}")
+    if not _native(idx):
+        flat = idx.reshape(-1)
+        order = torch.argsort(flat, stable=True)
+        off = torch.zeros(E + 1, dtype=torch.int32)
+        off[1:] = torch.cumsum(torch.bincount(flat, minlength=E), 0)
+        return off, (order // k).to(torch.int32), w.reshape(-1)[order]
+    off = torch.empty(E + 1, dtype=torch.int32, device=idx.device)
+    tok = torch.empty(T * k, dtype=torch.int32, device=idx.device)
+    wsel = torch.empty(T * k, dtype=torch.float32, device=idx.device)
+    torch.ops.mpamd.moe_group(idx.contiguous(), w.contiguous(), off, tok, wsel)
+    return off, tok, wsel
+
+
+def _moe_rows_dims(w8: torch.Tensor, w_scale: torch.Tensor, off: torch.Tensor, tok: torch.Tensor, T: int):
+    """(E, N, K, k) of stacked expert weights and a grouping of T tokens, with the checks both ops share."""
+    if w8.dim() != 5 or tuple(w8.shape[3:]) != (64, 8) or w8.dtype != torch.uint8:
+        raise ValueError("w8 must be stacked fp8 expert weights uint8 [E, N/16, K/32, 64, 8]")
+    E, N, K = w8.shape[0], 16 * w8.shape[1], 32 * w8.shape[2]
+    if tuple(w_scale.shape) != (E, N) or w_scale.dtype != torch.float32:
+        raise ValueError(f"w_scale must be fp32 [E, N] = [{E}, {N}]")
+    if off.numel() != E + 1 or off.dtype != torch.int32:
+        raise ValueError(f"off must be int32 [{E + 1}] pair offsets (ops.moe_group)")
+    if T < 1 or tok.dim() != 1 or tok.dtype != torch.int32 or tok.numel() < T or tok.numel() % T:
+        raise ValueError(f"tok must be int32 [T k] tokens of the {T} rows (ops.moe_group)")
+    return E, N, K, tok.numel() // T
+
+
+def moe_gate_up_w8_rows(x, w8, w_scale, off, tok, out=None):
+    """out [T k, F] bf16 row-major: row p = SwiGLU(x[tok[p]] @ gate_up[e]^T) for the expert e whose range
+    off[e] <= p < off[e + 1] holds p (fp32 SwiGLU, one rounding); ``x`` row-major [T, H].  One launch;
+    an expert without rows is never read."""
+    if x.dim() != 2:
+        raise ValueError("x must be row-major [T, H]")
+    T = x.shape[0]
+    E, N, K, k = _moe_rows_dims(w8, w_scale, off, tok, T)
+    if x.shape[1] != K:
+        raise ValueError(f"x must be [T, {K}]")
+    if out is None:
+        out = torch.empty(T * k, N // 2, dtype=x.dtype, device=x.device)
+    elif tuple(out.shape) != (T * k, N // 2) or out.dtype != x.dtype:
+        raise ValueError(f"out must be [{T * k}, {N // 2}] {x.dtype}")
+    if not _native(x):
+        o, tl = off.tolist(), tok.long()
+        for e in range(E):
+            if o[e + 1] > o[e]:
+                gu = x[tl[o[e]:o[e + 1]]].float() @ unpack_weight_w8(w8[e], w_scale[e], torch.float32).t()
+                g, u = gu.view(-1, N // (2 * GU_BLOCK), 2, GU_BLOCK).unbind(2)
+                out[o[e]:o[e + 1]] = (torch.nn.functional.silu(g) * u).reshape(-1, N // 2).to(out.dtype)
+        return out
+    torch.ops.mpamd.moe_gate_up_w8_rows(x, w8, w_scale, off, tok, out)
+    return out
+
+
+def moe_down_w8_rows(act, w8, w_scale, off, tok, wsel, T: int, out=None):
+    """y [T, H] = bf16(sum over token t's pairs p, in ascending expert order, of wsel[p] * (act[p] @
+    down[e]^T)) with ``act`` [T k, F] as ``moe_gate_up_w8_rows`` leaves it: channel scales and routing
+    weights in fp32, ONE bf16 rounding, a fixed summation order.  One launch."""
+    T = int(T)
+    E, N, K, k = _moe_rows_dims(w8, w_scale, off, tok, T)
+    if tuple(act.shape) != (T * k, K):
+        raise ValueError(f"act must be [{T * k}, {K}]")
+    if tuple(wsel.shape) != (T * k,) or wsel.dtype != torch.float32:
+        raise ValueError(f"wsel must be fp32 [{T * k}] routing weights (ops.moe_group)")
+    if out is None:
+        out = torch.empty(T, N, dtype=act.dtype, device=act.device)
+    elif tuple(out.shape) != (T, N) or out.dtype != act.dtype:
+        raise ValueError(f"out must be [{T}, {N}] {act.dtype}")
+    if not _native(act):
+        o, tl = off.tolist(), tok.long()
+        tot = torch.zeros(T, N, dtype=torch.float32)
+        for e in range(E):
+            if o[e + 1] > o[e]:
+                ye = act[o[e]:o[e + 1]].float() @ unpack_weight_w8(w8[e], w_scale[e], torch.float32).t()
+                tot.index_add_(0, tl[o[e]:o[e + 1]], ye * wsel[o[e]:o[e + 1], None])
+        out.copy_(tot.to(out.dtype))
+        return out
+    torch.ops.mpamd.moe_down_w8_rows(act, w8, w_scale, off, tok, wsel, _moe_rows_workspace(T, N, act.device), out)
+    return out
+
+
+_MOE_ROWS_WS = {}
+
+
+def _moe_rows_workspace(T: int, H: int, device) -> torch.Tensor:
+    """fp32 [T * H] scratch of ``moe_down_w8_rows`` (per device, grown on demand; the kernel zeroes the
+    columns it uses before it adds into them, so nothing of an earlier call survives)."""
+    ws = _MOE_ROWS_WS.get(device)
+    if ws is None or ws.numel() < T * H:
+        ws = _MOE_ROWS_WS[device] = torch.empty(T * H, dtype=torch.float32, device=device)
+    return ws[:T * H]
+
+
+# ---------------------------------------------------------------------------------------
 # W4A16 decode GEMM (csrc/gemm_w4.hip mp_gemm_w4): OCP MXFP4 weights - e2m1 codes, one e8m0 scale
 # per 32 weights along K, 4.25 bits per weight - dequantized in registers into the bf16 MFMA
 # (v_cvt_scalef32_pk_bf16_fp4), bf16 activations.  Weight layout, in the bf16 fragment order:

@@ -31,6 +31,9 @@ EXTRA = os.environ.get("MPAMD_HIPCC_EXTRA", "").split()
 # load addresses without a scalar load of the argument buffer (docs/KERNARG_PRELOAD.md: at most 14
 # dwords, and only the pointers and scalars ahead of the first by-value struct)
 PRELOAD = ["-mllvm", "-amdgpu-kernarg-preload-count=16"]
+# per-file device flags.  gemm_moe_rows.hip is built without the packed fp32 VALU forms (v_pk_add_f32,
+# v_pk_mul_f32, v_pk_fma_f32): its fp32 epilogues are scalar per lane
+FILE_FLAGS = {"gemm_moe_rows.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 
 
 def _torch_paths():
@@ -97,7 +100,7 @@ def build(force: bool = False, jobs: int = 0, verbose: bool = False, out: str = 
         objs.append(obj)
         t = stale(src, obj)
         if t is not None:
-            cmds.append(([HIPCC] + common + ["-c", src, "-o", obj], obj, t))
+            cmds.append(([HIPCC] + common + FILE_FLAGS.get(os.path.basename(src), []) + ["-c", src, "-o", obj], obj, t))
     bobj = os.path.join(BUILD, "bindings.o")
     objs.append(bobj)
     t = stale(binding, bobj)

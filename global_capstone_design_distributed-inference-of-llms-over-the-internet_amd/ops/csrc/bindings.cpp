@@ -810,6 +810,89 @@ bool moe_w8_ok(int64_t M, int64_t E, int64_t H, int64_t F) {
   return mp_moe_w8_ok((int)M, (int)E, (int)H, (int)F) != 0;
 }
 
+// Row-gathered grouped MoE GEMMs (gemm_moe_rows.hip).  An int32 / fp32 device vector of n elements
+static void check_moe_vec(const at::Tensor& t, at::ScalarType ty, int64_t n, const at::Tensor& like, const char* what) {
+  MP_CHECK(t.is_cuda() && t.scalar_type() == ty && t.is_contiguous() && t.numel() == n && t.device() == like.device(),
+           what);
+}
+
+// the grouping (mp_moe_group's outputs) of P = T k pairs over E experts -> k
+static int check_moe_pairs(const at::Tensor& off, const at::Tensor& tok, int64_t T, int E, const at::Tensor& like) {
+  check_moe_vec(off, at::kInt, E + 1, like, "off: int32 [E + 1] pair offsets on the weights' device");
+  MP_CHECK(T > 0 && tok.numel() >= T && tok.numel() % T == 0 && tok.numel() <= (1 << 16), "tok: int32 [T k] tokens");
+  check_moe_vec(tok, at::kInt, tok.numel(), like, "tok: int32 [T k] tokens on the weights' device");
+  return (int)(tok.numel() / T);
+}
+
+// bf16 contiguous row-major [rows, cols], 16-byte aligned
+static void check_moe_rows(const at::Tensor& t, const char* name, int64_t rows, int64_t cols, const at::Tensor& like) {
+  check_bf16_cuda(t, name);
+  check_rows(t, name);
+  MP_CHECK(t.is_contiguous() && t.size(0) == rows && t.size(1) == cols && t.device() == like.device(),
+           std::string(name) + ": contiguous [rows, cols] of the grouped shape");
+}
+
+void moe_group(const at::Tensor& idx, const at::Tensor& w, at::Tensor& off, at::Tensor& tok, at::Tensor& wsel) {
+  MP_CHECK(idx.is_cuda() && idx.scalar_type() == at::kLong && idx.dim() == 2 && idx.is_contiguous() && idx.numel() > 0,
+           "moe_group: idx int64 [T, k] expert ids");
+  const int64_t T = idx.size(0), k = idx.size(1), E = off.numel() - 1;
+  MP_CHECK(w.is_cuda() && w.scalar_type() == at::kFloat && w.is_contiguous() && w.sizes() == idx.sizes() &&
+               w.device() == idx.device(),
+           "moe_group: w fp32 [T, k] routing weights");
+  MP_CHECK(E >= 1, "moe_group: off int32 [E + 1]");
+  check_moe_vec(off, at::kInt, E + 1, idx, "moe_group: off int32 [E + 1]");
+  check_moe_vec(tok, at::kInt, T * k, idx, "moe_group: tok int32 [T k]");
+  check_moe_vec(wsel, at::kFloat, T * k, idx, "moe_group: wsel fp32 [T k]");
+  MP_CHECK(T * k <= (1 << 16), "moe_group: at most 65536 pairs");
+  const int rc = mp_moe_group(idx.data_ptr<int64_t>(), w.data_ptr<float>(), off.data_ptr<int32_t>(),
+                              tok.data_ptr<int32_t>(), wsel.data_ptr<float>(), (int)T, (int)k, (int)E, cur_stream());
+  TORCH_CHECK(rc != 1, "mpamd: moe_group: no grouping kernel covers T=", T, " k=", k, " E=", E);
+  check_launch(rc, "moe_group");
+}
+
+// out bf16 [T k, F]: row p = SwiGLU(x[tok[p]] . gate_up[expert of p]^T)
+void moe_gate_up_w8_rows(const at::Tensor& x, const at::Tensor& w8, const at::Tensor& wsc, const at::Tensor& off,
+                         const at::Tensor& tok, at::Tensor& out) {
+  const auto [E, N, K] = check_moe_weight(w8, wsc);
+  MP_CHECK(N % 32 == 0, "moe_gate_up_w8_rows: SwiGLU needs N % 32 == 0");
+  MP_CHECK(x.dim() == 2, "x must be 2-D [T, H]");
+  const int64_t T = x.size(0);
+  const int k = check_moe_pairs(off, tok, T, E, w8);
+  check_moe_rows(x, "x", T, K, w8);
+  check_moe_rows(out, "out", T * k, N / 2, w8);
+  const int rc = mp_moe_gate_up_w8_rows(x.data_ptr(), w8.data_ptr(), wsc.data_ptr<float>(), off.data_ptr<int32_t>(),
+                                        tok.data_ptr<int32_t>(), out.data_ptr(), (int)T, (int)(T * k), E, K, N / 2,
+                                        cur_stream());
+  TORCH_CHECK(rc != 1, "mpamd: moe_gate_up_w8_rows: no kernel covers T=", T, " k=", k, " E=", E, " H=", K, " F=", N / 2);
+  check_launch(rc, "moe_gate_up_w8_rows");
+}
+
+// y bf16 [T, H] = bf16(sum over each token's pairs of wsel * (act . down^T)); ws: fp32 [T, H] scratch
+void moe_down_w8_rows(const at::Tensor& act, const at::Tensor& w8, const at::Tensor& wsc, const at::Tensor& off,
+                      const at::Tensor& tok, const at::Tensor& wsel, at::Tensor& ws, at::Tensor& y) {
+  const auto [E, N, K] = check_moe_weight(w8, wsc);
+  MP_CHECK(y.dim() == 2, "y must be 2-D [T, H]");
+  const int64_t T = y.size(0);
+  const int k = check_moe_pairs(off, tok, T, E, w8);
+  check_moe_rows(act, "act", T * k, K, w8);
+  check_moe_vec(wsel, at::kFloat, T * k, w8, "wsel: fp32 [T k] routing weights on the weights' device");
+  check_moe_vec(ws, at::kFloat, T * N, w8, "ws: fp32 [T, H] workspace on the weights' device");
+  MP_CHECK(reinterpret_cast<uintptr_t>(ws.data_ptr()) % 16 == 0, "ws must be 16-B aligned");
+  check_bf16_cuda(y, "y");
+  check_rows(y, "y");
+  MP_CHECK(y.size(1) == N && y.device() == w8.device(), "y shape");
+  const int rc = mp_moe_down_w8_rows(act.data_ptr(), w8.data_ptr(), wsc.data_ptr<float>(), off.data_ptr<int32_t>(),
+                                     tok.data_ptr<int32_t>(), wsel.data_ptr<float>(), ws.data_ptr<float>(),
+                                     y.data_ptr(), y.stride(0), (int)T, (int)(T * k), E, N, K, cur_stream());
+  TORCH_CHECK(rc != 1, "mpamd: moe_down_w8_rows: no kernel covers T=", T, " k=", k, " E=", E, " H=", N, " F=", K);
+  check_launch(rc, "moe_down_w8_rows");
+}
+
+bool moe_rows_ok(int64_t T, int64_t E, int64_t k, int64_t H, int64_t F) {
+  if (T <= 0 || T > (1 << 16) || E <= 0 || E > 64 || k <= 0 || k > E) return false;
+  return mp_moe_rows_ok((int)T, (int)E, (int)k, (int)H, (int)F) != 0;
+}
+
 // Batched LoRA (lora.hip): the stacked adapter matrices, the row slots and the fp32 intermediate
 static mp::LoraArgs lora_args(const at::Tensor& mats, const char* name, const at::Tensor& slots, const at::Tensor& t,
                               int64_t M_) {
@@ -1129,6 +1212,12 @@ TORCH_LIBRARY(mpamd, m) {
   m.def("moe_gate_up_w8(Tensor x, Tensor w8, Tensor wsc, Tensor cnt, Tensor(a!) act, int M) -> ()");
   m.def("moe_down_w8(Tensor act, Tensor w8, Tensor wsc, Tensor cnt, Tensor wd, Tensor(a!) y, int M) -> ()");
   m.def("moe_w8_ok(int M, int E, int H, int F) -> bool", &moe_w8_ok);
+  m.def("moe_group(Tensor idx, Tensor w, Tensor(a!) off, Tensor(b!) tok, Tensor(c!) wsel) -> ()");
+  m.def("moe_gate_up_w8_rows(Tensor x, Tensor w8, Tensor wsc, Tensor off, Tensor tok, Tensor(a!) out) -> ()");
+  m.def(
+      "moe_down_w8_rows(Tensor act, Tensor w8, Tensor wsc, Tensor off, Tensor tok, Tensor wsel, Tensor(a!) ws, "
+      "Tensor(b!) y) -> ()");
+  m.def("moe_rows_ok(int T, int E, int k, int H, int F) -> bool", &moe_rows_ok);
   m.def("lora_shrink(Tensor x, Tensor A, Tensor scale, Tensor slots, Tensor(a!) t, int M) -> ()");
   m.def("lora_expand(Tensor t, Tensor B, Tensor slots, Tensor(a!) y) -> ()");
   m.def("lora_ok(int M, int N, int K, int R) -> bool", &lora_ok);
@@ -1168,6 +1257,9 @@ TORCH_LIBRARY_IMPL(mpamd, CUDA, m) {
   m.impl("dequant_w4", &dequant_w4);
   m.impl("moe_gate_up_w8", &moe_gate_up_w8);
   m.impl("moe_down_w8", &moe_down_w8);
+  m.impl("moe_group", &moe_group);
+  m.impl("moe_gate_up_w8_rows", &moe_gate_up_w8_rows);
+  m.impl("moe_down_w8_rows", &moe_down_w8_rows);
   m.impl("lora_shrink", &lora_shrink);
   m.impl("lora_expand", &lora_expand);
   m.impl("pack_weight", &pack_weight);

@@ -213,6 +213,16 @@ int mp_moe_gate_up_w8(const void* x, const void* w8, const float* wsc, const int
 int mp_moe_down_w8(const void* act, const void* w8, const float* wsc, const int32_t* cnt, const float* wd, void* y,
                    int64_t y_stride, int M, int E, int H, int F, hipStream_t stream);
 int mp_moe_w8_ok(int M, int E, int H, int F);
+// gemm_moe_rows.hip: the same MLP above 64 rows - pairs grouped by expert on the device, then the two
+// grouped GEMMs over each expert's gathered rows (P = T k pairs; 1: shape not covered, nothing launched)
+int mp_moe_group(const int64_t* idx, const float* w, int32_t* off, int32_t* tok, float* wsel, int T, int k, int E,
+                 hipStream_t stream);
+int mp_moe_gate_up_w8_rows(const void* x, const void* w8, const float* wsc, const int32_t* off, const int32_t* tok,
+                           void* out, int T, int P, int E, int H, int F, hipStream_t stream);
+int mp_moe_down_w8_rows(const void* act, const void* w8, const float* wsc, const int32_t* off, const int32_t* tok,
+                        const float* wsel, float* ws, void* y, int64_t y_stride, int T, int P, int E, int H, int F,
+                        hipStream_t stream);
+int mp_moe_rows_ok(int T, int E, int k, int H, int F);
 // lora.hip: 0, 1 when the shape is not covered (needs M <= 64, K % 32 == 0, N % 8 == 0, R % 16 == 0,
 // R <= 192; nothing launched), < 0 for a bad call, else the HIP error.  M == 0 returns 0.
 int mp_lora_ok(int M, int N, int K, int R);

@@ -17,7 +17,11 @@ MI355X execution strategy (runtime/executor.py ``_moe_mlp``):
   equal the sparse schedule's, the extra MFMA work is free at M <= 64, and the step has no
   data-dependent shapes - it stays inside the hipGraph;
 * prefill (T > 64) groups tokens by expert (one host sync per layer, outside any graph),
-  runs each expert's GEMMs on its gathered rows and scatter-adds the weighted result.
+  runs each expert's GEMMs on its gathered rows and scatter-adds the weighted result;
+* fp8 experts, prefill steps above 64 rows (up to MPAMD_MOE_ROWS; decode steps with
+  MPAMD_MOE_ROWS_DECODE=1): the same sparse schedule on the device -
+  ``ops.moe_group`` sorts the pairs by expert, ``ops.moe_gate_up_w8_rows`` / ``moe_down_w8_rows`` run
+  every expert over its gathered rows in two launches (ops/csrc/gemm_moe_rows.hip), no host sync.
 """
 from __future__ import annotations
 

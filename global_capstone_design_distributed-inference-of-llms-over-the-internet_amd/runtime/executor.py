@@ -19,6 +19,9 @@ Replaces the reference's Stage0 / StageSegment / StageLast modules
     Mixtral, 65..256 rows, LoRA steps of <= 64 rows): 7 launches per layer - add+RMSNorm, qkv, RoPE +
     attention, o, add+RMSNorm, gate/up with SwiGLU, down - on activations in the MFMA-fragment layout;
   - "dense": everything else (CPU, prefill, deep prompts, --gemm hipblaslt): those 7 on row-major activations;
+    an fp8 Mixtral stage runs the experts of its 65 .. MPAMD_MOE_ROWS-row prefill steps (and, with
+    MPAMD_MOE_ROWS_DECODE=1, decode steps) here on the row-gathered grouped kernels (device-side grouping +
+    two launches, ``_moe_mlp``) and dequantizes qkv / o only;
 * decode steps replayed from hipGraphs captured per (batch bucket, context bucket);
 * the last stage applies the final norm and ``lm_head`` to the LAST token of each
   sequence only (the reference projects every prefill position, src/llama_partition.py:470).
@@ -53,6 +56,11 @@ logger = logging.getLogger(__name__)
 # per-path weight tensors a layer loop reads (what CPU offload streams)
 _PACKED_FIELDS = ("input_norm", "post_norm", "qkv_p", "o_p", "gate_up_p", "down_p", "router_p")
 _DENSE_FIELDS = ("input_norm", "post_norm", "qkv", "o", "gate_up", "down", "router")
+# largest step (rows) an fp8 Mixtral stage sends to the row-gathered grouped expert kernels; above it
+# the experts dequantize into library GEMMs.  A 64-row block re-streams its expert's weights: at
+# Mixtral-8x7B shapes the kernels win up to 4096 rows and lose at 6144 (profiles/moe_rows/README.md).
+# MPAMD_MOE_ROWS overrides it
+MOE_ROWS_DEFAULT = 4096
 _GPT2_FIELDS = ("ln1_w", "ln1_b", "attn_w", "attn_b", "proj_w", "proj_b", "ln2_w", "ln2_b", "fc_w", "fc_b",
                 "fc2_w", "fc2_b")
 
@@ -359,6 +367,13 @@ class StageExecutor:
                     self._w8 = True  # the W8A16 layout and kernels (never the fused-norm path: _fused stays off)
                     self.graph_max_batch = min(self.graph_max_batch, 64)
         self._moe_grouped = os.environ.get("MPAMD_MOE_GROUPED", "1") != "0"
+        # ... and prefill steps (prompts, chunks, mixed steps) of 65 .. MPAMD_MOE_ROWS rows run the experts
+        # on the row-gathered grouped kernels (ops.moe_group / moe_gate_up_w8_rows / moe_down_w8_rows);
+        # 0 keeps the dequantizing schedule for them (qkv / o dequantize either way).  Pure decode steps
+        # of 65+ sessions keep the dequantizing schedule - the launches recorded for them in
+        # tests/golden/executor_paths - unless MPAMD_MOE_ROWS_DECODE=1 sends them to the same kernels
+        self._moe_rows_cap = int(os.environ.get("MPAMD_MOE_ROWS", str(MOE_ROWS_DEFAULT)))
+        self._moe_rows_decode = os.environ.get("MPAMD_MOE_ROWS_DECODE", "0") == "1"
         # MXFP4 weights (StageWeights.quantize_mxfp4: norm weights folded in before the one
         # quantization): <= 64-row decode steps run the fused-norm path on ops.linear_w4, everything
         # else dequantizes one projection at a time (LlamaLayer.dense) and normalises with unit weights
@@ -1289,9 +1304,19 @@ class StageExecutor:
         else:
             logits = ops.linear(xn, L.router)
         w, idx = moe.route(logits, k)
+        F = cfg.intermediate_size
+        if (self._moe_w8 and not packed and 64 < T <= self._moe_rows_cap and
+                (not st.decode or self._moe_rows_decode) and getattr(L, "gate_up_w8", None) is not None and
+                ops.moe_rows_ok(T, E, k, H, F)):
+            # fp8 experts above 64 rows: group the pairs by expert on the device, then the two
+            # row-gathered grouped launches (ops/csrc/gemm_moe_rows.hip) - no host sync, nothing dequantized
+            off, tok, wsel = ops.moe_group(idx, w, E)
+            rows = ops.moe_gate_up_w8_rows(xn, L.gate_up_w8, L.gate_up_ws, off, tok, out=e("moe_rows", (T * k, F)))
+            ops.moe_down_w8_rows(rows, L.down_w8, L.down_ws, off, tok, wsel, T, out=mlp)
+            return
         acc = e("moe_acc", (T, H), torch.float32)
         acc.zero_()
-        gp = (lambda j: L.gate_up_p[j]) if L.gate_up_p is not None else (lambda j: None)  # noqa: E731
+        gp =(lambda j: L.gate_up_p[j]) if L.gate_up_p is not None else (lambda j: None)  # noqa: E731
         dp = (lambda j: L.down_p[j]) if L.down_p is not None else (lambda j: None)  # noqa: E731
         # fp8 experts (no 16-bit copy kept): dequantize ONE expert's projection at a time
         gw = (lambda j: L.gate_up[j]) if L.gate_up is not None else \
