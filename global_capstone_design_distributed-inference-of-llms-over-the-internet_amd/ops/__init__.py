@@ -1566,6 +1566,56 @@ def linear_w8(x, w8, w_scale, a_rows: int, out=None, epilogue: int = 0, residual
 
 
 # ---------------------------------------------------------------------------------------
+# W8A16 GEMM ABOVE 64 rows (csrc/gemm_w8_rows.hip mp_gemm_w8_rows): row-major bf16 activations with a row
+# stride, the fp8 weight read in place (no dequantized copy), two-dimensionally tiled; epilogue 0 or
+# SwiGLU, row-major output.
+_W8_ROWS_OK = {}
+
+
+def w8_rows_ok(T: int, N: int, K: int, epilogue: int = 0) -> bool:
+    """Whether ``linear_w8_rows`` has a kernel for the shape: T >= 65, N % 16 == 0 (SwiGLU: % 32),
+    K % 128 == 0 (a dry dispatch, as ``moe_rows_ok``)."""
+    key = (int(T), int(N), int(K), int(epilogue))
+    if key not in _W8_ROWS_OK:
+        _W8_ROWS_OK[key] = bool(native_available() and torch.ops.mpamd.gemm_w8_rows_ok(*key))
+    return _W8_ROWS_OK[key]
+
+
+def linear_w8_rows(x, w8, w_scale, out=None, epilogue: int = 0):
+    """y [T, N'] = epilogue(x @ W^T) for row-major ``x`` [T, K] (unit inner stride, row stride % 8 == 0) and an
+    fp8 weight (``w8_from_fp8`` layout + fp32 column scales [N]); epilogue 0 (N' = N) or 1 (SwiGLU over the
+    16-row gate/up interleave, N' = N / 2).  Channel scales in fp32, one rounding to bf16, the same bits on
+    every run.  ``out``: any [T, N'] view with unit inner stride.  An uncovered shape is an error on the GPU
+    (``w8_rows_ok``); CPU tensors run ``reference.linear`` on the dequantized weight."""
+    if w8.dim() != 4 or tuple(w8.shape[2:]) != (64, 8) or w8.dtype != torch.uint8:
+        raise ValueError("w8 must be an fp8 weight uint8 [N/16, K/32, 64, 8] (ops.w8_from_fp8)")
+    N, K = 16 * w8.shape[0], 32 * w8.shape[1]
+    if tuple(w_scale.shape) != (N,) or w_scale.dtype != torch.float32:
+        raise ValueError(f"w_scale must be fp32 [{N}] column scales")
+    if epilogue not in (0, 1):
+        raise ValueError("linear_w8_rows: epilogue 0 (store) or 1 (SwiGLU)")
+    if x.dim() != 2 or x.shape[1] != K:
+        raise ValueError(f"x must be row-major [T, {K}]")
+    T, ncols = x.shape[0], N // 2 if epilogue == 1 else N
+    if out is not None and (tuple(out.shape) != (T, ncols) or out.dtype != x.dtype):
+        raise ValueError(f"out must be [{T}, {ncols}] {x.dtype}")
+    if not _native(x):
+        y = ref.linear(x, unpack_weight_w8(w8, w_scale, x.dtype), epilogue=epilogue)
+        if out is not None:
+            out.copy_(y)
+            return out
+        return y
+    if x.dtype != torch.bfloat16:
+        raise ValueError("x must be bf16")
+    if x.stride(1) != 1 or x.stride(0) % 8 or x.stride(0) < K:
+        raise ValueError("x must have unit inner stride and a row stride that is a multiple of 8")
+    if out is None:
+        out = torch.empty(T, ncols, dtype=x.dtype, device=x.device)
+    torch.ops.mpamd.gemm_w8_rows(x, w8, w_scale, out, int(epilogue))
+    return out
+
+
+# ---------------------------------------------------------------------------------------
 # Grouped W8A16 GEMMs of a sparse-MoE MLP (csrc/gemm_moe.hip): every expert of a layer in two
 # launches.  Weights: the W8A16 layout stacked per expert, uint8 [E, N/16, K/32, 64, 8] + fp32 [E, N];
 # ``cnt`` int32 [E]: tokens routed to each expert (0: the expert is skipped on the device - neither

@@ -32,8 +32,11 @@ EXTRA = os.environ.get("MPAMD_HIPCC_EXTRA", "").split()
 # dwords, and only the pointers and scalars ahead of the first by-value struct)
 PRELOAD = ["-mllvm", "-amdgpu-kernarg-preload-count=16"]
 # per-file device flags.  gemm_moe_rows.hip is built without the packed fp32 VALU forms (v_pk_add_f32,
-# v_pk_mul_f32, v_pk_fma_f32): its fp32 epilogues are scalar per lane
-FILE_FLAGS = {"gemm_moe_rows.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+# v_pk_mul_f32, v_pk_fma_f32): its fp32 epilogues are scalar per lane.  gemm_w8_rows.hip too: without the
+# flag the compiler pairs its accumulator-scale multiplies into v_pk_mul_f32, and the two files' W8A16
+# epilogues are meant to stay the same instruction forms
+_NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+FILE_FLAGS = {"gemm_moe_rows.hip": _NO_PK_F32, "gemm_w8_rows.hip": _NO_PK_F32}
 
 
 def _torch_paths():

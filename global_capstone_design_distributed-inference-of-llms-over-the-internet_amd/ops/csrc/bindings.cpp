@@ -893,6 +893,44 @@ bool moe_rows_ok(int64_t T, int64_t E, int64_t k, int64_t H, int64_t F) {
   return mp_moe_rows_ok((int)T, (int)E, (int)k, (int)H, (int)F) != 0;
 }
 
+// W8A16 GEMM above 64 rows (gemm_w8_rows.hip mp_gemm_w8_rows): x bf16 row-major [T, K] with a row stride,
+// the fp8 weight in place, out bf16 [T, N'] (any row stride).  The messages name the op's arguments.
+void gemm_w8_rows(const at::Tensor& x, const at::Tensor& w8, const at::Tensor& w_scale, at::Tensor& out,
+                  int64_t epilogue) {
+  MP_CHECK(w8.is_cuda() && w8.scalar_type() == at::kByte && w8.dim() == 4 && w8.size(2) == 64 && w8.size(3) == 8 &&
+               w8.is_contiguous(),
+           "linear_w8_rows: w8 must be a contiguous fp8 weight uint8 [N/16, K/32, 64, 8] on the GPU (ops.w8_from_fp8)");
+  const int64_t N = 16 * w8.size(0), K = 32 * w8.size(1);
+  MP_CHECK(w_scale.is_cuda() && w_scale.scalar_type() == at::kFloat && w_scale.is_contiguous() &&
+               w_scale.numel() == N && w_scale.device() == w8.device(),
+           "linear_w8_rows: w_scale must be contiguous fp32 [N] column scales on w8's device");
+  MP_CHECK(epilogue == 0 || epilogue == 1, "linear_w8_rows: epilogue 0 (store) or 1 (SwiGLU)");
+  MP_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16 && x.device() == w8.device(),
+           "linear_w8_rows: x must be bf16 on w8's device");
+  MP_CHECK(x.dim() == 2 && x.size(1) == K, "linear_w8_rows: x must be 2-D [T, K] with K of w8");
+  MP_CHECK(x.stride(1) == 1 && x.stride(0) % 8 == 0 && x.stride(0) >= K &&
+               reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0,
+           "linear_w8_rows: x needs unit inner stride, a row stride that is a multiple of 8 and 16-B alignment");
+  const int64_t T = x.size(0), ncols = epilogue == 1 ? N / 2 : N;
+  MP_CHECK(T < (1ll << 31) && N < (1ll << 31) && K < (1ll << 31), "linear_w8_rows: x / w8 dimensions exceed 32 bits");
+  MP_CHECK(out.is_cuda() && out.scalar_type() == at::kBFloat16 && out.device() == w8.device(),
+           "linear_w8_rows: out must be bf16 on w8's device");
+  MP_CHECK(out.dim() == 2 && out.size(0) == T && out.size(1) == ncols && out.stride(1) == 1 && out.stride(0) >= ncols,
+           "linear_w8_rows: out must be [T, N'] rows with unit inner stride");
+  mp::GemmArgs a = mp::gemm_shape_args((int)T, (int)N, (int)K, (int)epilogue, 0);
+  a.x = x.data_ptr(), a.x_stride = x.stride(0);
+  a.w = w8.data_ptr(), a.wsc = w_scale.data_ptr<float>();
+  a.y = out.data_ptr(), a.y_stride = out.stride(0);
+  const int rc = mp_gemm_w8_rows(&a, cur_stream());
+  TORCH_CHECK(rc != 1, "mpamd: linear_w8_rows: no kernel covers T=", T, " N=", N, " K=", K, " epilogue=", epilogue);
+  check_launch(rc, "gemm_w8_rows");
+}
+
+bool gemm_w8_rows_ok(int64_t T, int64_t N, int64_t K, int64_t epilogue) {
+  if (T <= 0 || N <= 0 || K <= 0 || T >= (1ll << 31) || N >= (1ll << 31) || K >= (1ll << 31)) return false;
+  return mp_gemm_w8_rows_ok((int)T, (int)N, (int)K, (int)epilogue) != 0;
+}
+
 // Batched LoRA (lora.hip): the stacked adapter matrices, the row slots and the fp32 intermediate
 static mp::LoraArgs lora_args(const at::Tensor& mats, const char* name, const at::Tensor& slots, const at::Tensor& t,
                               int64_t M_) {
@@ -1218,6 +1256,8 @@ TORCH_LIBRARY(mpamd, m) {
       "moe_down_w8_rows(Tensor act, Tensor w8, Tensor wsc, Tensor off, Tensor tok, Tensor wsel, Tensor(a!) ws, "
       "Tensor(b!) y) -> ()");
   m.def("moe_rows_ok(int T, int E, int k, int H, int F) -> bool", &moe_rows_ok);
+  m.def("gemm_w8_rows(Tensor x, Tensor w8, Tensor w_scale, Tensor(a!) out, int epilogue) -> ()");
+  m.def("gemm_w8_rows_ok(int T, int N, int K, int epilogue) -> bool", &gemm_w8_rows_ok);
   m.def("lora_shrink(Tensor x, Tensor A, Tensor scale, Tensor slots, Tensor(a!) t, int M) -> ()");
   m.def("lora_expand(Tensor t, Tensor B, Tensor slots, Tensor(a!) y) -> ()");
   m.def("lora_ok(int M, int N, int K, int R) -> bool", &lora_ok);
@@ -1260,6 +1300,7 @@ TORCH_LIBRARY_IMPL(mpamd, CUDA, m) {
   m.impl("moe_group", &moe_group);
   m.impl("moe_gate_up_w8_rows", &moe_gate_up_w8_rows);
   m.impl("moe_down_w8_rows", &moe_down_w8_rows);
+  m.impl("gemm_w8_rows", &gemm_w8_rows);
   m.impl("lora_shrink", &lora_shrink);
   m.impl("lora_expand", &lora_expand);
   m.impl("pack_weight", &pack_weight);

@@ -223,6 +223,11 @@ int mp_moe_down_w8_rows(const void* act, const void* w8, const float* wsc, const
                         const float* wsel, float* ws, void* y, int64_t y_stride, int T, int P, int E, int H, int F,
                         hipStream_t stream);
 int mp_moe_rows_ok(int T, int E, int k, int H, int F);
+// gemm_w8_rows.hip: the W8A16 GEMM above 64 rows on ROW-MAJOR bf16 x (x_stride % 8 == 0): M = T >= 65 rows,
+// N % 16 == 0 (SwiGLU: % 32), K % 128 == 0, epilogue 0 / 1 with row-major output; reads x, x_stride, w, wsc,
+// y, y_stride, M, N, K, epilogue.  0, 1 when the shape is not covered (nothing launched), < 0 for a bad call
+int mp_gemm_w8_rows(const mp::GemmArgs* a, hipStream_t stream);
+int mp_gemm_w8_rows_ok(int T, int N, int K, int epilogue);
 // lora.hip: 0, 1 when the shape is not covered (needs M <= 64, K % 32 == 0, N % 8 == 0, R % 16 == 0,
 // R <= 192; nothing launched), < 0 for a bad call, else the HIP error.  M == 0 returns 0.
 int mp_lora_ok(int M, int N, int K, int R);

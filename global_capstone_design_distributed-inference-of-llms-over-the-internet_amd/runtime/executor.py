@@ -21,7 +21,8 @@ Replaces the reference's Stage0 / StageSegment / StageLast modules
   - "dense": everything else (CPU, prefill, deep prompts, --gemm hipblaslt): those 7 on row-major activations;
     an fp8 Mixtral stage runs the experts of its 65 .. MPAMD_MOE_ROWS-row prefill steps (and, with
     MPAMD_MOE_ROWS_DECODE=1, decode steps) here on the row-gathered grouped kernels (device-side grouping +
-    two launches, ``_moe_mlp``) and dequantizes qkv / o only;
+    two launches, ``_moe_mlp``); the W8A16 projections of a 65 .. MPAMD_W8_ROWS-row step of an fp8 stage
+    (dense Llama: all four; Mixtral: qkv / o) read the fp8 weight in place (``_proj_dense``);
 * decode steps replayed from hipGraphs captured per (batch bucket, context bucket);
 * the last stage applies the final norm and ``lm_head`` to the LAST token of each
   sequence only (the reference projects every prefill position, src/llama_partition.py:470).
@@ -61,6 +62,11 @@ _DENSE_FIELDS = ("input_norm", "post_norm", "qkv", "o", "gate_up", "down", "rout
 # Mixtral-8x7B shapes the kernels win up to 4096 rows and lose at 6144 (profiles/moe_rows/README.md).
 # MPAMD_MOE_ROWS overrides it
 MOE_ROWS_DEFAULT = 4096
+# largest step (rows) whose W8A16 projections (dense fp8 Llama: all four; fp8 Mixtral: qkv / o) run on the
+# in-place fp8 GEMM above 64 rows (ops.linear_w8_rows) instead of dequantizing into a library GEMM:
+# the largest measured row count at which it wins on all four Llama-3-70B projections
+# (profiles/w8_rows/README.md).  MPAMD_W8_ROWS overrides it, 0 turns the route off
+W8_ROWS_DEFAULT = 4096
 _GPT2_FIELDS = ("ln1_w", "ln1_b", "attn_w", "attn_b", "proj_w", "proj_b", "ln2_w", "ln2_b", "fc_w", "fc_b",
                 "fc2_w", "fc2_b")
 
@@ -374,6 +380,11 @@ class StageExecutor:
         # tests/golden/executor_paths - unless MPAMD_MOE_ROWS_DECODE=1 sends them to the same kernels
         self._moe_rows_cap = int(os.environ.get("MPAMD_MOE_ROWS", str(MOE_ROWS_DEFAULT)))
         self._moe_rows_decode = os.environ.get("MPAMD_MOE_ROWS_DECODE", "0") == "1"
+        # W8A16 projections of the row-major path at 65 .. MPAMD_W8_ROWS rows read the fp8 weight in place
+        # (_proj_dense); pure decode steps of 65+ sessions keep their recorded launches unless
+        # MPAMD_W8_ROWS_DECODE=1, the rule of MPAMD_MOE_ROWS_DECODE
+        self._w8_rows_cap = int(os.environ.get("MPAMD_W8_ROWS", str(W8_ROWS_DEFAULT)))
+        self._w8_rows_decode = os.environ.get("MPAMD_W8_ROWS_DECODE", "0") == "1"
         # MXFP4 weights (StageWeights.quantize_mxfp4: norm weights folded in before the one
         # quantization): <= 64-row decode steps run the fused-norm path on ops.linear_w4, everything
         # else dequantizes one projection at a time (LlamaLayer.dense) and normalises with unit weights
@@ -994,6 +1005,21 @@ class StageExecutor:
             self._ar(mlp)
         return res, mlp, None
 
+    def _proj_dense(self, st: _Step, L, name: str, x, out, wdt=torch.bfloat16, **kw):
+        """Projection ``name`` of layer ``L`` on the row-major path.  A W8A16 layer's weight is read in place
+        by ``ops.linear_w8_rows`` on a GPU step of 65 .. MPAMD_W8_ROWS rows (not a pure decode step unless
+        MPAMD_W8_ROWS_DECODE=1; never under TP, offload or --gemm hipblaslt); everything else dequantizes
+        the projection (``L.dense``) into ``ops.linear(x, w, out=out, **kw)``.  ``kw``: ``epilogue`` (0 / 1)
+        and ``wp``, the packed bf16 copy, which a W8A16 layer does not have and the in-place route ignores."""
+        epilogue = kw.get("epilogue", 0)
+        if (L.w8 and self.device.type == "cuda" and 64 < st.T <= self._w8_rows_cap and
+                (not st.decode or self._w8_rows_decode) and self._tp is None and self._streamer is None and
+                ops.gemm_policy() != "hipblaslt"):
+            w8 = getattr(L, name + "_w8")
+            if ops.w8_rows_ok(st.T, 16 * w8.shape[0], 32 * w8.shape[1], epilogue):
+                return ops.linear_w8_rows(x, w8, getattr(L, name + "_ws"), out=out, epilogue=epilogue)
+        return ops.linear(x, L.dense(name, wdt), out=out, **kw)
+
     def _layers_dense(self, st: _Step):
         """Row-major path: any row count, any device; deep prompts, and LoRA steps with the torch form of
         the update by runs of rows (``ops.lora_update``)."""
@@ -1028,12 +1054,12 @@ class StageExecutor:
                 ops.rmsnorm(h if li == 0 else mlp, g_in, eps, out=xn, residual=res, mode=2 if li == 0 else 1)
             # (fp8 MoE layers dequantize into the executor's dtype: an fp32 CPU stage stays fp32)
             wdt = self.dtype if L.moe else torch.bfloat16
-            ops.linear(xn, L.dense("qkv", wdt), out=qkv, wp=qkv_p)
+            self._proj_dense(st, L, "qkv", xn, qkv, wdt, wp=qkv_p)
             if LL.qkv is not None:
                 ops.lora_update(xn, qkv, LL.qkv.A, LL.qkv.B, lo.scale, runs)
             kc, vc = self.cache.layer(li)
             self._rope_attend(st, qkv, kc, vc, attn, False)
-            ops.linear(attn, L.dense("o", wdt), out=o, wp=L.o_p)
+            self._proj_dense(st, L, "o", attn, o, wdt, wp=L.o_p)
             if LL.o is not None:
                 ops.lora_update(attn, o, LL.o.A, LL.o.B, lo.scale, runs)
             self._ar(o)
@@ -1042,12 +1068,12 @@ class StageExecutor:
                 self._moe_mlp(st, L, xn, mlp, act, packed=False)
                 continue
             if LL.gate_up is not None:  # epilogue 0, the update, then SwiGLU
-                gu = ops.linear(xn, L.dense("gate_up"), out=st.buf("gu", (T, 2 * F)), wp=gu_p)
+                gu = self._proj_dense(st, L, "gate_up", xn, st.buf("gu", (T, 2 * F)), wp=gu_p)
                 ops.lora_update(xn, gu, LL.gate_up.A, LL.gate_up.B, lo.scale, runs)
                 ops.swiglu(gu, out=act)
             else:
-                ops.linear(xn, L.dense("gate_up"), out=act, epilogue=1, wp=gu_p)
-            ops.linear(act, L.dense("down"), out=mlp, wp=L.down_p)
+                self._proj_dense(st, L, "gate_up", xn, act, epilogue=1, wp=gu_p)
+            self._proj_dense(st, L, "down", act, mlp, wp=L.down_p)
             if LL.down is not None:
                 ops.lora_update(act, mlp, LL.down.A, LL.down.B, lo.scale, runs)
             self._ar(mlp)
