@@ -1849,7 +1849,8 @@ def linear_w4(x, w4, s4, a_rows: int, out=None, epilogue: int = 0, residual=None
     with optional ``ss_in`` row scale, packed SwiGLU, 3 = residual-stream producer).  A shape the
     kernel does not cover raises.  Out of scope for 4-bit weights: the split-K ring,
     ``linear_partials`` / the qkv fold, a start-up autotuner, W4A8 / W4A4 on the block-scaled
-    MFMA, and MoE / tensor-parallel / offloaded stages."""
+    MFMA, and MoE / tensor-parallel / offloaded stages.  Steps above 64 rows: ``linear_w4_rows``
+    (row-major activations, epilogue 0 / SwiGLU); the fused-norm epilogues stop at 64 rows."""
     M = int(a_rows)
     N, K = 16 * w4.shape[0], 128 * w4.shape[1]
     if not _native(x):
@@ -1861,6 +1862,57 @@ def linear_w4(x, w4, s4, a_rows: int, out=None, epilogue: int = 0, residual=None
         out = _gemm_out(M, ncols, out_packed, x.dtype, x.device)
     torch.ops.mpamd.gemm_w4(x, w4, s4, out, residual, int(epilogue), M, 1 | (2 if out_packed else 0), ap_out, ss_out,
                             ss_zero, ss_in, 1.0 / K, float(eps))
+    return out
+
+
+# ---------------------------------------------------------------------------------------
+# W4A16 GEMM ABOVE 64 rows (csrc/gemm_w4_rows.hip mp_gemm_w4_rows): row-major bf16 activations with a row
+# stride, the MXFP4 codes and block scales read in place (no dequantized copy), gemm_w8_rows.hip's
+# two-dimensional split; epilogue 0 or SwiGLU, row-major output.
+_W4_ROWS_OK = {}
+
+
+def w4_rows_ok(T: int, N: int, K: int, epilogue: int = 0) -> bool:
+    """Whether ``linear_w4_rows`` has a kernel for the shape: T >= 65, N % 16 == 0 (SwiGLU: % 32),
+    K % 128 == 0 (a dry dispatch, as ``w8_rows_ok``)."""
+    key = (int(T), int(N), int(K), int(epilogue))
+    if key not in _W4_ROWS_OK:
+        _W4_ROWS_OK[key] = bool(native_available() and torch.ops.mpamd.gemm_w4_rows_ok(*key))
+    return _W4_ROWS_OK[key]
+
+
+def linear_w4_rows(x, w4, s4, out=None, epilogue: int = 0):
+    """y [T, N'] = epilogue(x @ W^T) for row-major ``x`` [T, K] (unit inner stride, row stride % 8 == 0) and an
+    MXFP4 weight (``pack_weight_w4``: codes + e8m0 block scales); epilogue 0 (N' = N) or 1 (SwiGLU over the
+    16-row gate/up interleave, N' = N / 2).  The block scales are applied by the convert (exact bf16 values),
+    fp32 accumulation, one rounding to bf16, the same bits on every run.  ``out``: any [T, N'] view with unit
+    inner stride.  An uncovered shape is an error on the GPU (``w4_rows_ok``); CPU tensors run
+    ``reference.linear`` on the dequantized weight."""
+    if w4.dim() != 4 or tuple(w4.shape[2:]) != (64, 16) or w4.dtype != torch.uint8:
+        raise ValueError("w4 must be an MXFP4 weight uint8 [N/16, K/128, 64, 16] (ops.pack_weight_w4)")
+    N, K = 16 * w4.shape[0], 128 * w4.shape[1]
+    if tuple(s4.shape) != (N // 16, K // 128, 16, 4) or s4.dtype != torch.uint8:
+        raise ValueError(f"s4 must be the e8m0 block scales uint8 [{N // 16}, {K // 128}, 16, 4]")
+    if epilogue not in (0, 1):
+        raise ValueError("linear_w4_rows: epilogue 0 (store) or 1 (SwiGLU)")
+    if x.dim() != 2 or x.shape[1] != K:
+        raise ValueError(f"x must be row-major [T, {K}]")
+    T, ncols = x.shape[0], N // 2 if epilogue == 1 else N
+    if out is not None and (tuple(out.shape) != (T, ncols) or out.dtype != x.dtype):
+        raise ValueError(f"out must be [{T}, {ncols}] {x.dtype}")
+    if not _native(x):
+        y = ref.linear(x, unpack_weight_w4(w4, s4, x.dtype), epilogue=epilogue)
+        if out is not None:
+            out.copy_(y)
+            return out
+        return y
+    if x.dtype != torch.bfloat16:
+        raise ValueError("x must be bf16")
+    if x.stride(1) != 1 or x.stride(0) % 8 or x.stride(0) < K:
+        raise ValueError("x must have unit inner stride and a row stride that is a multiple of 8")
+    if out is None:
+        out = torch.empty(T, ncols, dtype=x.dtype, device=x.device)
+    torch.ops.mpamd.gemm_w4_rows(x, w4, s4, out, int(epilogue))
     return out
 
 

@@ -47,26 +47,9 @@
 //
 // Deterministic: no atomics, no k split, every wave walks K upwards.  Nothing outside x[0:T, 0:K], the
 // weight, the scales and y[0:T, 0:N'] is touched.  Registers / LDS / scratch: profiles/w8_rows/README.md.
-#include "gemm_kernels.h"
+#include "gemm_rows_plan.h"  // W8R_LDS_BYTES, w8r_place, W8rPlan, w8r_plan: shared with gemm_w4_rows.hip
 
 namespace mp {
-
-constexpr int W8R_LDS_BYTES = 160 * 1024;  // gemm_t2d.h's workgroup budget
-
-// blockIdx -> (column group, row block), gemm_t2d.h's t2d_place without a k split: the MB row blocks of one
-// column group share blockIdx % 8 (one XCD under round-robin dispatch) when the grid allows it.
-// Placement only - never correctness.
-__device__ __forceinline__ void w8r_place(int MB, int& cg, int& mb) {
-  const int b = blockIdx.x, G = gridDim.x;
-  if (G % (8 * MB) == 0) {
-    const int j = b >> 3;
-    mb = j % MB;
-    cg = (j / MB) * 8 + (b & 7);
-  } else {
-    mb = b % MB;
-    cg = b / MB;
-  }
-}
 
 template <int MW, int NW, int WM, int WN, int KU>
 struct W8rGeom {
@@ -202,33 +185,6 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_w8_rows_kernel(const bf16_t*
         y[(int64_t)row * ys + col] = f2bf(v);
       }
     }
-}
-
-// The geometry and column split of a shape (the RULE of the header).  False: not covered.
-struct W8rPlan {
-  int wide, MB, NB, nbig, NBB, NBS;
-};
-static bool w8r_plan(int T, int N, int K, int epi, W8rPlan& p) {
-  if (epi != 0 && epi != 1) return false;
-  const int step = epi == 1 ? 2 : 1;
-  if (T < 65 || N <= 0 || K <= 0 || N % (16 * step) || K % 128) return false;
-  const int units = (N / 16) / step;
-  p.wide = T > 128;
-  const int cap = (p.wide ? 16 : 4) / step;  // units a workgroup can hold
-  p.MB = (T + 127) / 128;
-  int want = sk_num_cus() / p.MB;            // groups for one workgroup per CU
-  const int need = (units + cap - 1) / cap;
-  if (want < need) want = need;
-  p.NB = units < want ? units : want;
-  if (p.NB > 8 && p.NB % 8) {  // whole XCD rounds (w8r_place)
-    const int up = (p.NB + 7) / 8 * 8, down = p.NB / 8 * 8;
-    if (up <= units) p.NB = up; else if (down >= need) p.NB = down;
-  }
-  const int base = units / p.NB, rem = units % p.NB;
-  p.NBB = (base + (rem ? 1 : 0)) * step;
-  p.NBS = base * step;
-  p.nbig = rem ? rem : p.NB;
-  return (int64_t)p.NB * p.MB < (1ll << 31);
 }
 
 template <int MW, int NW, int WM, int WN, int KU>

@@ -228,6 +228,10 @@ int mp_moe_rows_ok(int T, int E, int k, int H, int F);
 // y, y_stride, M, N, K, epilogue.  0, 1 when the shape is not covered (nothing launched), < 0 for a bad call
 int mp_gemm_w8_rows(const mp::GemmArgs* a, hipStream_t stream);
 int mp_gemm_w8_rows_ok(int T, int N, int K, int epilogue);
+// gemm_w4_rows.hip: its W4A16 counterpart - the same x, shapes, epilogues and return codes; w the MXFP4 codes
+// and wsc the e8m0 block scales s4, as mp_gemm_w4 takes them
+int mp_gemm_w4_rows(const mp::GemmArgs* a, hipStream_t stream);
+int mp_gemm_w4_rows_ok(int T, int N, int K, int epilogue);
 // lora.hip: 0, 1 when the shape is not covered (needs M <= 64, K % 32 == 0, N % 8 == 0, R % 16 == 0,
 // R <= 192; nothing launched), < 0 for a bad call, else the HIP error.  M == 0 returns 0.
 int mp_lora_ok(int M, int N, int K, int R);

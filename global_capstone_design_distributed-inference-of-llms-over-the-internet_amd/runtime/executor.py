@@ -22,7 +22,10 @@ Replaces the reference's Stage0 / StageSegment / StageLast modules
     an fp8 Mixtral stage runs the experts of its 65 .. MPAMD_MOE_ROWS-row prefill steps (and, with
     MPAMD_MOE_ROWS_DECODE=1, decode steps) here on the row-gathered grouped kernels (device-side grouping +
     two launches, ``_moe_mlp``); the W8A16 projections of a 65 .. MPAMD_W8_ROWS-row step of an fp8 stage
-    (dense Llama: all four; Mixtral: qkv / o) read the fp8 weight in place (``_proj_dense``);
+    (dense Llama: all four; Mixtral: qkv / o) read the fp8 weight in place (``_proj_dense``), and so do the
+    four projections of a 65 .. MPAMD_W4_ROWS-row step of a dense MXFP4 stage (``ops.linear_w4_rows``; above
+    the cap, and under TP / offload / --gemm hipblaslt, an MXFP4 stage still dequantizes one projection at
+    a time);
 * decode steps replayed from hipGraphs captured per (batch bucket, context bucket);
 * the last stage applies the final norm and ``lm_head`` to the LAST token of each
   sequence only (the reference projects every prefill position, src/llama_partition.py:470).
@@ -67,6 +70,13 @@ MOE_ROWS_DEFAULT = 4096
 # the largest measured row count at which it wins on all four Llama-3-70B projections
 # (profiles/w8_rows/README.md).  MPAMD_W8_ROWS overrides it, 0 turns the route off
 W8_ROWS_DEFAULT = 4096
+# the same for the four projections of a dense MXFP4 Llama stage (ops.linear_w4_rows instead of the HIP
+# dequantizer + a library GEMM), by the same rule: the largest measured row count at which the in-place
+# kernel's slowest round beats the partner's fastest on all four projections of Llama-2-7B and Llama-3-70B.
+# There is none (profiles/w4_rows/README.md: the 7B down projection loses at 65 rows already, the HIP
+# dequantizer being far cheaper than the torch chain the fp8 route replaced), so the route is OFF by default
+# and MPAMD_W4_ROWS=<rows> opts in
+W4_ROWS_DEFAULT = 0
 _GPT2_FIELDS = ("ln1_w", "ln1_b", "attn_w", "attn_b", "proj_w", "proj_b", "ln2_w", "ln2_b", "fc_w", "fc_b",
                 "fc2_w", "fc2_b")
 
@@ -385,9 +395,14 @@ class StageExecutor:
         # MPAMD_W8_ROWS_DECODE=1, the rule of MPAMD_MOE_ROWS_DECODE
         self._w8_rows_cap = int(os.environ.get("MPAMD_W8_ROWS", str(W8_ROWS_DEFAULT)))
         self._w8_rows_decode = os.environ.get("MPAMD_W8_ROWS_DECODE", "0") == "1"
+        # ... and the projections of an MXFP4 stage at 65 .. MPAMD_W4_ROWS rows read the codes and block
+        # scales in place, under the same rule for pure decode steps (MPAMD_W4_ROWS_DECODE)
+        self._w4_rows_cap = int(os.environ.get("MPAMD_W4_ROWS", str(W4_ROWS_DEFAULT)))
+        self._w4_rows_decode = os.environ.get("MPAMD_W4_ROWS_DECODE", "0") == "1"
         # MXFP4 weights (StageWeights.quantize_mxfp4: norm weights folded in before the one
-        # quantization): <= 64-row decode steps run the fused-norm path on ops.linear_w4, everything
-        # else dequantizes one projection at a time (LlamaLayer.dense) and normalises with unit weights
+        # quantization): <= 64-row decode steps run the fused-norm path on ops.linear_w4, steps of
+        # 65 .. MPAMD_W4_ROWS rows the in-place GEMM (_proj_dense), everything else dequantizes one
+        # projection at a time (LlamaLayer.dense); both normalise with unit weights
         self._w4 = bool(self.device.type == "cuda" and weights.w4 and cfg.model_type != "gpt2" and
                         not cfg.is_moe and self._tp is None)
         if weights.w4 and self._tp is not None:
@@ -1008,7 +1023,8 @@ class StageExecutor:
     def _proj_dense(self, st: _Step, L, name: str, x, out, wdt=torch.bfloat16, **kw):
         """Projection ``name`` of layer ``L`` on the row-major path.  A W8A16 layer's weight is read in place
         by ``ops.linear_w8_rows`` on a GPU step of 65 .. MPAMD_W8_ROWS rows (not a pure decode step unless
-        MPAMD_W8_ROWS_DECODE=1; never under TP, offload or --gemm hipblaslt); everything else dequantizes
+        MPAMD_W8_ROWS_DECODE=1; never under TP, offload or --gemm hipblaslt), an MXFP4 layer's by
+        ``ops.linear_w4_rows`` under MPAMD_W4_ROWS / MPAMD_W4_ROWS_DECODE in the same way; everything else dequantizes
         the projection (``L.dense``) into ``ops.linear(x, w, out=out, **kw)``.  ``kw``: ``epilogue`` (0 / 1)
         and ``wp``, the packed bf16 copy, which a W8A16 layer does not have and the in-place route ignores."""
         epilogue = kw.get("epilogue", 0)
@@ -1018,6 +1034,12 @@ class StageExecutor:
             w8 = getattr(L, name + "_w8")
             if ops.w8_rows_ok(st.T, 16 * w8.shape[0], 32 * w8.shape[1], epilogue):
                 return ops.linear_w8_rows(x, w8, getattr(L, name + "_ws"), out=out, epilogue=epilogue)
+        if (L.w4 and self.device.type == "cuda" and 64 < st.T <= self._w4_rows_cap and
+                (not st.decode or self._w4_rows_decode) and self._tp is None and self._streamer is None and
+                ops.gemm_policy() != "hipblaslt"):
+            w4 = getattr(L, name + "_w4")
+            if ops.w4_rows_ok(st.T, 16 * w4.shape[0], 128 * w4.shape[1], epilogue):
+                return ops.linear_w4_rows(x, w4, getattr(L, name + "_s4"), out=out, epilogue=epilogue)
         return ops.linear(x, L.dense(name, wdt), out=out, **kw)
 
     def _layers_dense(self, st: _Step):

@@ -27,6 +27,8 @@ def main():
     ap.add_argument("--prompt-len", type=int, default=2048)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--fp8", action="store_true")
+    ap.add_argument("--quant_type", default="none", choices=["none", "fp8", "mxfp4"],
+                    help="weight format (--fp8 is the older spelling of fp8); mxfp4: MPAMD_W4_ROWS sets the route")
     ap.add_argument("--kv_cache_dtype", default="bf16", choices=["bf16", "fp8"])
     ap.add_argument("--sliding_window", default="cap", choices=["cap", "attend"],
                     help="models with a sliding window: attend = the prompt may pass it (windowed rows)")
@@ -39,7 +41,7 @@ def main():
     dev = torch.device("cuda:0")
     cfg = resolve_model(a.model)
     L = cfg.num_hidden_layers
-    w = random_stage_weights(cfg, 0, L, has_embed=True, has_head=True, device=dev, fp8=a.fp8)
+    w = random_stage_weights(cfg, 0, L, has_embed=True, has_head=True, device=dev, fp8=a.fp8, quant_type=a.quant_type)
     T = a.batch * a.prompt_len
     ex = StageExecutor(cfg, w, dev, max_sessions=a.batch + 4, max_seq_len=a.prompt_len + 64,
                        kv_cache_bytes=16 << 30, max_tokens_per_step=T,
@@ -61,8 +63,8 @@ def main():
     proj = L * (H * (cfg.q_dim + 2 * cfg.kv_dim) + cfg.q_dim * H + 3 * H * F)
     attn = L * 2 * a.batch * cfg.num_attention_heads * cfg.head_dim * a.prompt_len * (a.prompt_len + 1)
     flops = 2 * proj * T + attn + 2 * H * cfg.vocab_size * a.batch
-    print(json.dumps({"model": a.model, "kv_cache_dtype": a.kv_cache_dtype, "sliding_window": a.sliding_window,
-                      "window": ex.window, "batch": a.batch, "prompt_len": a.prompt_len, "tokens": T,
+    print(json.dumps({"model": a.model, "quant_type": ex.quant_type, "w4_rows": os.environ.get("MPAMD_W4_ROWS"),
+                      "kv_cache_dtype": a.kv_cache_dtype, "sliding_window": a.sliding_window, "window": ex.window, "batch": a.batch, "prompt_len": a.prompt_len, "tokens": T,
                       "cold_s": round(times[0], 4), "warm_s": round(warm, 4),
                       "warm_all_s": [round(t, 5) for t in times[1:]],
                       "warm_tokens_per_s": round(T / warm, 1), "warm_tflops": round(flops / warm / 1e12, 1)}),
