@@ -2118,3 +2118,71 @@ def lora_update(x, y, A, B, scale, runs):
         t = scale[s] * (x[r0:r1].float() @ A[s].float().t())
         y[r0:r1] = (y[r0:r1].float() + t @ B[s].float().t()).to(y.dtype)
     return y
+
+
+# The same two steps ABOVE 64 rows (csrc/lora_rows.hip): row-major ``x`` [T, K] and ``y`` [T, N] (unit inner
+# stride, a row stride that is a multiple of 8; ``y`` may be a column slice of a wider buffer), the slots on
+# the device, any T.  A 16-row tile runs one pass per distinct slot among its rows, so the launches do not
+# depend on how many sessions the step holds; the semantics and guarantees are those above.
+_LORA_ROWS_OK = {}
+
+
+def lora_rows_ok(T: int, N: int, K: int, R: int) -> bool:
+    """Whether the two kernels cover the shape: T >= 1, K % 32 == 0, N % 16 == 0, R % 16 == 0, R <= 192
+    (a dry dispatch where the library is loaded, as ``lora_ok``)."""
+    key = (int(T), int(N), int(K), int(R))
+    if key[1:] not in _LORA_ROWS_OK:  # (the row count only has to be positive)
+        if native_available():
+            _LORA_ROWS_OK[key[1:]] = bool(torch.ops.mpamd.lora_rows_ok(1, *key[1:]))
+        else:
+            _LORA_ROWS_OK[key[1:]] = bool(key[1] > 0 and key[1] % 16 == 0 and key[2] > 0 and key[2] % 32 == 0 and
+                                          0 < key[3] <= 192 and key[3] % 16 == 0)
+    return key[0] >= 1 and _LORA_ROWS_OK[key[1:]]
+
+
+def _lora_row_major(v: torch.Tensor, name: str, cols: int, like: torch.Tensor):
+    if v.dim() != 2 or v.shape[1] != cols or v.stride(1) != 1 or v.stride(0) % 8 != 0 or v.dtype != like.dtype:
+        raise ValueError(f"{name} must be [T, {cols}] rows of the adapters' dtype with unit inner stride and a row "
+                         f"stride that is a multiple of 8")
+
+
+def lora_shrink_rows(x, A, scale, slots, out=None):
+    """t fp32 [T, R] from row-major ``x`` [T, K].  Rows with slot -1 are not written (``out`` keeps what it
+    held; a fresh one holds zeros)."""
+    T = int(x.shape[0])
+    if out is None:
+        out = torch.zeros(T, A.shape[1] if A.dim() == 3 else 0, dtype=torch.float32, device=A.device)
+    S, R, K = _lora_dims(A, "A", slots, out, T)
+    if scale.dtype != torch.float32 or scale.numel() != S:
+        raise ValueError(f"scale must be fp32 [{S}]")
+    _lora_row_major(x, "x", K, A)
+    if T == 0:
+        return out
+    if not _native(x):
+        for m, s in zip(*map(torch.Tensor.tolist, _lora_rows(slots, T, S))):  # row by row, as ``lora_shrink``
+            out[m] = scale[s] * torch.mv(A[s].float(), x[m].float())
+        return out
+    torch.ops.mpamd.lora_shrink_rows(x, A, scale, slots, out)
+    return out
+
+
+def lora_expand_rows(t, B, slots, y):
+    """``y`` [T, N] updated in place from ``t`` fp32 [T, R]."""
+    T = int(y.shape[0])
+    S, N, R = _lora_dims(B, "B", slots, t, T)
+    _lora_row_major(y, "y", N, B)
+    if T == 0:
+        return y
+    if not _native(y):
+        for m, s in zip(*map(torch.Tensor.tolist, _lora_rows(slots, T, S))):
+            y[m] = (y[m].float() + torch.mv(B[s].float(), t[m])).to(y.dtype)
+        return y
+    torch.ops.mpamd.lora_expand_rows(t, B, slots, y)
+    return y
+
+
+def lora_update_rows(x, y, A, B, scale, slots, t=None):
+    """The whole update, ``y += B[s] (scale[s] A[s] x)`` for every row with a slot: shrink, then expand, on a
+    caller-supplied or fresh ``t`` fp32 [T, R].  Two launches, whatever the number of runs."""
+    t = lora_shrink_rows(x, A, scale, slots, out=t)
+    return lora_expand_rows(t, B, slots, y)

@@ -933,8 +933,8 @@ bool gemm_w8_rows_ok(int64_t T, int64_t N, int64_t K, int64_t epilogue) {
 
 // Batched LoRA (lora.hip): the stacked adapter matrices, the row slots and the fp32 intermediate
 static mp::LoraArgs lora_args(const at::Tensor& mats, const char* name, const at::Tensor& slots, const at::Tensor& t,
-                              int64_t M_) {
-  MP_CHECK(M_ >= 0 && M_ <= (1 << 20), "lora: M out of range");
+                              int64_t M_, int64_t max_m = 1 << 20) {
+  MP_CHECK(M_ >= 0 && M_ <= max_m, "lora: M out of range");
   const int M = (int)M_;
   check_bf16_cuda(mats, name);
   MP_CHECK(mats.dim() == 3 && mats.size(0) >= 1 && mats.stride(2) == 1 && mats.stride(1) == mats.size(2) &&
@@ -991,6 +991,54 @@ void lora_expand(const at::Tensor& t, const at::Tensor& B, const at::Tensor& slo
 }
 
 bool lora_ok(int64_t M, int64_t N, int64_t K, int64_t R) { return mp_lora_ok((int)M, (int)N, (int)K, (int)R) != 0; }
+
+// The same two steps above 64 rows (lora_rows.hip): x bf16 rows [T, K] with a row stride, any T that fits 31 bits
+constexpr int64_t LORA_ROWS_MAX_T = (1ll << 31) - 16;
+
+// t[m] = scale[s] * (A[s] x[m]) for the rows with s = slots[m] in [0, S) (mp_lora_shrink_rows)
+void lora_shrink_rows(const at::Tensor& x, const at::Tensor& A, const at::Tensor& scale, const at::Tensor& slots,
+                      at::Tensor& t) {
+  check_bf16_cuda(x, "x");
+  check_rows(x, "x");
+  mp::LoraArgs a = lora_args(A, "A", slots, t, x.size(0), LORA_ROWS_MAX_T);
+  MP_CHECK(A.size(1) == a.R, "A: [S, R, K] with R = t.size(1)");
+  MP_CHECK(x.size(1) == A.size(2) && x.stride(0) >= x.size(1) && x.device() == A.device(),
+           "x: [T, K] rows with K = A.size(2)");
+  MP_CHECK(A.size(2) < (1ll << 31), "A: K exceeds 32 bits");
+  a.K = (int)A.size(2);
+  a.A = A.data_ptr(), a.a_stride = A.stride(0);
+  MP_CHECK(scale.is_cuda() && scale.scalar_type() == at::kFloat && scale.is_contiguous() && scale.numel() == a.S &&
+               scale.device() == A.device(),
+           "scale: fp32 [S]");
+  a.x = x.data_ptr(), a.x_stride = x.stride(0), a.scale = scale.data_ptr<float>();
+  const int rc = mp_lora_shrink_rows(&a, cur_stream());
+  TORCH_CHECK(rc != 1, "mpamd: lora_shrink_rows: no kernel covers T=", a.M, " K=", a.K, " R=", a.R);
+  check_launch(rc, "lora_shrink_rows");
+}
+
+// y[m] = bf16(y[m] + B[s] t[m]) in place for the same rows (mp_lora_expand_rows)
+void lora_expand_rows(const at::Tensor& t, const at::Tensor& B, const at::Tensor& slots, at::Tensor& y) {
+  check_bf16_cuda(y, "y");
+  check_rows(y, "y");
+  mp::LoraArgs a = lora_args(B, "B", slots, t, y.size(0), LORA_ROWS_MAX_T);
+  MP_CHECK(B.size(2) == a.R, "B: [S, N, R] with R = t.size(1)");
+  MP_CHECK(y.size(1) == B.size(1) && y.stride(0) >= y.size(1) && y.device() == B.device(),
+           "y: [T, N] rows with N = B.size(1)");
+  MP_CHECK(B.size(1) < (1ll << 31), "B: N exceeds 32 bits");
+  a.N = (int)B.size(1);
+  a.B = B.data_ptr(), a.b_stride = B.stride(0);
+  a.y = y.data_ptr(), a.y_stride = y.stride(0);
+  const int rc = mp_lora_expand_rows(&a, cur_stream());
+  TORCH_CHECK(rc != 1, "mpamd: lora_expand_rows: no kernel covers T=", a.M, " N=", a.N, " R=", a.R);
+  check_launch(rc, "lora_expand_rows");
+}
+
+bool lora_rows_ok(int64_t T, int64_t N, int64_t K, int64_t R) {
+  if (T <= 0 || T > LORA_ROWS_MAX_T || N <= 0 || K <= 0 || R <= 0 || N >= (1ll << 31) || K >= (1ll << 31) ||
+      R >= (1ll << 31))
+    return false;
+  return mp_lora_rows_ok((int)T, (int)N, (int)K, (int)R) != 0;
+}
 
 // MXFP4 weight operands (gemm_w4.hip): codes uint8 [N/16, K/128, 64, 16] + e8m0 scales uint8 [N/16, K/128, 16, 4]
 static void check_w4(const at::Tensor& w4, const at::Tensor& s4) {
@@ -1304,6 +1352,9 @@ TORCH_LIBRARY(mpamd, m) {
   m.def("lora_shrink(Tensor x, Tensor A, Tensor scale, Tensor slots, Tensor(a!) t, int M) -> ()");
   m.def("lora_expand(Tensor t, Tensor B, Tensor slots, Tensor(a!) y) -> ()");
   m.def("lora_ok(int M, int N, int K, int R) -> bool", &lora_ok);
+  m.def("lora_shrink_rows(Tensor x, Tensor A, Tensor scale, Tensor slots, Tensor(a!) t) -> ()");
+  m.def("lora_expand_rows(Tensor t, Tensor B, Tensor slots, Tensor(a!) y) -> ()");
+  m.def("lora_rows_ok(int T, int N, int K, int R) -> bool", &lora_rows_ok);
   m.def("pack_act(Tensor x, Tensor(a!) ap) -> ()");
   m.def("pack_weight(Tensor w) -> Tensor");
   m.def("quant_act_fp8(Tensor ap, Tensor(a!) a8, Tensor(b!) scale, int M, int K) -> ()");
@@ -1347,6 +1398,8 @@ TORCH_LIBRARY_IMPL(mpamd, CUDA, m) {
   m.impl("gemm_w4_rows", &gemm_w4_rows);
   m.impl("lora_shrink", &lora_shrink);
   m.impl("lora_expand", &lora_expand);
+  m.impl("lora_shrink_rows", &lora_shrink_rows);
+  m.impl("lora_expand_rows", &lora_expand_rows);
   m.impl("pack_weight", &pack_weight);
   m.impl("pack_act", &pack_act);
   m.impl("quant_act_fp8", &quant_act_fp8);

@@ -130,10 +130,11 @@ inline GemmArgs gemm_shape_args(int M, int N, int K, int epilogue, int flags) {
   return a;
 }
 
-// What both batched-LoRA launchers take (lora.hip).  Row m belongs to adapter slot slots[m] in
+// What the batched-LoRA launchers take (lora.hip, lora_rows.hip).  Row m belongs to adapter slot slots[m] in
 // [-1, S); a row with slot -1 is a base-model row: nothing of it is read or written.
 struct LoraArgs {
-  const void* x;                   // shrink: packed bf16 activation (apk_off, common.h), M rows of K
+  const void* x;                   // shrink: packed bf16 activation (apk_off, common.h), M rows of K;
+                                   // lora_rows.hip: bf16 rows [M, K], x_stride elements apart
   const void* A;                   // shrink: bf16 [S, R, K], slot s at A + s * a_stride elements
   int64_t a_stride;
   const void* B;                   // expand: bf16 [S, N, R], slot s at B + s * b_stride elements
@@ -144,6 +145,7 @@ struct LoraArgs {
   void* y;                         // expand: bf16 rows [M, N], updated in place
   int64_t y_stride;
   int M, N, K, R, S;               // shrink ignores N, expand ignores K
+  int64_t x_stride;                // lora_rows.hip only (a multiple of 8)
 };
 
 }  // namespace mp
@@ -237,6 +239,11 @@ int mp_gemm_w4_rows_ok(int T, int N, int K, int epilogue);
 int mp_lora_ok(int M, int N, int K, int R);
 int mp_lora_shrink(const mp::LoraArgs* a, hipStream_t stream);
 int mp_lora_expand(const mp::LoraArgs* a, hipStream_t stream);
+// lora_rows.hip: the same two steps on row-major x (x_stride) for any M >= 1 - the steps above 64 rows; needs
+// K % 32 == 0, N % 16 == 0, R % 16 == 0, R <= 192.  The same return codes.
+int mp_lora_rows_ok(int T, int N, int K, int R);
+int mp_lora_shrink_rows(const mp::LoraArgs* a, hipStream_t stream);
+int mp_lora_expand_rows(const mp::LoraArgs* a, hipStream_t stream);
 // fp8.hip
 void mp_fp8_set_kernel(int kind);
 int mp_quant_act_fp8(const void* ap, void* a8, float* scale, float* part, int M, int K, hipStream_t stream);

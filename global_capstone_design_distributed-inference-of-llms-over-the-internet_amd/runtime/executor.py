@@ -25,7 +25,9 @@ Replaces the reference's Stage0 / StageSegment / StageLast modules
     (dense Llama: all four; Mixtral: qkv / o) read the fp8 weight in place (``_proj_dense``), and so do the
     four projections of a 65 .. MPAMD_W4_ROWS-row step of a dense MXFP4 stage (``ops.linear_w4_rows``; above
     the cap, and under TP / offload / --gemm hipblaslt, an MXFP4 stage still dequantizes one projection at
-    a time);
+    a time); a LoRA step of 65 .. MPAMD_LORA_ROWS rows (prompts, chunks, mixed and verify steps; decode steps
+    with MPAMD_LORA_ROWS_DECODE=1) runs every targeted projection's update as two launches that read the row
+    slots on the device (``_lora_dense``, ``ops.lora_update_rows``) instead of a torch loop over runs;
 * decode steps replayed from hipGraphs captured per (batch bucket, context bucket);
 * the last stage applies the final norm and ``lm_head`` to the LAST token of each
   sequence only (the reference projects every prefill position, src/llama_partition.py:470).
@@ -77,6 +79,11 @@ W8_ROWS_DEFAULT = 4096
 # dequantizer being far cheaper than the torch chain the fp8 route replaced), so the route is OFF by default
 # and MPAMD_W4_ROWS=<rows> opts in
 W4_ROWS_DEFAULT = 0
+# largest LoRA step (rows) whose updates run on the segmented MFMA kernels above 64 rows (ops.lora_update_rows)
+# instead of the torch form by runs (ops.lora_update), by the same rule on the four Llama-2-7B projections
+# at r = 16, one adapter and 64 sessions' runs (profiles/lora_rows/README.md).  MPAMD_LORA_ROWS overrides it,
+# 0 keeps the torch form everywhere
+LORA_ROWS_DEFAULT = 8192
 _GPT2_FIELDS = ("ln1_w", "ln1_b", "attn_w", "attn_b", "proj_w", "proj_b", "ln2_w", "ln2_b", "fc_w", "fc_b",
                 "fc2_w", "fc2_b")
 
@@ -399,6 +406,10 @@ class StageExecutor:
         # scales in place, under the same rule for pure decode steps (MPAMD_W4_ROWS_DECODE)
         self._w4_rows_cap = int(os.environ.get("MPAMD_W4_ROWS", str(W4_ROWS_DEFAULT)))
         self._w4_rows_decode = os.environ.get("MPAMD_W4_ROWS_DECODE", "0") == "1"
+        # ... and the LoRA updates of a 65 .. MPAMD_LORA_ROWS-row step run as two launches per projection
+        # (_lora_rows), pure decode steps keeping their recorded torch form unless MPAMD_LORA_ROWS_DECODE=1
+        self._lora_rows_cap = int(os.environ.get("MPAMD_LORA_ROWS", str(LORA_ROWS_DEFAULT)))
+        self._lora_rows_decode = os.environ.get("MPAMD_LORA_ROWS_DECODE", "0") == "1"
         # MXFP4 weights (StageWeights.quantize_mxfp4: norm weights folded in before the one
         # quantization): <= 64-row decode steps run the fused-norm path on ops.linear_w4, steps of
         # 65 .. MPAMD_W4_ROWS rows the in-place GEMM (_proj_dense), everything else dequantizes one
@@ -1042,12 +1053,25 @@ class StageExecutor:
                 return ops.linear_w4_rows(x, w4, getattr(L, name + "_s4"), out=out, epilogue=epilogue)
         return ops.linear(x, L.dense(name, wdt), out=out, **kw)
 
+    def _lora_dense(self, st: _Step, lp, x, y):
+        """``y += B (scale A x)`` of one targeted projection on the row-major path.  A GPU step of 65 ..
+        MPAMD_LORA_ROWS rows (not a pure decode step unless MPAMD_LORA_ROWS_DECODE=1) runs the two segmented
+        kernels on the device slots (``ops.lora_update_rows``; ``t`` fp32, one buffer per rank); everything
+        else the torch form by runs of rows (``ops.lora_update``)."""
+        R = lp.A.shape[1]
+        if (self.device.type == "cuda" and 64 < st.T <= self._lora_rows_cap and
+                (not st.decode or self._lora_rows_decode) and
+                ops.lora_rows_ok(st.T, lp.B.shape[1], lp.A.shape[2], R)):
+            t = st.buf(f"lora_t{R}", (st.T, R), torch.float32)
+            return ops.lora_update_rows(x, y, lp.A, lp.B, self._lora.scale, st.lora[0], t=t)
+        return ops.lora_update(x, y, lp.A, lp.B, self._lora.scale, st.lora[1])
+
     def _layers_dense(self, st: _Step):
-        """Row-major path: any row count, any device; deep prompts, and LoRA steps with the torch form of
-        the update by runs of rows (``ops.lora_update``)."""
+        """Row-major path: any row count, any device; deep prompts, and LoRA steps (``_lora_dense``: the
+        segmented kernels above 64 rows, else the torch form of the update by runs of rows)."""
         cfg, T, eps, prompt = self.cfg, st.T, self.cfg.rms_norm_eps, st.prompt
         H, F = cfg.hidden_size, cfg.intermediate_size
-        lo, runs = (self._lora, st.lora[1]) if st.lora is not None else (None, None)
+        lo = self._lora if st.lora is not None else None
         h, res, qkv, o, mlp = self._begin(st)
         xn = st.buf("xn", (T, H))
         attn = st.buf("attn", (T, cfg.q_dim))
@@ -1078,12 +1102,12 @@ class StageExecutor:
             wdt = self.dtype if L.moe else torch.bfloat16
             self._proj_dense(st, L, "qkv", xn, qkv, wdt, wp=qkv_p)
             if LL.qkv is not None:
-                ops.lora_update(xn, qkv, LL.qkv.A, LL.qkv.B, lo.scale, runs)
+                self._lora_dense(st, LL.qkv, xn, qkv)
             kc, vc = self.cache.layer(li)
             self._rope_attend(st, qkv, kc, vc, attn, False)
             self._proj_dense(st, L, "o", attn, o, wdt, wp=L.o_p)
             if LL.o is not None:
-                ops.lora_update(attn, o, LL.o.A, LL.o.B, lo.scale, runs)
+                self._lora_dense(st, LL.o, attn, o)
             self._ar(o)
             ops.rmsnorm(o, g_post, eps, out=xn, residual=res, mode=1)
             if L.moe:
@@ -1091,13 +1115,13 @@ class StageExecutor:
                 continue
             if LL.gate_up is not None:  # epilogue 0, the update, then SwiGLU
                 gu = self._proj_dense(st, L, "gate_up", xn, st.buf("gu", (T, 2 * F)), wp=gu_p)
-                ops.lora_update(xn, gu, LL.gate_up.A, LL.gate_up.B, lo.scale, runs)
+                self._lora_dense(st, LL.gate_up, xn, gu)
                 ops.swiglu(gu, out=act)
             else:
                 self._proj_dense(st, L, "gate_up", xn, act, epilogue=1, wp=gu_p)
             self._proj_dense(st, L, "down", act, mlp, wp=L.down_p)
             if LL.down is not None:
-                ops.lora_update(act, mlp, LL.down.A, LL.down.B, lo.scale, runs)
+                self._lora_dense(st, LL.down, act, mlp)
             self._ar(mlp)
         return res, mlp, None
 
