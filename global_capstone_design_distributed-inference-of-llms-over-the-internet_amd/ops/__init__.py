@@ -1694,6 +1694,80 @@ def moe_down_w8(act, w8, w_scale, cnt, wd, a_rows: int, out=None):
 
 
 # ---------------------------------------------------------------------------------------
+# The same two launches over UNQUANTIZED expert stacks (csrc/gemm_moe_bf16.hip): ``wp`` is the stack an
+# unquantized stage already holds, ``pack_weight`` per expert, [E, N/16, K/32, 64, 8] - no scales, no
+# repacking.  ``cnt``, ``wd`` and the E packed slabs between the launches are as above.
+def moe_ok(M: int, E: int, H: int, F: int) -> bool:
+    """Whether both grouped bf16 kernels cover the shape (M <= 64 rows; a dry dispatch, as ``moe_w8_ok``)."""
+    key = ("bf16", int(M), int(E), int(H), int(F))
+    if key not in _MOE_OK:
+        _MOE_OK[key] = bool(native_available() and torch.ops.mpamd.moe_ok(*key[1:]))
+    return _MOE_OK[key]
+
+
+def _moe_bf16_dims(wp: torch.Tensor, cnt: torch.Tensor, M: int):
+    """(E, N, K) of stacked packed expert weights, with the checks both grouped bf16 ops share."""
+    if wp.dim() != 5 or tuple(wp.shape[3:]) != (64, 8) or (_native(wp) and wp.dtype != torch.bfloat16):
+        raise ValueError("wp must be stacked packed expert weights bf16 [E, N/16, K/32, 64, 8]")
+    E, N, K = wp.shape[0], 16 * wp.shape[1], 32 * wp.shape[2]
+    if cnt.numel() != E or cnt.dtype != torch.int32:
+        raise ValueError(f"cnt must be int32 [{E}] routed-token counts")
+    if not 0 <= M <= 64:
+        raise ValueError(f"the grouped MoE GEMMs take 0..64 rows, got {M}")
+    return E, N, K
+
+
+def moe_gate_up(x, wp, cnt, a_rows: int, out=None):
+    """act[e] = SwiGLU(x @ gate_up[e]^T) for every routed expert, one launch: ``x`` packed bf16
+    (``a_rows`` rows), output E packed slabs (an unrouted expert's slab is left untouched).  A routed
+    slab holds the bits of ``linear(x, None, wp=wp[e], a_rows=a_rows, epilogue=1, out_packed=True)`` on
+    the ring form.  CPU tensors: the same formula in fp32, routed experts only."""
+    M = int(a_rows)
+    E, N, K = _moe_bf16_dims(wp, cnt, M)
+    if x.dim() != 1 or x.dtype != wp.dtype or x.numel() < packed_numel(M, K):
+        raise ValueError(f"x must be a packed activation of {M} rows x {K}, in the weights' dtype")
+    F_ = N // 2
+    slab = packed_numel(M, F_)
+    if out is None:
+        out = torch.zeros(E * slab, dtype=x.dtype, device=x.device)
+    if not _native(x):
+        xr = ref.unpack_act(x, M, K)
+        for e, c in enumerate(cnt.tolist()):
+            if c <= 0:
+                continue
+            y = (xr.float() @ unpack_weight(wp[e]).float().t()).to(x.dtype)
+            ref.pack_act(ref.swiglu(y), out=out[e * slab:(e + 1) * slab])
+        return out
+    torch.ops.mpamd.moe_gate_up(x, wp, cnt, out, M)
+    return out
+
+
+def moe_down(act, wp, cnt, wd, a_rows: int, out=None):
+    """y [M, H] = bf16(sum over routed experts e of wd[:, e] * (act[e] @ down[e]^T)), one launch: the
+    routing weights applied in fp32, ONE rounding of the combined sum.  CPU tensors: the same formula."""
+    M = int(a_rows)
+    E, N, K = _moe_bf16_dims(wp, cnt, M)
+    if tuple(wd.shape) != (M, E) or wd.dtype != torch.float32:
+        raise ValueError(f"wd must be the fp32 [{M}, {E}] dense routing matrix")
+    slab = packed_numel(M, K)
+    if act.dim() != 1 or act.dtype != wp.dtype or act.numel() < E * slab:
+        raise ValueError(f"act must hold {E} packed activations of {M} rows x {K}, in the weights' dtype")
+    if out is None:
+        out = torch.empty(M, N, dtype=act.dtype, device=act.device)
+    if not _native(act):
+        tot = torch.zeros(M, N, dtype=torch.float32)
+        for e, c in enumerate(cnt.tolist()):
+            if c <= 0:
+                continue
+            a = ref.unpack_act(act[e * slab:(e + 1) * slab], M, K)
+            tot += wd[:, e:e + 1] * (a.float() @ unpack_weight(wp[e]).float().t())
+        out.copy_(tot.to(out.dtype))
+        return out
+    torch.ops.mpamd.moe_down(act, wp, cnt, wd, out, M)
+    return out
+
+
+# ---------------------------------------------------------------------------------------
 # The same MLP ABOVE 64 rows (csrc/gemm_moe_rows.hip): the T * k routed (token, expert) pairs are
 # grouped by expert on the device (``moe_group``: no host sync), then each expert's GEMMs run over the
 # rows routed to it only - gate/up gathers its rows from the row-major ``x`` through ``tok``, down adds

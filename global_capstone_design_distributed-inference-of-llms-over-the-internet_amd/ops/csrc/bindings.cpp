@@ -810,6 +810,53 @@ bool moe_w8_ok(int64_t M, int64_t E, int64_t H, int64_t F) {
   return mp_moe_w8_ok((int)M, (int)E, (int)H, (int)F) != 0;
 }
 
+// Stacked bf16 expert weights of the grouped bf16 MoE GEMMs (gemm_moe_bf16.hip): [E, N/16, K/32, 64, 8],
+// ops.pack_weight per expert -> (E, N, K)
+static std::tuple<int, int, int> check_moe_weight_bf16(const at::Tensor& wp) {
+  MP_CHECK(wp.is_cuda() && wp.scalar_type() == at::kBFloat16 && wp.dim() == 5 && wp.size(3) == 64 && wp.size(4) == 8 &&
+               wp.is_contiguous(),
+           "wp must be stacked packed expert weights bf16 [E, N/16, K/32, 64, 8] (ops.pack_weight per expert)");
+  return {(int)wp.size(0), 16 * (int)wp.size(1), 32 * (int)wp.size(2)};
+}
+
+// Grouped gate/up + SwiGLU of all bf16 experts (gemm_moe_bf16.hip mp_moe_gate_up): packed bf16 x (M rows)
+void moe_gate_up(const at::Tensor& x, const at::Tensor& wp, const at::Tensor& cnt, at::Tensor& act, int64_t M_) {
+  check_bf16_cuda(x, "x");
+  const auto [E, N, K] = check_moe_weight_bf16(wp);
+  const int M = (int)M_;
+  MP_CHECK(M >= 0 && M <= 64, "moe_gate_up: 0 <= M <= 64");
+  MP_CHECK(N % 32 == 0, "moe_gate_up: SwiGLU needs N % 32 == 0");
+  MP_CHECK(x.is_contiguous() && x.numel() >= packed_numel(M, K) && x.device() == wp.device(), "packed x too small");
+  check_moe_cnt(cnt, E, wp);
+  check_moe_act(act, M, E, N / 2, wp);
+  const int rc = mp_moe_gate_up(x.data_ptr(), wp.data_ptr(), cnt.data_ptr<int32_t>(), act.data_ptr(), M, E, K, N / 2,
+                                cur_stream());
+  TORCH_CHECK(rc != 1, "mpamd: moe_gate_up: no grouped kernel covers M=", M, " E=", E, " H=", K, " F=", N / 2);
+  check_launch(rc, "moe_gate_up");
+}
+
+// Grouped down + combine (gemm_moe_bf16.hip mp_moe_down): y bf16 [M, H] = sum_e wd[:, e] * (act[e] . down[e]^T)
+void moe_down(const at::Tensor& act, const at::Tensor& wp, const at::Tensor& cnt, const at::Tensor& wd, at::Tensor& y,
+              int64_t M_) {
+  const auto [E, N, K] = check_moe_weight_bf16(wp);
+  const int M = (int)M_;
+  MP_CHECK(M >= 0 && M <= 64, "moe_down: 0 <= M <= 64");
+  check_moe_cnt(cnt, E, wp);
+  check_moe_act(act, M, E, K, wp);
+  MP_CHECK(wd.is_cuda() && wd.scalar_type() == at::kFloat && wd.is_contiguous() && wd.dim() == 2 && wd.size(0) == M &&
+               wd.size(1) == E && wd.device() == wp.device(),
+           "wd: fp32 [M, E] dense routing weights");
+  check_bf16_cuda(y, "y");
+  check_rows(y, "y");
+  MP_CHECK(y.size(0) == M && y.size(1) == N && y.device() == wp.device(), "y shape");
+  const int rc = mp_moe_down(act.data_ptr(), wp.data_ptr(), cnt.data_ptr<int32_t>(), wd.data_ptr<float>(),
+                             y.data_ptr(), y.stride(0), M, E, N, K, cur_stream());
+  TORCH_CHECK(rc != 1, "mpamd: moe_down: no grouped kernel covers M=", M, " E=", E, " H=", N, " F=", K);
+  check_launch(rc, "moe_down");
+}
+
+bool moe_ok(int64_t M, int64_t E, int64_t H, int64_t F) { return mp_moe_ok((int)M, (int)E, (int)H, (int)F) != 0; }
+
 // Row-gathered grouped MoE GEMMs (gemm_moe_rows.hip).  An int32 / fp32 device vector of n elements
 static void check_moe_vec(const at::Tensor& t, at::ScalarType ty, int64_t n, const at::Tensor& like, const char* what) {
   MP_CHECK(t.is_cuda() && t.scalar_type() == ty && t.is_contiguous() && t.numel() == n && t.device() == like.device(),
@@ -1339,6 +1386,9 @@ TORCH_LIBRARY(mpamd, m) {
   m.def("moe_gate_up_w8(Tensor x, Tensor w8, Tensor wsc, Tensor cnt, Tensor(a!) act, int M) -> ()");
   m.def("moe_down_w8(Tensor act, Tensor w8, Tensor wsc, Tensor cnt, Tensor wd, Tensor(a!) y, int M) -> ()");
   m.def("moe_w8_ok(int M, int E, int H, int F) -> bool", &moe_w8_ok);
+  m.def("moe_gate_up(Tensor x, Tensor wp, Tensor cnt, Tensor(a!) act, int M) -> ()");
+  m.def("moe_down(Tensor act, Tensor wp, Tensor cnt, Tensor wd, Tensor(a!) y, int M) -> ()");
+  m.def("moe_ok(int M, int E, int H, int F) -> bool", &moe_ok);
   m.def("moe_group(Tensor idx, Tensor w, Tensor(a!) off, Tensor(b!) tok, Tensor(c!) wsel) -> ()");
   m.def("moe_gate_up_w8_rows(Tensor x, Tensor w8, Tensor wsc, Tensor off, Tensor tok, Tensor(a!) out) -> ()");
   m.def(
@@ -1391,6 +1441,8 @@ TORCH_LIBRARY_IMPL(mpamd, CUDA, m) {
   m.impl("dequant_w4", &dequant_w4);
   m.impl("moe_gate_up_w8", &moe_gate_up_w8);
   m.impl("moe_down_w8", &moe_down_w8);
+  m.impl("moe_gate_up", &moe_gate_up);
+  m.impl("moe_down", &moe_down);
   m.impl("moe_group", &moe_group);
   m.impl("moe_gate_up_w8_rows", &moe_gate_up_w8_rows);
   m.impl("moe_down_w8_rows", &moe_down_w8_rows);

@@ -215,6 +215,12 @@ int mp_moe_gate_up_w8(const void* x, const void* w8, const float* wsc, const int
 int mp_moe_down_w8(const void* act, const void* w8, const float* wsc, const int32_t* cnt, const float* wd, void* y,
                    int64_t y_stride, int M, int E, int H, int F, hipStream_t stream);
 int mp_moe_w8_ok(int M, int E, int H, int F);
+// gemm_moe_bf16.hip: the same two launches over bf16 expert stacks (ops.pack_weight per expert), no scales
+int mp_moe_gate_up(const void* x, const void* wp, const int32_t* cnt, void* act, int M, int E, int H, int F,
+                   hipStream_t stream);
+int mp_moe_down(const void* act, const void* wp, const int32_t* cnt, const float* wd, void* y, int64_t y_stride,
+                int M, int E, int H, int F, hipStream_t stream);
+int mp_moe_ok(int M, int E, int H, int F);
 // gemm_moe_rows.hip: the same MLP above 64 rows - pairs grouped by expert on the device, then the two
 // grouped GEMMs over each expert's gathered rows (P = T k pairs; 1: shape not covered, nothing launched)
 int mp_moe_group(const int64_t* idx, const float* w, int32_t* off, int32_t* tok, float* wsel, int T, int k, int E,

@@ -16,6 +16,9 @@ MI355X execution strategy (runtime/executor.py ``_moe_mlp``):
   expert is routed to by some token (P(unused) = (6/8 * 5/7)^64 ~ 1e-10), so the bytes read
   equal the sparse schedule's, the extra MFMA work is free at M <= 64, and the step has no
   data-dependent shapes - it stays inside the hipGraph;
+* MPAMD_MOE_GROUPED_BF16=1: those steps run the routed experts only, in two grouped launches over the
+  packed bf16 stacks (``ops.moe_gate_up`` / ``moe_down``, ops/csrc/gemm_moe_bf16.hip) - unrouted experts
+  skipped on the device, still no data-dependent shape;
 * prefill (T > 64) groups tokens by expert (one host sync per layer, outside any graph),
   runs each expert's GEMMs on its gathered rows and scatter-adds the weighted result;
 * fp8 experts, prefill steps above 64 rows (up to MPAMD_MOE_ROWS; decode steps with

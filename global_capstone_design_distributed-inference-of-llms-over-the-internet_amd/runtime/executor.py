@@ -390,6 +390,11 @@ class StageExecutor:
                     self._w8 = True  # the W8A16 layout and kernels (never the fused-norm path: _fused stays off)
                     self.graph_max_batch = min(self.graph_max_batch, 64)
         self._moe_grouped = os.environ.get("MPAMD_MOE_GROUPED", "1") != "0"
+        # UNQUANTIZED experts: MPAMD_MOE_GROUPED_BF16=1 sends steps of <= 64 rows to the grouped bf16 launches
+        # (ops.moe_gate_up / moe_down, _moe_bf16_route).  Off by default: the per-expert launches of the
+        # default path are the ones recorded in tests/golden/executor_paths
+        self._moe_grouped_bf16 = os.environ.get("MPAMD_MOE_GROUPED_BF16", "0") == "1"
+        self._moe_packed: Dict[int, tuple] = {}
         # ... and prefill steps (prompts, chunks, mixed steps) of 65 .. MPAMD_MOE_ROWS rows run the experts
         # on the row-gathered grouped kernels (ops.moe_group / moe_gate_up_w8_rows / moe_down_w8_rows);
         # 0 keeps the dequantizing schedule for them (qkv / o dequantize either way).  Pure decode steps
@@ -1364,6 +1369,29 @@ class StageExecutor:
             acc.addcmul_(y, wd[:, j:j + 1])
         mlp.copy_(acc)
 
+    def _moe_bf16_route(self, L, T: int, packed: bool) -> bool:
+        """Whether a step of T rows runs this layer's UNQUANTIZED experts on the grouped bf16 launches: a
+        packed GPU step (or any CPU step, on the ops' torch forms) of <= 64 rows, a shape both kernels
+        cover, no tensor parallelism, no CPU offload.  Everything else keeps the per-expert loop."""
+        cfg = self.cfg
+        E, H, F = cfg.num_local_experts, cfg.hidden_size, cfg.intermediate_size
+        if not 0 < T <= 64 or self._tp is not None or self._streamer is not None or L.gate_up is None:
+            return False
+        if self.device.type == "cuda":
+            return packed and L.gate_up_p is not None and L.gate_up_p.dim() == 5 and ops.moe_ok(T, E, H, F)
+        return E <= 32 and H % 128 == 0 and F % 128 == 0
+
+    def _moe_stacks(self, L):
+        """The layer's packed expert stacks (gate_up [E, 2F/16, H/32, 64, 8], down [E, H/16, F/32, 64, 8]):
+        the ones ``pack_for_decode`` left on a GPU stage; a CPU stage packs them once per layer."""
+        if L.gate_up_p is not None:
+            return L.gate_up_p, L.down_p
+        key = id(L)
+        if key not in self._moe_packed:
+            self._moe_packed[key] = (torch.stack([ops.pack_weight(w) for w in L.gate_up]),
+                                     torch.stack([ops.pack_weight(w) for w in L.down]))
+        return self._moe_packed[key]
+
     def _moe_mlp(self, st: _Step, L, xn, mlp, act, packed: bool) -> None:
         """Mixtral sparse-MoE MLP into ``mlp`` (ops/moe.py has the routing math and the
         decode-vs-prefill strategy).  Decode steps run every expert on the whole batch with a
@@ -1385,6 +1413,16 @@ class StageExecutor:
             off, tok, wsel = ops.moe_group(idx, w, E)
             rows = ops.moe_gate_up_w8_rows(xn, L.gate_up_w8, L.gate_up_ws, off, tok, out=e("moe_rows", (T * k, F)))
             ops.moe_down_w8_rows(rows, L.down_w8, L.down_ws, off, tok, wsel, T, out=mlp)
+            return
+        if self._moe_grouped_bf16 and self._moe_bf16_route(L, T, packed):
+            # unquantized experts, <= 64 rows, MPAMD_MOE_GROUPED_BF16=1: two grouped launches over the packed
+            # stacks (ops/csrc/gemm_moe_bf16.hip) - unrouted experts skipped on the device, no host sync
+            gu_p, dn_p = self._moe_stacks(L)
+            wd = moe.dense_weights(w, idx, E, out=e("moe_w", (T, E), torch.float32))
+            cnt = (wd > 0).sum(0, dtype=torch.int32)
+            slabs = ops.moe_gate_up(xn if packed else ops.pack_act(xn), gu_p, cnt, T,
+                                    out=e("moe_act_p", (E * ops.packed_numel(T, F),)))
+            ops.moe_down(slabs, dn_p, cnt, wd, T, out=mlp)
             return
         acc = e("moe_acc", (T, H), torch.float32)
         acc.zero_()
