@@ -2040,6 +2040,93 @@ def linear_mx(ax, as_, w8, w_scale, a_rows: int, out=None, epilogue: int = 0, re
     return out
 
 
+# ---------------------------------------------------------------------------------------
+# W8A8-MX GEMM ABOVE 64 rows (csrc/gemm_mx_rows.hip): row-major bf16 activations are quantized to MX e4m3
+# in one launch (mp_quant_mx_rows), then multiplied with the fp8 weight in place on the block-scaled MFMA
+# (mp_gemm_mx_rows), gemm_w8_rows.hip's two-dimensional split; epilogue 0 or SwiGLU, row-major output.
+_MX_ROWS_OK = {}
+_MX_ROWS_WS = {}
+
+
+def mx_rows_buffers(T: int, K: int, device):
+    """(ax, as) buffers of ``quant_mx_rows`` for T rows x K: uint8 [ceil(T/16), K/128, 2, 64, 16] and
+    uint8 [ceil(T/64), K/128, 64, 4]."""
+    T, K = int(T), int(K)
+    return (torch.empty((T + 15) // 16, K // 128, 2, 64, 16, dtype=torch.uint8, device=device),
+            torch.empty((T + 63) // 64, K // 128, 64, 4, dtype=torch.uint8, device=device))
+
+
+def quant_mx_rows(x: torch.Tensor, ax=None, as_=None):
+    """Row-major bf16 ``x`` [T, K] (unit inner stride, row stride % 8 == 0, K % 128 == 0) -> MX e4m3 bytes +
+    e8m0 block scales in the fragment order of ``gemm_mx_rows.hip``; the block rule is ``mx_block_quant``'s.
+    ``ax`` / ``as_``: buffers at least as large as ``mx_rows_buffers(T, K)``'s."""
+    if ax is None or as_ is None:
+        ax, as_ = mx_rows_buffers(x.shape[0], x.shape[1], x.device)
+    torch.ops.mpamd.quant_mx_rows(x, ax, as_)
+    return ax, as_
+
+
+def mx_rows_ok(T: int, N: int, K: int, epilogue: int = 0) -> bool:
+    """Whether ``linear_mx_rows`` has a kernel for the shape: T >= 65, N % 16 == 0 (SwiGLU: % 32),
+    K % 128 == 0 (a dry dispatch, as ``w8_rows_ok``)."""
+    key = (int(T), int(N), int(K), int(epilogue))
+    if key not in _MX_ROWS_OK:
+        _MX_ROWS_OK[key] = bool(native_available() and torch.ops.mpamd.gemm_mx_rows_ok(*key))
+    return _MX_ROWS_OK[key]
+
+
+def _mx_rows_workspace(T: int, K: int, device):
+    """Flat (ax, as) scratch of ``linear_mx_rows`` (per device, grown to the largest request; steps above 64
+    rows are never graph-captured, so growing is safe)."""
+    na, ns = (T + 15) // 16 * 16 * K, (T + 63) // 64 * 2 * K
+    ws = _MX_ROWS_WS.get(device)
+    if ws is None or ws[0].numel() < na or ws[1].numel() < ns:
+        ws = (torch.empty(max(na, ws[0].numel() if ws else 0), dtype=torch.uint8, device=device),
+              torch.empty(max(ns, ws[1].numel() if ws else 0), dtype=torch.uint8, device=device))
+        _MX_ROWS_WS[device] = ws
+    return ws
+
+
+def linear_mx_rows(x, w8, w_scale, out=None, epilogue: int = 0):
+    """y [T, N'] = epilogue(mx_block_quant(x) @ W^T) for row-major ``x`` [T, K] (unit inner stride, row stride
+    % 8 == 0) and an fp8 weight (``w8_from_fp8`` layout + fp32 column scales [N]): the activations are
+    quantized to e4m3 with an e8m0 scale per 32-element block and the product runs on the block-scaled MFMA.
+    Epilogue 0 (N' = N) or 1 (SwiGLU over the 16-row gate/up interleave, N' = N / 2).  Channel scales in
+    fp32, one rounding to bf16, the same bits on every run.  ``out``: any [T, N'] view with unit inner
+    stride.  An uncovered shape is an error on the GPU (``mx_rows_ok``); CPU tensors run ``reference.linear``
+    on the block-quantized activation and the dequantized weight."""
+    if w8.dim() != 4 or tuple(w8.shape[2:]) != (64, 8) or w8.dtype != torch.uint8:
+        raise ValueError("w8 must be an fp8 weight uint8 [N/16, K/32, 64, 8] (ops.w8_from_fp8)")
+    N, K = 16 * w8.shape[0], 32 * w8.shape[1]
+    if tuple(w_scale.shape) != (N,) or w_scale.dtype != torch.float32:
+        raise ValueError(f"w_scale must be fp32 [{N}] column scales")
+    if epilogue not in (0, 1):
+        raise ValueError("linear_mx_rows: epilogue 0 (store) or 1 (SwiGLU)")
+    if x.dim() != 2 or x.shape[1] != K:
+        raise ValueError(f"x must be row-major [T, {K}]")
+    T, ncols = x.shape[0], N // 2 if epilogue == 1 else N
+    if out is not None and (tuple(out.shape) != (T, ncols) or out.dtype != x.dtype):
+        raise ValueError(f"out must be [{T}, {ncols}] {x.dtype}")
+    if not _native(x):
+        y = ref.linear(mx_block_quant(x).to(x.dtype), unpack_weight_w8(w8, w_scale, x.dtype), epilogue=epilogue)
+        if out is not None:
+            out.copy_(y)
+            return out
+        return y
+    if x.dtype != torch.bfloat16:
+        raise ValueError("x must be bf16")
+    if x.stride(1) != 1 or x.stride(0) % 8 or x.stride(0) < K:
+        raise ValueError("x must have unit inner stride and a row stride that is a multiple of 8")
+    if not mx_rows_ok(T, N, K, epilogue):
+        raise RuntimeError(f"mpamd: linear_mx_rows: no kernel covers T={T} N={N} K={K} epilogue={epilogue}")
+    if out is None:
+        out = torch.empty(T, ncols, dtype=x.dtype, device=x.device)
+    ax, as_ = _mx_rows_workspace(T, K, x.device)
+    torch.ops.mpamd.quant_mx_rows(x, ax, as_)
+    torch.ops.mpamd.gemm_mx_rows(ax, as_, w8, w_scale, out, T, int(epilogue))
+    return out
+
+
 def autotune_w8(shapes, device, ms=(4, 16, 32, 48, 64), iters: int = 12, rounds: int = 3) -> dict:
     """``autotune_gemm`` for the W8A16 GEMM: ring vs split-K ring per (N, K, epilogue) and M
     bucket, on fp8 weights rotated over ~1 GiB (decode never finds them in the Infinity Cache)."""

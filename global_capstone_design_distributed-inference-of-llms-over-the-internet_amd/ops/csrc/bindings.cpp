@@ -978,6 +978,66 @@ bool gemm_w8_rows_ok(int64_t T, int64_t N, int64_t K, int64_t epilogue) {
   return mp_gemm_w8_rows_ok((int)T, (int)N, (int)K, (int)epilogue) != 0;
 }
 
+// W8A8-MX GEMM above 64 rows (gemm_mx_rows.hip).  The quantizer: x bf16 row-major [T, K] with a row stride ->
+// ax uint8 [ceil(T/16) * K * 16] e4m3 bytes and as uint8 [ceil(T/64) * K * 2] e8m0 block scales (at least)
+static void check_mx_rows_buffers(const at::Tensor& ax, const at::Tensor& as, int64_t T, int64_t K,
+                                  const at::Device& dev) {
+  MP_CHECK(ax.is_cuda() && ax.scalar_type() == at::kByte && ax.is_contiguous() && ax.device() == dev &&
+               ax.numel() >= (T + 15) / 16 * 16 * K && reinterpret_cast<uintptr_t>(ax.data_ptr()) % 16 == 0,
+           "mx_rows: ax must be contiguous uint8 [ceil(T/16), K/128, 2, 64, 16] on the input's device");
+  MP_CHECK(as.is_cuda() && as.scalar_type() == at::kByte && as.is_contiguous() && as.device() == dev &&
+               as.numel() >= (T + 63) / 64 * 2 * K && reinterpret_cast<uintptr_t>(as.data_ptr()) % 4 == 0,
+           "mx_rows: as must be contiguous uint8 [ceil(T/64), K/128, 64, 4] on the input's device");
+}
+
+void quant_mx_rows(const at::Tensor& x, at::Tensor& ax, at::Tensor& as) {
+  MP_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16, "quant_mx_rows: x must be bf16 on the GPU");
+  MP_CHECK(x.dim() == 2 && x.size(0) >= 1 && x.size(1) >= 128 && x.size(1) % 128 == 0,
+           "quant_mx_rows: x must be 2-D [T, K] with T >= 1 and K % 128 == 0");
+  const int64_t T = x.size(0), K = x.size(1);
+  MP_CHECK(x.stride(1) == 1 && x.stride(0) % 8 == 0 && x.stride(0) >= K &&
+               reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0,
+           "quant_mx_rows: x needs unit inner stride, a row stride that is a multiple of 8 and 16-B alignment");
+  MP_CHECK(T < (1ll << 31) && K < (1ll << 31), "quant_mx_rows: x dimensions exceed 32 bits");
+  check_mx_rows_buffers(ax, as, T, K, x.device());
+  check_launch(mp_quant_mx_rows(x.data_ptr(), x.stride(0), ax.data_ptr(), as.data_ptr(), (int)T, (int)K, cur_stream()),
+               "quant_mx_rows");
+}
+
+// The GEMM: ax / as of quant_mx_rows for T rows, the fp8 weight in place, out bf16 [T, N'] (any row stride).
+// gemm_w8_rows's checks; the messages name the op's arguments.
+void gemm_mx_rows(const at::Tensor& ax, const at::Tensor& as, const at::Tensor& w8, const at::Tensor& w_scale,
+                  at::Tensor& out, int64_t T, int64_t epilogue) {
+  MP_CHECK(w8.is_cuda() && w8.scalar_type() == at::kByte && w8.dim() == 4 && w8.size(2) == 64 && w8.size(3) == 8 &&
+               w8.is_contiguous(),
+           "linear_mx_rows: w8 must be a contiguous fp8 weight uint8 [N/16, K/32, 64, 8] on the GPU (ops.w8_from_fp8)");
+  const int64_t N = 16 * w8.size(0), K = 32 * w8.size(1);
+  MP_CHECK(w_scale.is_cuda() && w_scale.scalar_type() == at::kFloat && w_scale.is_contiguous() &&
+               w_scale.numel() == N && w_scale.device() == w8.device(),
+           "linear_mx_rows: w_scale must be contiguous fp32 [N] column scales on w8's device");
+  MP_CHECK(epilogue == 0 || epilogue == 1, "linear_mx_rows: epilogue 0 (store) or 1 (SwiGLU)");
+  MP_CHECK(T >= 1 && T < (1ll << 31) && N < (1ll << 31) && K < (1ll << 31),
+           "linear_mx_rows: T / w8 dimensions out of range");
+  check_mx_rows_buffers(ax, as, T, K, w8.device());
+  const int64_t ncols = epilogue == 1 ? N / 2 : N;
+  MP_CHECK(out.is_cuda() && out.scalar_type() == at::kBFloat16 && out.device() == w8.device(),
+           "linear_mx_rows: out must be bf16 on w8's device");
+  MP_CHECK(out.dim() == 2 && out.size(0) == T && out.size(1) == ncols && out.stride(1) == 1 && out.stride(0) >= ncols,
+           "linear_mx_rows: out must be [T, N'] rows with unit inner stride");
+  mp::GemmArgs a = mp::gemm_shape_args((int)T, (int)N, (int)K, (int)epilogue, 0);
+  a.x = ax.data_ptr(), a.as = as.data_ptr();
+  a.w = w8.data_ptr(), a.wsc = w_scale.data_ptr<float>();
+  a.y = out.data_ptr(), a.y_stride = out.stride(0);
+  const int rc = mp_gemm_mx_rows(&a, cur_stream());
+  TORCH_CHECK(rc != 1, "mpamd: linear_mx_rows: no kernel covers T=", T, " N=", N, " K=", K, " epilogue=", epilogue);
+  check_launch(rc, "gemm_mx_rows");
+}
+
+bool gemm_mx_rows_ok(int64_t T, int64_t N, int64_t K, int64_t epilogue) {
+  if (T <= 0 || N <= 0 || K <= 0 || T >= (1ll << 31) || N >= (1ll << 31) || K >= (1ll << 31)) return false;
+  return mp_gemm_mx_rows_ok((int)T, (int)N, (int)K, (int)epilogue) != 0;
+}
+
 // Batched LoRA (lora.hip): the stacked adapter matrices, the row slots and the fp32 intermediate
 static mp::LoraArgs lora_args(const at::Tensor& mats, const char* name, const at::Tensor& slots, const at::Tensor& t,
                               int64_t M_, int64_t max_m = 1 << 20) {
@@ -1399,6 +1459,10 @@ TORCH_LIBRARY(mpamd, m) {
   m.def("gemm_w8_rows_ok(int T, int N, int K, int epilogue) -> bool", &gemm_w8_rows_ok);
   m.def("gemm_w4_rows(Tensor x, Tensor w4, Tensor s4, Tensor(a!) out, int epilogue) -> ()");
   m.def("gemm_w4_rows_ok(int T, int N, int K, int epilogue) -> bool", &gemm_w4_rows_ok);
+  m.def("quant_mx_rows(Tensor x, Tensor(a!) ax, Tensor(b!) as_) -> ()");
+  m.def(
+      "gemm_mx_rows(Tensor ax, Tensor as_, Tensor w8, Tensor w_scale, Tensor(a!) out, int T, int epilogue) -> ()");
+  m.def("gemm_mx_rows_ok(int T, int N, int K, int epilogue) -> bool", &gemm_mx_rows_ok);
   m.def("lora_shrink(Tensor x, Tensor A, Tensor scale, Tensor slots, Tensor(a!) t, int M) -> ()");
   m.def("lora_expand(Tensor t, Tensor B, Tensor slots, Tensor(a!) y) -> ()");
   m.def("lora_ok(int M, int N, int K, int R) -> bool", &lora_ok);
@@ -1448,6 +1512,8 @@ TORCH_LIBRARY_IMPL(mpamd, CUDA, m) {
   m.impl("moe_down_w8_rows", &moe_down_w8_rows);
   m.impl("gemm_w8_rows", &gemm_w8_rows);
   m.impl("gemm_w4_rows", &gemm_w4_rows);
+  m.impl("quant_mx_rows", &quant_mx_rows);
+  m.impl("gemm_mx_rows", &gemm_mx_rows);
   m.impl("lora_shrink", &lora_shrink);
   m.impl("lora_expand", &lora_expand);
   m.impl("lora_shrink_rows", &lora_shrink_rows);

@@ -240,6 +240,13 @@ int mp_gemm_w8_rows_ok(int T, int N, int K, int epilogue);
 // and wsc the e8m0 block scales s4, as mp_gemm_w4 takes them
 int mp_gemm_w4_rows(const mp::GemmArgs* a, hipStream_t stream);
 int mp_gemm_w4_rows_ok(int T, int N, int K, int epilogue);
+// gemm_mx_rows.hip: the W8A8-MX counterpart above 64 rows.  mp_quant_mx_rows turns row-major bf16 x [T, K]
+// (xs elements a row, a multiple of 8; K % 128 == 0) into ax uint8 [ceil(T/16)][K/128][2][64][16] and as uint8
+// [ceil(T/64)][K/128][64][4].  mp_gemm_mx_rows takes a.x = ax, a.as = as and w / wsc / y / y_stride / M / N / K /
+// epilogue as mp_gemm_w8_rows does (x_stride unused), with the same shapes and return codes
+int mp_quant_mx_rows(const void* x, int64_t xs, void* ax, void* as, int T, int K, hipStream_t stream);
+int mp_gemm_mx_rows(const mp::GemmArgs* a, hipStream_t stream);
+int mp_gemm_mx_rows_ok(int T, int N, int K, int epilogue);
 // lora.hip: 0, 1 when the shape is not covered (needs M <= 64, K % 32 == 0, N % 8 == 0, R % 16 == 0,
 // R <= 192; nothing launched), < 0 for a bad call, else the HIP error.  M == 0 returns 0.
 int mp_lora_ok(int M, int N, int K, int R);

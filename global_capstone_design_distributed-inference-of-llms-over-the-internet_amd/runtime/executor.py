@@ -72,6 +72,11 @@ MOE_ROWS_DEFAULT = 4096
 # the largest measured row count at which it wins on all four Llama-3-70B projections
 # (profiles/w8_rows/README.md).  MPAMD_W8_ROWS overrides it, 0 turns the route off
 W8_ROWS_DEFAULT = 4096
+# the same for an fp8 stage in MX mode (MPAMD_FP8_MODE=mx): the largest step whose W8A16 projections run
+# W8A8-MX on the block-scaled MFMA instead (ops.linear_mx_rows: the activation quantizer + the GEMM).  It
+# changes the outputs (activations become e4m3 blocks), so it is OFF by default and MPAMD_MX_ROWS=<rows>
+# opts in; profiles/mx_rows/README.md has the measurements a default would be decided on
+MX_ROWS_DEFAULT = 0
 # the same for the four projections of a dense MXFP4 Llama stage (ops.linear_w4_rows instead of the HIP
 # dequantizer + a library GEMM), by the same rule: the largest measured row count at which the in-place
 # kernel's slowest round beats the partner's fastest on all four projections of Llama-2-7B and Llama-3-70B.
@@ -407,6 +412,9 @@ class StageExecutor:
         # MPAMD_W8_ROWS_DECODE=1, the rule of MPAMD_MOE_ROWS_DECODE
         self._w8_rows_cap = int(os.environ.get("MPAMD_W8_ROWS", str(W8_ROWS_DEFAULT)))
         self._w8_rows_decode = os.environ.get("MPAMD_W8_ROWS_DECODE", "0") == "1"
+        # ... in MX mode (MPAMD_FP8_MODE=mx) they run W8A8-MX at 65 .. MPAMD_MX_ROWS rows instead (the quantizer
+        # + ops.linear_mx_rows), under the same conditions and MPAMD_W8_ROWS_DECODE
+        self._mx_rows_cap = int(os.environ.get("MPAMD_MX_ROWS", str(MX_ROWS_DEFAULT)))
         # ... and the projections of an MXFP4 stage at 65 .. MPAMD_W4_ROWS rows read the codes and block
         # scales in place, under the same rule for pure decode steps (MPAMD_W4_ROWS_DECODE)
         self._w4_rows_cap = int(os.environ.get("MPAMD_W4_ROWS", str(W4_ROWS_DEFAULT)))
@@ -1039,11 +1047,18 @@ class StageExecutor:
     def _proj_dense(self, st: _Step, L, name: str, x, out, wdt=torch.bfloat16, **kw):
         """Projection ``name`` of layer ``L`` on the row-major path.  A W8A16 layer's weight is read in place
         by ``ops.linear_w8_rows`` on a GPU step of 65 .. MPAMD_W8_ROWS rows (not a pure decode step unless
-        MPAMD_W8_ROWS_DECODE=1; never under TP, offload or --gemm hipblaslt), an MXFP4 layer's by
+        MPAMD_W8_ROWS_DECODE=1; never under TP, offload or --gemm hipblaslt) - in MX mode by ``ops.linear_mx_rows``
+        on a step of 65 .. MPAMD_MX_ROWS rows under the same conditions, tried first -, an MXFP4 layer's by
         ``ops.linear_w4_rows`` under MPAMD_W4_ROWS / MPAMD_W4_ROWS_DECODE in the same way; everything else dequantizes
         the projection (``L.dense``) into ``ops.linear(x, w, out=out, **kw)``.  ``kw``: ``epilogue`` (0 / 1)
         and ``wp``, the packed bf16 copy, which a W8A16 layer does not have and the in-place route ignores."""
         epilogue = kw.get("epilogue", 0)
+        if (self._mx and L.w8 and self.device.type == "cuda" and 64 < st.T <= self._mx_rows_cap and
+                (not st.decode or self._w8_rows_decode) and self._tp is None and self._streamer is None and
+                ops.gemm_policy() != "hipblaslt"):
+            w8 = getattr(L, name + "_w8")
+            if ops.mx_rows_ok(st.T, 16 * w8.shape[0], 32 * w8.shape[1], epilogue):
+                return ops.linear_mx_rows(x, w8, getattr(L, name + "_ws"), out=out, epilogue=epilogue)
         if (L.w8 and self.device.type == "cuda" and 64 < st.T <= self._w8_rows_cap and
                 (not st.decode or self._w8_rows_decode) and self._tp is None and self._streamer is None and
                 ops.gemm_policy() != "hipblaslt"):
