@@ -1883,6 +1883,101 @@ def _moe_rows_workspace(T: int, H: int, device) -> torch.Tensor:
 
 
 # ---------------------------------------------------------------------------------------
+# The same MLP for LARGE steps (csrc/gemm_moe_tiled.hip): over ``moe_group``'s grouping, every expert's rows
+# are cut into 128-row blocks and a workgroup takes one block x up to 256 output columns, so an expert's
+# weights are read once per 128 rows (from L2 after the first block) instead of once per 64.  Down writes
+# each pair's weighted row in fp32 into slot j of its token - j = the pair's rank among the token's valid
+# expert ids - and a streaming combine adds a token's slots in ascending expert order: one bf16 rounding, no
+# atomics, the same bits on every run.  T >= 65; the summation order is its own, so the executor takes these
+# launches only under MPAMD_MOE_TILED.
+def moe_tiled_ok(T: int, E: int, k: int, H: int, F: int) -> bool:
+    """Whether the tiled launches cover the shape (T >= 65, 1 <= k <= E <= 32, T k <= 65536, H and F
+    multiples of 128; a dry dispatch, as ``moe_rows_ok``)."""
+    key = ("tiled", int(T), int(E), int(k), int(H), int(F))
+    if key not in _MOE_OK:
+        _MOE_OK[key] = bool(native_available() and torch.ops.mpamd.moe_tiled_ok(*key[1:]))
+    return _MOE_OK[key]
+
+
+def moe_gate_up_w8_tiled(x, w8, w_scale, off, tok, out=None):
+    """``moe_gate_up_w8_rows``' result - out [T k, F] bf16 row-major, row p = SwiGLU(x[tok[p]] @
+    gate_up[e]^T), fp32 SwiGLU, one rounding - on the tiled launch.  An expert without rows is never read."""
+    if not _native(x):
+        return moe_gate_up_w8_rows(x, w8, w_scale, off, tok, out=out)
+    if x.dim() != 2:
+        raise ValueError("x must be row-major [T, H]")
+    T = x.shape[0]
+    E, N, K, k = _moe_rows_dims(w8, w_scale, off, tok, T)
+    if x.shape[1] != K:
+        raise ValueError(f"x must be [T, {K}]")
+    if out is None:
+        out = torch.empty(T * k, N // 2, dtype=x.dtype, device=x.device)
+    elif tuple(out.shape) != (T * k, N // 2) or out.dtype != x.dtype:
+        raise ValueError(f"out must be [{T * k}, {N // 2}] {x.dtype}")
+    torch.ops.mpamd.moe_gate_up_w8_tiled(x, w8, w_scale, off, tok, out)
+    return out
+
+
+def moe_down_w8_tiled(act, w8, w_scale, off, tok, wsel, idx, T: int, out=None):
+    """y [T, H] = bf16(sum over token t's valid pairs, in ascending expert order, of wsel[p] * (act[p] @
+    down[e]^T)): the down launch into the fp32 per-pair workspace [T, k, H], then ``moe_combine_tiled``.
+    ``idx`` is the int64 [T, k] routing that ``moe_group`` sorted (it names each pair's slot in its token)."""
+    T = int(T)
+    E, N, K, k = _moe_rows_dims(w8, w_scale, off, tok, T)
+    if tuple(act.shape) != (T * k, K):
+        raise ValueError(f"act must be [{T * k}, {K}]")
+    if tuple(wsel.shape) != (T * k,) or wsel.dtype != torch.float32:
+        raise ValueError(f"wsel must be fp32 [{T * k}] routing weights (ops.moe_group)")
+    if tuple(idx.shape) != (T, k) or idx.dtype != torch.int64:
+        raise ValueError(f"idx must be the int64 [{T}, {k}] expert ids (moe.route)")
+    if out is None:
+        out = torch.empty(T, N, dtype=act.dtype, device=act.device)
+    elif tuple(out.shape) != (T, N) or out.dtype != act.dtype:
+        raise ValueError(f"out must be [{T}, {N}] {act.dtype}")
+    ws = _moe_tiled_workspace(T * k * N, act.device)
+    if not _native(act):
+        o, tl = off.tolist(), tok.long()
+        rows = ws.view(T * k, N)
+        for e in range(E):
+            if o[e + 1] > o[e]:
+                t = tl[o[e]:o[e + 1]]
+                j = ((idx[t] >= 0) & (idx[t] < e)).sum(1)
+                ye = act[o[e]:o[e + 1]].float() @ unpack_weight_w8(w8[e], w_scale[e], torch.float32).t()
+                rows[t * k + j] = ye * wsel[o[e]:o[e + 1], None]
+        return moe_combine_tiled(ws, idx, E, out)
+    torch.ops.mpamd.moe_down_w8_tiled(act, w8, w_scale, off, tok, wsel, idx.contiguous(), ws)
+    return moe_combine_tiled(ws, idx, E, out)
+
+
+def moe_combine_tiled(ws, idx, E: int, out):
+    """out[t] = bf16(ws[t, 0] + ws[t, 1] + ...) over the first v_t slots of the fp32 workspace [T, k, H], v_t
+    = token t's expert ids inside [0, E): slots that were never written are never read.  One launch."""
+    T, k = idx.shape
+    if not _native(ws):
+        rows = ws.view(T, k, -1)
+        v = ((idx >= 0) & (idx < E)).sum(1)
+        tot = torch.zeros(T, rows.shape[2], dtype=torch.float32)
+        for j in range(k):
+            tot[v > j] += rows[v > j, j]
+        out.copy_(tot.to(out.dtype))
+        return out
+    torch.ops.mpamd.moe_combine_tiled(ws, idx.contiguous(), out, int(E))
+    return out
+
+
+_MOE_TILED_WS = {}
+
+
+def _moe_tiled_workspace(n: int, device) -> torch.Tensor:
+    """fp32 [T k H] per-pair scratch of ``moe_down_w8_tiled`` (per device, grown on demand; the combine reads
+    only the slots the down launch of the same call wrote)."""
+    ws = _MOE_TILED_WS.get(device)
+    if ws is None or ws.numel() < n:
+        ws = _MOE_TILED_WS[device] = torch.empty(n, dtype=torch.float32, device=device)
+    return ws[:n]
+
+
+# ---------------------------------------------------------------------------------------
 # W4A16 decode GEMM (csrc/gemm_w4.hip mp_gemm_w4): OCP MXFP4 weights - e2m1 codes, one e8m0 scale
 # per 32 weights along K, 4.25 bits per weight - dequantized in registers into the bf16 MFMA
 # (v_cvt_scalef32_pk_bf16_fp4), bf16 activations.  Weight layout, in the bf16 fragment order:

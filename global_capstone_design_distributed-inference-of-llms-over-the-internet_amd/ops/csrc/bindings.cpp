@@ -940,6 +940,74 @@ bool moe_rows_ok(int64_t T, int64_t E, int64_t k, int64_t H, int64_t F) {
   return mp_moe_rows_ok((int)T, (int)E, (int)k, (int)H, (int)F) != 0;
 }
 
+// Tiled grouped MoE GEMMs (gemm_moe_tiled.hip): the _rows arguments, 128-row x up-to-256-column workgroups.
+// idx: the routing that mp_moe_group sorted -> (T, k)
+static std::pair<int64_t, int64_t> check_moe_idx(const at::Tensor& idx, const at::Tensor& like) {
+  MP_CHECK(idx.is_cuda() && idx.scalar_type() == at::kLong && idx.dim() == 2 && idx.is_contiguous() &&
+               idx.numel() > 0 && idx.numel() <= (1 << 16) && idx.device() == like.device(),
+           "idx: int64 [T, k] expert ids (at most 65536 pairs) on the weights' device");
+  return {idx.size(0), idx.size(1)};
+}
+
+// the fp32 per-pair workspace [T, k, H]
+static void check_moe_tiled_ws(const at::Tensor& ws, int64_t n, const at::Tensor& like) {
+  check_moe_vec(ws, at::kFloat, n, like, "ws: fp32 [T, k, H] workspace on the weights' device");
+  MP_CHECK(reinterpret_cast<uintptr_t>(ws.data_ptr()) % 16 == 0, "ws must be 16-B aligned");
+}
+
+void moe_gate_up_w8_tiled(const at::Tensor& x, const at::Tensor& w8, const at::Tensor& wsc, const at::Tensor& off,
+                          const at::Tensor& tok, at::Tensor& out) {
+  const auto [E, N, K] = check_moe_weight(w8, wsc);
+  MP_CHECK(N % 32 == 0, "moe_gate_up_w8_tiled: SwiGLU needs N % 32 == 0");
+  MP_CHECK(x.dim() == 2, "x must be 2-D [T, H]");
+  const int64_t T = x.size(0);
+  const int k = check_moe_pairs(off, tok, T, E, w8);
+  check_moe_rows(x, "x", T, K, w8);
+  check_moe_rows(out, "out", T * k, N / 2, w8);
+  const int rc = mp_moe_gate_up_w8_tiled(x.data_ptr(), w8.data_ptr(), wsc.data_ptr<float>(), off.data_ptr<int32_t>(),
+                                         tok.data_ptr<int32_t>(), out.data_ptr(), (int)T, (int)(T * k), E, K, N / 2,
+                                         cur_stream());
+  TORCH_CHECK(rc != 1, "mpamd: moe_gate_up_w8_tiled: no kernel covers T=", T, " k=", k, " E=", E, " H=", K, " F=", N / 2);
+  check_launch(rc, "moe_gate_up_w8_tiled");
+}
+
+// ws fp32 [T, k, H]: row (t, j) = wsel * (act . down^T) of token t's j-th valid expert, ascending
+void moe_down_w8_tiled(const at::Tensor& act, const at::Tensor& w8, const at::Tensor& wsc, const at::Tensor& off,
+                       const at::Tensor& tok, const at::Tensor& wsel, const at::Tensor& idx, at::Tensor& ws) {
+  const auto [E, N, K] = check_moe_weight(w8, wsc);
+  const auto [T, k] = check_moe_idx(idx, w8);
+  MP_CHECK(check_moe_pairs(off, tok, T, E, w8) == k, "tok: int32 [T k] tokens of idx's pairs");
+  check_moe_rows(act, "act", T * k, K, w8);
+  check_moe_vec(wsel, at::kFloat, T * k, w8, "wsel: fp32 [T k] routing weights on the weights' device");
+  check_moe_tiled_ws(ws, T * k * N, w8);
+  const int rc = mp_moe_down_w8_tiled(act.data_ptr(), w8.data_ptr(), wsc.data_ptr<float>(), off.data_ptr<int32_t>(),
+                                      tok.data_ptr<int32_t>(), wsel.data_ptr<float>(), idx.data_ptr<int64_t>(),
+                                      ws.data_ptr<float>(), (int)T, (int)(T * k), E, N, K, cur_stream());
+  TORCH_CHECK(rc != 1, "mpamd: moe_down_w8_tiled: no kernel covers T=", T, " k=", k, " E=", E, " H=", N, " F=", K);
+  check_launch(rc, "moe_down_w8_tiled");
+}
+
+// y bf16 [T, H] = bf16(sum of ws[t, 0 .. v_t)), v_t = token t's ids in [0, E)
+void moe_combine_tiled(const at::Tensor& ws, const at::Tensor& idx, at::Tensor& y, int64_t E) {
+  check_bf16_cuda(y, "y");
+  check_rows(y, "y");
+  const auto [T, k] = check_moe_idx(idx, y);
+  MP_CHECK(y.size(0) == T && y.size(1) % 4 == 0 && y.stride(0) % 4 == 0, "y: bf16 [T, H] rows, H and stride % 4 == 0");
+  MP_CHECK(E >= 1 && E <= 32, "E: 1 .. 32 experts");
+  check_moe_tiled_ws(ws, T * k * y.size(1), y);
+  const int rc = mp_moe_combine_tiled(ws.data_ptr<float>(), idx.data_ptr<int64_t>(), y.data_ptr(), y.stride(0), (int)T,
+                                      (int)k, (int)E, (int)y.size(1), cur_stream());
+  TORCH_CHECK(rc != 1, "mpamd: moe_combine_tiled: no kernel covers T=", T, " k=", k, " H=", y.size(1));
+  check_launch(rc, "moe_combine_tiled");
+}
+
+bool moe_tiled_ok(int64_t T, int64_t E, int64_t k, int64_t H, int64_t F) {
+  if (T <= 0 || T > (1 << 16) || E <= 0 || E > 64 || k <= 0 || k > E || H <= 0 || F <= 0 || H > (1 << 24) ||
+      F > (1 << 24))
+    return false;
+  return mp_moe_tiled_ok((int)T, (int)E, (int)k, (int)H, (int)F) != 0;
+}
+
 // W8A16 GEMM above 64 rows (gemm_w8_rows.hip mp_gemm_w8_rows): x bf16 row-major [T, K] with a row stride,
 // the fp8 weight in place, out bf16 [T, N'] (any row stride).  The messages name the op's arguments.
 void gemm_w8_rows(const at::Tensor& x, const at::Tensor& w8, const at::Tensor& w_scale, at::Tensor& out,
@@ -1455,6 +1523,12 @@ TORCH_LIBRARY(mpamd, m) {
       "moe_down_w8_rows(Tensor act, Tensor w8, Tensor wsc, Tensor off, Tensor tok, Tensor wsel, Tensor(a!) ws, "
       "Tensor(b!) y) -> ()");
   m.def("moe_rows_ok(int T, int E, int k, int H, int F) -> bool", &moe_rows_ok);
+  m.def("moe_gate_up_w8_tiled(Tensor x, Tensor w8, Tensor wsc, Tensor off, Tensor tok, Tensor(a!) out) -> ()");
+  m.def(
+      "moe_down_w8_tiled(Tensor act, Tensor w8, Tensor wsc, Tensor off, Tensor tok, Tensor wsel, Tensor idx, "
+      "Tensor(a!) ws) -> ()");
+  m.def("moe_combine_tiled(Tensor ws, Tensor idx, Tensor(a!) y, int E) -> ()");
+  m.def("moe_tiled_ok(int T, int E, int k, int H, int F) -> bool", &moe_tiled_ok);
   m.def("gemm_w8_rows(Tensor x, Tensor w8, Tensor w_scale, Tensor(a!) out, int epilogue) -> ()");
   m.def("gemm_w8_rows_ok(int T, int N, int K, int epilogue) -> bool", &gemm_w8_rows_ok);
   m.def("gemm_w4_rows(Tensor x, Tensor w4, Tensor s4, Tensor(a!) out, int epilogue) -> ()");
@@ -1510,6 +1584,9 @@ TORCH_LIBRARY_IMPL(mpamd, CUDA, m) {
   m.impl("moe_group", &moe_group);
   m.impl("moe_gate_up_w8_rows", &moe_gate_up_w8_rows);
   m.impl("moe_down_w8_rows", &moe_down_w8_rows);
+  m.impl("moe_gate_up_w8_tiled", &moe_gate_up_w8_tiled);
+  m.impl("moe_down_w8_tiled", &moe_down_w8_tiled);
+  m.impl("moe_combine_tiled", &moe_combine_tiled);
   m.impl("gemm_w8_rows", &gemm_w8_rows);
   m.impl("gemm_w4_rows", &gemm_w4_rows);
   m.impl("quant_mx_rows", &quant_mx_rows);

@@ -28,14 +28,16 @@ __device__ __forceinline__ void w8r_place(int MB, int& cg, int& mb) {
 struct W8rPlan {
   int wide, MB, NB, nbig, NBB, NBS;
 };
-static bool w8r_plan(int T, int N, int K, int epi, W8rPlan& p) {
+// The rule for MB row blocks of a given geometry: what a kernel whose row blocks are not ceil(T / 128)
+// (gemm_moe_tiled.hip: row-block slots of the experts) shares with the dense ones.
+static bool w8r_plan_blocks(int MB, int wide, int N, int K, int epi, W8rPlan& p) {
   if (epi != 0 && epi != 1) return false;
   const int step = epi == 1 ? 2 : 1;
-  if (T < 65 || N <= 0 || K <= 0 || N % (16 * step) || K % 128) return false;
+  if (MB <= 0 || N <= 0 || K <= 0 || N % (16 * step) || K % 128) return false;
   const int units = (N / 16) / step;
-  p.wide = T > 128;
+  p.wide = wide;
   const int cap = (p.wide ? 16 : 4) / step;  // units a workgroup can hold
-  p.MB = (T + 127) / 128;
+  p.MB = MB;
   int want = sk_num_cus() / p.MB;            // groups for one workgroup per CU
   const int need = (units + cap - 1) / cap;
   if (want < need) want = need;
@@ -49,6 +51,9 @@ static bool w8r_plan(int T, int N, int K, int epi, W8rPlan& p) {
   p.NBS = base * step;
   p.nbig = rem ? rem : p.NB;
   return (int64_t)p.NB * p.MB < (1ll << 31);
+}
+static bool w8r_plan(int T, int N, int K, int epi, W8rPlan& p) {
+  return T >= 65 && w8r_plan_blocks((T + 127) / 128, T > 128, N, K, epi, p);
 }
 
 }  // namespace mp

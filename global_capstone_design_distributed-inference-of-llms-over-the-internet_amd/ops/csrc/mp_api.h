@@ -231,6 +231,18 @@ int mp_moe_down_w8_rows(const void* act, const void* w8, const float* wsc, const
                         const float* wsel, float* ws, void* y, int64_t y_stride, int T, int P, int E, int H, int F,
                         hipStream_t stream);
 int mp_moe_rows_ok(int T, int E, int k, int H, int F);
+// gemm_moe_tiled.hip: the same MLP for large steps (T >= 65) on 128-row x up-to-256-column workgroups, over
+// mp_moe_group's grouping: gate/up + SwiGLU into out [P][F], down into the fp32 per-pair workspace ws
+// [T][k][H] (idx: the int64 [T][k] routing that was grouped), combine into y (row stride y_stride % 4 == 0).
+// The same return codes.
+int mp_moe_gate_up_w8_tiled(const void* x, const void* w8, const float* wsc, const int32_t* off, const int32_t* tok,
+                            void* out, int T, int P, int E, int H, int F, hipStream_t stream);
+int mp_moe_down_w8_tiled(const void* act, const void* w8, const float* wsc, const int32_t* off, const int32_t* tok,
+                         const float* wsel, const int64_t* idx, float* ws, int T, int P, int E, int H, int F,
+                         hipStream_t stream);
+int mp_moe_combine_tiled(const float* ws, const int64_t* idx, void* y, int64_t y_stride, int T, int k, int E, int H,
+                         hipStream_t stream);
+int mp_moe_tiled_ok(int T, int E, int k, int H, int F);
 // gemm_w8_rows.hip: the W8A16 GEMM above 64 rows on ROW-MAJOR bf16 x (x_stride % 8 == 0): M = T >= 65 rows,
 // N % 16 == 0 (SwiGLU: % 32), K % 128 == 0, epilogue 0 / 1 with row-major output; reads x, x_stride, w, wsc,
 // y, y_stride, M, N, K, epilogue.  0, 1 when the shape is not covered (nothing launched), < 0 for a bad call

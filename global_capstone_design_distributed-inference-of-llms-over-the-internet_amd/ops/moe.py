@@ -24,7 +24,12 @@ MI355X execution strategy (runtime/executor.py ``_moe_mlp``):
 * fp8 experts, prefill steps above 64 rows (up to MPAMD_MOE_ROWS; decode steps with
   MPAMD_MOE_ROWS_DECODE=1): the same sparse schedule on the device -
   ``ops.moe_group`` sorts the pairs by expert, ``ops.moe_gate_up_w8_rows`` / ``moe_down_w8_rows`` run
-  every expert over its gathered rows in two launches (ops/csrc/gemm_moe_rows.hip), no host sync.
+  every expert over its gathered rows in two launches (ops/csrc/gemm_moe_rows.hip), no host sync;
+* MPAMD_MOE_TILED=<rows>: fp8 experts of steps of at least that many rows (no upper cap) run, over the same
+  grouping, on ``ops.moe_gate_up_w8_tiled`` / ``moe_down_w8_tiled`` (ops/csrc/gemm_moe_tiled.hip): 128-row
+  blocks of an expert x up to 256 columns per workgroup, so a weight byte is read once per block instead of
+  once per 64 rows; down writes fp32 per-pair rows and a streaming combine adds them in ascending expert
+  order.  Opt-in: the summation order, and so the outputs of the steps it takes, differ from both others.
 """
 from __future__ import annotations
 

@@ -407,6 +407,12 @@ class StageExecutor:
         # tests/golden/executor_paths - unless MPAMD_MOE_ROWS_DECODE=1 sends them to the same kernels
         self._moe_rows_cap = int(os.environ.get("MPAMD_MOE_ROWS", str(MOE_ROWS_DEFAULT)))
         self._moe_rows_decode = os.environ.get("MPAMD_MOE_ROWS_DECODE", "0") == "1"
+        # MPAMD_MOE_TILED=<rows>: steps of at least that many rows (no upper cap but the kernels' shape gate)
+        # take the tiled launches (ops.moe_gate_up_w8_tiled / moe_down_w8_tiled: 128-row blocks, each
+        # expert's weights read once per block) ahead of the row-gathered route.  Unset or 0: off - the
+        # steps it takes change their outputs (a summation order of its own), so it is opt-in;
+        # profiles/moe_tiled/README.md has the measurements a default would be decided on
+        self._moe_tiled_min = int(os.environ.get("MPAMD_MOE_TILED", "0"))
         # W8A16 projections of the row-major path at 65 .. MPAMD_W8_ROWS rows read the fp8 weight in place
         # (_proj_dense); pure decode steps of 65+ sessions keep their recorded launches unless
         # MPAMD_W8_ROWS_DECODE=1, the rule of MPAMD_MOE_ROWS_DECODE
@@ -1420,6 +1426,14 @@ class StageExecutor:
             logits = ops.linear(xn, L.router)
         w, idx = moe.route(logits, k)
         F = cfg.intermediate_size
+        if (self._moe_w8 and not packed and 0 < self._moe_tiled_min <= T and
+                (not st.decode or self._moe_rows_decode) and getattr(L, "gate_up_w8", None) is not None and
+                ops.moe_tiled_ok(T, E, k, H, F)):
+            # MPAMD_MOE_TILED: the same grouping, then the tiled launches (ops/csrc/gemm_moe_tiled.hip)
+            off, tok, wsel = ops.moe_group(idx, w, E)
+            rows = ops.moe_gate_up_w8_tiled(xn, L.gate_up_w8, L.gate_up_ws, off, tok, out=e("moe_rows", (T * k, F)))
+            ops.moe_down_w8_tiled(rows, L.down_w8, L.down_ws, off, tok, wsel, idx, T, out=mlp)
+            return
         if (self._moe_w8 and not packed and 64 < T <= self._moe_rows_cap and
                 (not st.decode or self._moe_rows_decode) and getattr(L, "gate_up_w8", None) is not None and
                 ops.moe_rows_ok(T, E, k, H, F)):

@@ -1,11 +1,13 @@
 """A/B of one Mixtral MoE layer's expert MLP over fp8 weights ABOVE 64 rows: the three row-gathered
-launches (ops.moe_group + moe_gate_up_w8_rows + moe_down_w8_rows) against the dequantizing schedule
+launches (ops.moe_group + moe_gate_up_w8_rows + moe_down_w8_rows), the tiled launches for large steps
+(ops.moe_group + moe_gate_up_w8_tiled + moe_down_w8_tiled: gemm_moe_tiled.hip) and the dequantizing schedule
 they replace (StageExecutor._moe_mlp: argsort + bincount().tolist(), then per routed expert two
 ``ops.unpack_weight_w8``, ``index_select``, two ``ops.linear`` and an ``index_add_``, the bf16 copy).
-Mixtral-8x7B shapes by default (H 4096, F 14336, E 8, top-2), T = 65 .. 2048; the weights rotate over
-``--copies`` layer copies (1.41 GB each: far more than the 256 MB Infinity Cache), the two forms
-alternate round by round, min..max over the rounds is printed.  ``rows_bytes``: the fp8 bytes the new
-launches stream - an expert with c rows streams its 3 H F bytes ceil(c / 64) times.
+Mixtral-8x7B shapes by default (H 4096, F 14336, E 8, top-2), T = 65 .. 2048 (the tiled launches take T >=
+65); the weights rotate over ``--copies`` layer copies (1.41 GB each: far more than the 256 MB Infinity
+Cache), the three forms alternate round by round, min..max over the rounds is printed.  ``rows_bytes``: the
+fp8 bytes the row-gathered launches stream - an expert with c rows streams its 3 H F bytes ceil(c / 64)
+times.  ``tiled_PFLOPs``: 6 T k H F / time.  ``tiled_wins``: its slowest round beats both others' fastest.
 
     python lab/tools/moe_rows_ab.py [--rows 65,128,...] [--rounds 5] [--iters 10] [--out FILE.json]
 """
@@ -45,7 +47,7 @@ def main():
                        torch.full((E, H), 1e-3, device=dev)))
     rows_out = []
     for T in [int(m) for m in a.rows.split(",")]:
-        assert ops.moe_rows_ok(T, E, k, H, F)
+        assert ops.moe_rows_ok(T, E, k, H, F) and ops.moe_tiled_ok(T, E, k, H, F)
         x = torch.randn(T, H, device=dev, generator=g).to(torch.bfloat16)
         w, idx = moe.route(torch.randn(T, E, device=dev, generator=g), k)
         counts = torch.bincount(idx.reshape(-1), minlength=E).tolist()
@@ -58,6 +60,12 @@ def main():
             off, tok, wsel = ops.moe_group(idx, w, E)
             ops.moe_gate_up_w8_rows(x, gu8, gus, off, tok, out=act)
             ops.moe_down_w8_rows(act, dn8, dns, off, tok, wsel, T, out=y)
+
+        def tiled(i):
+            gu8, gus, dn8, dns = layers[i % a.copies]
+            off, tok, wsel = ops.moe_group(idx, w, E)
+            ops.moe_gate_up_w8_tiled(x, gu8, gus, off, tok, out=act)
+            ops.moe_down_w8_tiled(act, dn8, dns, off, tok, wsel, idx, T, out=y)
 
         def dequant(i):
             gu8, gus, dn8, dns = layers[i % a.copies]
@@ -88,13 +96,17 @@ def main():
             torch.cuda.synchronize()
             return t0.elapsed_time(t1) * 1e3 / a.iters  # us per layer
 
-        t = {"rows": [], "dequant": []}
-        for _ in range(a.rounds):  # alternate the two forms
+        t = {"rows": [], "tiled": [], "dequant": []}
+        for _ in range(a.rounds):  # alternate the three forms
             t["rows"].append(timed(rows))
+            t["tiled"].append(timed(tiled))
             t["dequant"].append(timed(dequant))
         nbytes = sum(-(-c // 64) for c in counts) * 3 * H * F
         row = {"T": T, "counts": counts, "rows_us": [min(t["rows"]), max(t["rows"])],
+               "tiled_us": [min(t["tiled"]), max(t["tiled"])],
                "dequant_us": [min(t["dequant"]), max(t["dequant"])], "rows_bytes": nbytes,
+               "tiled_PFLOPs": [6.0 * T * k * H * F / max(t["tiled"]) / 1e9, 6.0 * T * k * H * F / min(t["tiled"]) / 1e9],
+               "tiled_wins": max(t["tiled"]) < min(t["rows"] + t["dequant"]),
                "rows_TBps": [nbytes / max(t["rows"]) / 1e6, nbytes / min(t["rows"]) / 1e6],
                "wins": max(t["rows"]) < min(t["dequant"])}
         rows_out.append(row)
