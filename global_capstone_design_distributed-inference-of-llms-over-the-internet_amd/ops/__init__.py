@@ -2017,9 +2017,10 @@ def linear_w4(x, w4, s4, a_rows: int, out=None, epilogue: int = 0, residual=None
     ``a_rows`` rows (M <= 64): the one-launch ring kernel with the fused-norm path's epilogues (0
     with optional ``ss_in`` row scale, packed SwiGLU, 3 = residual-stream producer).  A shape the
     kernel does not cover raises.  Out of scope for 4-bit weights: the split-K ring,
-    ``linear_partials`` / the qkv fold, a start-up autotuner, W4A8 / W4A4 on the block-scaled
-    MFMA, and MoE / tensor-parallel / offloaded stages.  Steps above 64 rows: ``linear_w4_rows``
-    (row-major activations, epilogue 0 / SwiGLU); the fused-norm epilogues stop at 64 rows."""
+    ``linear_partials`` / the qkv fold, a start-up autotuner, W4A8 at 64 rows and below and W4A4 on
+    the block-scaled MFMA, and MoE / tensor-parallel / offloaded stages.  Steps above 64 rows:
+    ``linear_w4_rows`` (row-major activations, epilogue 0 / SwiGLU) or ``linear_w4mx_rows`` (W4A8-MX, the
+    same arguments); the fused-norm epilogues stop at 64 rows."""
     M = int(a_rows)
     N, K = 16 * w4.shape[0], 128 * w4.shape[1]
     if not _native(x):
@@ -2219,6 +2220,88 @@ def linear_mx_rows(x, w8, w_scale, out=None, epilogue: int = 0):
     ax, as_ = _mx_rows_workspace(T, K, x.device)
     torch.ops.mpamd.quant_mx_rows(x, ax, as_)
     torch.ops.mpamd.gemm_mx_rows(ax, as_, w8, w_scale, out, T, int(epilogue))
+    return out
+
+
+# ---------------------------------------------------------------------------------------
+# W4A8-MX GEMM ABOVE 64 rows (csrc/gemm_w4mx_rows.hip): row-major bf16 activations are quantized to MX e4m3 on
+# NATURAL 32-blocks (k 32 b .. 32 b + 31, the blocks MXFP4 weights have) in one launch (mp_quant_mxn_rows), then
+# multiplied with the MXFP4 codes and block scales in place on the block-scaled MFMA (mp_gemm_w4mx_rows): no
+# fp4 -> bf16 convert.  gemm_w8_rows.hip's two-dimensional split; epilogue 0 or SwiGLU, row-major output.
+_W4MX_ROWS_OK = {}
+
+
+def mxn_block_quant(x: torch.Tensor) -> torch.Tensor:
+    """fp32 reference of ``quant_mxn_rows`` + dequantization on row-major x[M, K]: ``mx_block_quant``'s rule
+    (e8m0 scale of the block maximum, clamp to +-448, e4m3 round to nearest even) on natural blocks of 32
+    consecutive k."""
+    M, K = x.shape
+    v = x.to(torch.bfloat16).float().view(M, K // 32, 32)
+    amax = v.abs().amax(dim=2, keepdim=True)
+    m, ex = torch.frexp(amax / 448.0)
+    e = torch.where(m > 0.5, ex, ex - 1).clamp(-126, 126)  # ceil(log2(amax / 448))
+    e = torch.where(amax > 0, e, torch.zeros_like(e)).float()
+    q = (v * torch.exp2(-e)).clamp(-448.0, 448.0).to(torch.float8_e4m3fn).float()
+    return (q * torch.exp2(e)).view(M, K)
+
+
+def quant_mxn_rows(x: torch.Tensor, axn=None, asn=None):
+    """Row-major bf16 ``x`` [T, K] (unit inner stride, row stride % 8 == 0, K % 128 == 0) -> MX e4m3 bytes +
+    e8m0 scales of natural 32-blocks in the fragment order of ``gemm_w4mx_rows.hip``; the values are
+    ``mxn_block_quant``'s.  ``axn`` / ``asn``: buffers at least as large as ``mx_rows_buffers(T, K)``'s."""
+    if axn is None or asn is None:
+        axn, asn = mx_rows_buffers(x.shape[0], x.shape[1], x.device)
+    torch.ops.mpamd.quant_mxn_rows(x, axn, asn)
+    return axn, asn
+
+
+def w4mx_rows_ok(T: int, N: int, K: int, epilogue: int = 0) -> bool:
+    """Whether ``linear_w4mx_rows`` has a kernel for the shape: T >= 65, N % 16 == 0 (SwiGLU: % 32),
+    K % 128 == 0 (a dry dispatch, as ``w4_rows_ok``)."""
+    key = (int(T), int(N), int(K), int(epilogue))
+    if key not in _W4MX_ROWS_OK:
+        _W4MX_ROWS_OK[key] = bool(native_available() and torch.ops.mpamd.gemm_w4mx_rows_ok(*key))
+    return _W4MX_ROWS_OK[key]
+
+
+def linear_w4mx_rows(x, w4, s4, out=None, epilogue: int = 0):
+    """y [T, N'] = epilogue(mxn_block_quant(x) @ W^T) for row-major ``x`` [T, K] (unit inner stride, row stride
+    % 8 == 0) and an MXFP4 weight (``pack_weight_w4``): the activations are quantized to e4m3 with an e8m0
+    scale per 32 consecutive k and the product runs on the block-scaled MFMA, which reads the e2m1 codes and
+    their block scales as they are.  Epilogue 0 (N' = N) or 1 (SwiGLU over the 16-row gate/up interleave,
+    N' = N / 2).  fp32 accumulation, one rounding to bf16, the same bits on every run.  ``out``: any [T, N']
+    view with unit inner stride.  An uncovered shape is an error on the GPU (``w4mx_rows_ok``); CPU tensors
+    run ``reference.linear`` on the block-quantized activation and the dequantized weight.  The quantizer's
+    workspace is ``linear_mx_rows``'s (per device)."""
+    if w4.dim() != 4 or tuple(w4.shape[2:]) != (64, 16) or w4.dtype != torch.uint8:
+        raise ValueError("w4 must be an MXFP4 weight uint8 [N/16, K/128, 64, 16] (ops.pack_weight_w4)")
+    N, K = 16 * w4.shape[0], 128 * w4.shape[1]
+    if tuple(s4.shape) != (N // 16, K // 128, 16, 4) or s4.dtype != torch.uint8:
+        raise ValueError(f"s4 must be the e8m0 block scales uint8 [{N // 16}, {K // 128}, 16, 4]")
+    if epilogue not in (0, 1):
+        raise ValueError("linear_w4mx_rows: epilogue 0 (store) or 1 (SwiGLU)")
+    if x.dim() != 2 or x.shape[1] != K:
+        raise ValueError(f"x must be row-major [T, {K}]")
+    T, ncols = x.shape[0], N // 2 if epilogue == 1 else N
+    if out is not None and (tuple(out.shape) != (T, ncols) or out.dtype != x.dtype):
+        raise ValueError(f"out must be [{T}, {ncols}] {x.dtype}")
+    if not _native(x):
+        y = ref.linear(mxn_block_quant(x).to(x.dtype), unpack_weight_w4(w4, s4, x.dtype), epilogue=epilogue)
+        if out is not None:
+            out.copy_(y)
+            return out
+        return y
+    if x.dtype != torch.bfloat16:
+        raise ValueError("x must be bf16")
+    if x.stride(1) != 1 or x.stride(0) % 8 or x.stride(0) < K:
+        raise ValueError("x must have unit inner stride and a row stride that is a multiple of 8")
+    if not w4mx_rows_ok(T, N, K, epilogue):
+        raise RuntimeError(f"mpamd: linear_w4mx_rows: no kernel covers T={T} N={N} K={K} epilogue={epilogue}")
+    if out is None:
+        out = torch.empty(T, ncols, dtype=x.dtype, device=x.device)
+    axn, asn = _mx_rows_workspace(T, K, x.device)
+    torch.ops.mpamd.quant_mxn_rows(x, axn, asn)
+    torch.ops.mpamd.gemm_w4mx_rows(axn, asn, w4, s4, out, T, int(epilogue))
     return out
 
 

@@ -1301,6 +1301,57 @@ bool gemm_w4_rows_ok(int64_t T, int64_t N, int64_t K, int64_t epilogue) {
   return mp_gemm_w4_rows_ok((int)T, (int)N, (int)K, (int)epilogue) != 0;
 }
 
+// W4A8-MX GEMM above 64 rows (gemm_w4mx_rows.hip).  The quantizer on natural 32-blocks: quant_mx_rows's
+// arguments, checks and buffer sizes (check_mx_rows_buffers), another byte order inside a step
+void quant_mxn_rows(const at::Tensor& x, at::Tensor& axn, at::Tensor& asn) {
+  MP_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16, "quant_mxn_rows: x must be bf16 on the GPU");
+  MP_CHECK(x.dim() == 2 && x.size(0) >= 1 && x.size(1) >= 128 && x.size(1) % 128 == 0,
+           "quant_mxn_rows: x must be 2-D [T, K] with T >= 1 and K % 128 == 0");
+  const int64_t T = x.size(0), K = x.size(1);
+  MP_CHECK(x.stride(1) == 1 && x.stride(0) % 8 == 0 && x.stride(0) >= K &&
+               reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0,
+           "quant_mxn_rows: x needs unit inner stride, a row stride that is a multiple of 8 and 16-B alignment");
+  MP_CHECK(T < (1ll << 31) && K < (1ll << 31), "quant_mxn_rows: x dimensions exceed 32 bits");
+  check_mx_rows_buffers(axn, asn, T, K, x.device());
+  check_launch(mp_quant_mxn_rows(x.data_ptr(), x.stride(0), axn.data_ptr(), asn.data_ptr(), (int)T, (int)K, cur_stream()),
+               "quant_mxn_rows");
+}
+
+// The GEMM: axn / asn of quant_mxn_rows for T rows, the MXFP4 weight in place, out bf16 [T, N'] (any row stride)
+void gemm_w4mx_rows(const at::Tensor& axn, const at::Tensor& asn, const at::Tensor& w4, const at::Tensor& s4,
+                    at::Tensor& out, int64_t T, int64_t epilogue) {
+  MP_CHECK(w4.is_cuda() && w4.scalar_type() == at::kByte && w4.dim() == 4 && w4.size(2) == 64 && w4.size(3) == 16 &&
+               w4.is_contiguous(),
+           "linear_w4mx_rows: w4 must be a contiguous MXFP4 weight uint8 [N/16, K/128, 64, 16] on the GPU "
+           "(ops.pack_weight_w4)");
+  const int64_t N = 16 * w4.size(0), K = 128 * w4.size(1);
+  MP_CHECK(s4.is_cuda() && s4.scalar_type() == at::kByte && s4.dim() == 4 && s4.size(0) == w4.size(0) &&
+               s4.size(1) == w4.size(1) && s4.size(2) == 16 && s4.size(3) == 4 && s4.is_contiguous() &&
+               s4.device() == w4.device(),
+           "linear_w4mx_rows: s4 must be the contiguous e8m0 block scales uint8 [N/16, K/128, 16, 4] on w4's device");
+  MP_CHECK(epilogue == 0 || epilogue == 1, "linear_w4mx_rows: epilogue 0 (store) or 1 (SwiGLU)");
+  MP_CHECK(T >= 1 && T < (1ll << 31) && N < (1ll << 31) && K < (1ll << 31),
+           "linear_w4mx_rows: T / w4 dimensions out of range");
+  check_mx_rows_buffers(axn, asn, T, K, w4.device());
+  const int64_t ncols = epilogue == 1 ? N / 2 : N;
+  MP_CHECK(out.is_cuda() && out.scalar_type() == at::kBFloat16 && out.device() == w4.device(),
+           "linear_w4mx_rows: out must be bf16 on w4's device");
+  MP_CHECK(out.dim() == 2 && out.size(0) == T && out.size(1) == ncols && out.stride(1) == 1 && out.stride(0) >= ncols,
+           "linear_w4mx_rows: out must be [T, N'] rows with unit inner stride");
+  mp::GemmArgs a = mp::gemm_shape_args((int)T, (int)N, (int)K, (int)epilogue, 0);
+  a.x = axn.data_ptr(), a.as = asn.data_ptr();
+  a.w = w4.data_ptr(), a.wsc = s4.data_ptr();
+  a.y = out.data_ptr(), a.y_stride = out.stride(0);
+  const int rc = mp_gemm_w4mx_rows(&a, cur_stream());
+  TORCH_CHECK(rc != 1, "mpamd: linear_w4mx_rows: no kernel covers T=", T, " N=", N, " K=", K, " epilogue=", epilogue);
+  check_launch(rc, "gemm_w4mx_rows");
+}
+
+bool gemm_w4mx_rows_ok(int64_t T, int64_t N, int64_t K, int64_t epilogue) {
+  if (T <= 0 || N <= 0 || K <= 0 || T >= (1ll << 31) || N >= (1ll << 31) || K >= (1ll << 31)) return false;
+  return mp_gemm_w4mx_rows_ok((int)T, (int)N, (int)K, (int)epilogue) != 0;
+}
+
 // MXFP4 weight -> row-major bf16 [N, K]
 at::Tensor dequant_w4(const at::Tensor& w4, const at::Tensor& s4) {
   check_w4(w4, s4);
@@ -1537,6 +1588,10 @@ TORCH_LIBRARY(mpamd, m) {
   m.def(
       "gemm_mx_rows(Tensor ax, Tensor as_, Tensor w8, Tensor w_scale, Tensor(a!) out, int T, int epilogue) -> ()");
   m.def("gemm_mx_rows_ok(int T, int N, int K, int epilogue) -> bool", &gemm_mx_rows_ok);
+  m.def("quant_mxn_rows(Tensor x, Tensor(a!) axn, Tensor(b!) asn) -> ()");
+  m.def(
+      "gemm_w4mx_rows(Tensor axn, Tensor asn, Tensor w4, Tensor s4, Tensor(a!) out, int T, int epilogue) -> ()");
+  m.def("gemm_w4mx_rows_ok(int T, int N, int K, int epilogue) -> bool", &gemm_w4mx_rows_ok);
   m.def("lora_shrink(Tensor x, Tensor A, Tensor scale, Tensor slots, Tensor(a!) t, int M) -> ()");
   m.def("lora_expand(Tensor t, Tensor B, Tensor slots, Tensor(a!) y) -> ()");
   m.def("lora_ok(int M, int N, int K, int R) -> bool", &lora_ok);
@@ -1591,6 +1646,8 @@ TORCH_LIBRARY_IMPL(mpamd, CUDA, m) {
   m.impl("gemm_w4_rows", &gemm_w4_rows);
   m.impl("quant_mx_rows", &quant_mx_rows);
   m.impl("gemm_mx_rows", &gemm_mx_rows);
+  m.impl("quant_mxn_rows", &quant_mxn_rows);
+  m.impl("gemm_w4mx_rows", &gemm_w4mx_rows);
   m.impl("lora_shrink", &lora_shrink);
   m.impl("lora_expand", &lora_expand);
   m.impl("lora_shrink_rows", &lora_shrink_rows);

@@ -17,8 +17,9 @@
 // there is no per-column accumulator scale.
 //
 // Not built for 4-bit weights (ops.linear_w4 docstring): the split-K ring, partial slabs / the
-// qkv fold, a start-up autotuner, W4A8 / W4A4 on the block-scaled MFMA.  Steps above 64 rows read the
-// same layout in place in gemm_w4_rows.hip (epilogue 0 / SwiGLU on row-major activations).
+// qkv fold, a start-up autotuner, W4A8 at 64 rows and below and W4A4 on the block-scaled MFMA.  Steps above 64
+// rows read the same layout in place in gemm_w4_rows.hip (W4A16) and gemm_w4mx_rows.hip (W4A8-MX on the
+// block-scaled MFMA), epilogue 0 / SwiGLU on row-major activations.
 #include "gemm_kernels.h"
 #include "mxfp4_cvt.h"  // f4w_to_bf16, e8m0_scale: shared with gemm_w4_rows.hip
 

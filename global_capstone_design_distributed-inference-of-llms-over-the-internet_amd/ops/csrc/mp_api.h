@@ -259,6 +259,14 @@ int mp_gemm_w4_rows_ok(int T, int N, int K, int epilogue);
 int mp_quant_mx_rows(const void* x, int64_t xs, void* ax, void* as, int T, int K, hipStream_t stream);
 int mp_gemm_mx_rows(const mp::GemmArgs* a, hipStream_t stream);
 int mp_gemm_mx_rows_ok(int T, int N, int K, int epilogue);
+// gemm_w4mx_rows.hip: the W4A8-MX counterpart above 64 rows (MXFP4 weights in place on the block-scaled MFMA).
+// mp_quant_mxn_rows is mp_quant_mx_rows on NATURAL 32-blocks (block b of a step = k 32 b .. 32 b + 31): the same
+// arguments and buffer sizes, axn byte i of half h of lane 16 q + r = x[16 mt + r][128 kb + 64 h + 16 q + i].
+// mp_gemm_w4mx_rows takes a.x = axn, a.as = asn, w the MXFP4 codes and wsc the e8m0 block scales s4 (as
+// mp_gemm_w4_rows), y / y_stride / M / N / K / epilogue and the return codes of mp_gemm_w8_rows
+int mp_quant_mxn_rows(const void* x, int64_t xs, void* ax, void* as, int T, int K, hipStream_t stream);
+int mp_gemm_w4mx_rows(const mp::GemmArgs* a, hipStream_t stream);
+int mp_gemm_w4mx_rows_ok(int T, int N, int K, int epilogue);
 // lora.hip: 0, 1 when the shape is not covered (needs M <= 64, K % 32 == 0, N % 8 == 0, R % 16 == 0,
 // R <= 192; nothing launched), < 0 for a bad call, else the HIP error.  M == 0 returns 0.
 int mp_lora_ok(int M, int N, int K, int R);

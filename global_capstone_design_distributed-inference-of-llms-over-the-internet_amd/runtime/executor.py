@@ -23,8 +23,8 @@ Replaces the reference's Stage0 / StageSegment / StageLast modules
     MPAMD_MOE_ROWS_DECODE=1, decode steps) here on the row-gathered grouped kernels (device-side grouping +
     two launches, ``_moe_mlp``); the W8A16 projections of a 65 .. MPAMD_W8_ROWS-row step of an fp8 stage
     (dense Llama: all four; Mixtral: qkv / o) read the fp8 weight in place (``_proj_dense``), and so do the
-    four projections of a 65 .. MPAMD_W4_ROWS-row step of a dense MXFP4 stage (``ops.linear_w4_rows``; above
-    the cap, and under TP / offload / --gemm hipblaslt, an MXFP4 stage still dequantizes one projection at
+    four projections of a 65 .. MPAMD_W4_ROWS-row step of a dense MXFP4 stage (``ops.linear_w4_rows``; with
+    MPAMD_W4_MX_ROWS=<rows> W4A8-MX on the block-scaled MFMA instead, ``ops.linear_w4mx_rows``; above the caps, and under TP / offload / --gemm hipblaslt, an MXFP4 stage still dequantizes one projection at
     a time); a LoRA step of 65 .. MPAMD_LORA_ROWS rows (prompts, chunks, mixed and verify steps; decode steps
     with MPAMD_LORA_ROWS_DECODE=1) runs every targeted projection's update as two launches that read the row
     slots on the device (``_lora_dense``, ``ops.lora_update_rows``) instead of a torch loop over runs;
@@ -84,6 +84,11 @@ MX_ROWS_DEFAULT = 0
 # dequantizer being far cheaper than the torch chain the fp8 route replaced), so the route is OFF by default
 # and MPAMD_W4_ROWS=<rows> opts in
 W4_ROWS_DEFAULT = 0
+# the largest step of such a stage whose projections run W4A8-MX on the block-scaled MFMA instead
+# (ops.linear_w4mx_rows: the natural-block activation quantizer + a GEMM that takes the e2m1 codes and their block
+# scales as they are).  It changes the outputs (activations become e4m3 blocks), so it is OFF by default and
+# MPAMD_W4_MX_ROWS=<rows> opts in; profiles/w4mx_rows/README.md has the measurements a default would be decided on
+W4_MX_ROWS_DEFAULT = 0
 # largest LoRA step (rows) whose updates run on the segmented MFMA kernels above 64 rows (ops.lora_update_rows)
 # instead of the torch form by runs (ops.lora_update), by the same rule on the four Llama-2-7B projections
 # at r = 16, one adapter and 64 sessions' runs (profiles/lora_rows/README.md).  MPAMD_LORA_ROWS overrides it,
@@ -425,6 +430,9 @@ class StageExecutor:
         # scales in place, under the same rule for pure decode steps (MPAMD_W4_ROWS_DECODE)
         self._w4_rows_cap = int(os.environ.get("MPAMD_W4_ROWS", str(W4_ROWS_DEFAULT)))
         self._w4_rows_decode = os.environ.get("MPAMD_W4_ROWS_DECODE", "0") == "1"
+        # ... or, at 65 .. MPAMD_W4_MX_ROWS rows, run W4A8-MX (the quantizer + ops.linear_w4mx_rows), tried first,
+        # under the same conditions and MPAMD_W4_ROWS_DECODE
+        self._w4_mx_rows_cap = int(os.environ.get("MPAMD_W4_MX_ROWS", str(W4_MX_ROWS_DEFAULT)))
         # ... and the LoRA updates of a 65 .. MPAMD_LORA_ROWS-row step run as two launches per projection
         # (_lora_rows), pure decode steps keeping their recorded torch form unless MPAMD_LORA_ROWS_DECODE=1
         self._lora_rows_cap = int(os.environ.get("MPAMD_LORA_ROWS", str(LORA_ROWS_DEFAULT)))
@@ -1055,7 +1063,8 @@ class StageExecutor:
         by ``ops.linear_w8_rows`` on a GPU step of 65 .. MPAMD_W8_ROWS rows (not a pure decode step unless
         MPAMD_W8_ROWS_DECODE=1; never under TP, offload or --gemm hipblaslt) - in MX mode by ``ops.linear_mx_rows``
         on a step of 65 .. MPAMD_MX_ROWS rows under the same conditions, tried first -, an MXFP4 layer's by
-        ``ops.linear_w4_rows`` under MPAMD_W4_ROWS / MPAMD_W4_ROWS_DECODE in the same way; everything else dequantizes
+        ``ops.linear_w4_rows`` under MPAMD_W4_ROWS / MPAMD_W4_ROWS_DECODE in the same way - or, tried first, by
+        ``ops.linear_w4mx_rows`` (W4A8-MX) on a step of 65 .. MPAMD_W4_MX_ROWS rows; everything else dequantizes
         the projection (``L.dense``) into ``ops.linear(x, w, out=out, **kw)``.  ``kw``: ``epilogue`` (0 / 1)
         and ``wp``, the packed bf16 copy, which a W8A16 layer does not have and the in-place route ignores."""
         epilogue = kw.get("epilogue", 0)
@@ -1071,6 +1080,12 @@ class StageExecutor:
             w8 = getattr(L, name + "_w8")
             if ops.w8_rows_ok(st.T, 16 * w8.shape[0], 32 * w8.shape[1], epilogue):
                 return ops.linear_w8_rows(x, w8, getattr(L, name + "_ws"), out=out, epilogue=epilogue)
+        if (L.w4 and self.device.type == "cuda" and 64 < st.T <= self._w4_mx_rows_cap and
+                (not st.decode or self._w4_rows_decode) and self._tp is None and self._streamer is None and
+                ops.gemm_policy() != "hipblaslt"):
+            w4 = getattr(L, name + "_w4")
+            if ops.w4mx_rows_ok(st.T, 16 * w4.shape[0], 128 * w4.shape[1], epilogue):
+                return ops.linear_w4mx_rows(x, w4, getattr(L, name + "_s4"), out=out, epilogue=epilogue)
         if (L.w4 and self.device.type == "cuda" and 64 < st.T <= self._w4_rows_cap and
                 (not st.decode or self._w4_rows_decode) and self._tp is None and self._streamer is None and
                 ops.gemm_policy() != "hipblaslt"):
