@@ -1978,6 +1978,123 @@ def _moe_tiled_workspace(n: int, device) -> torch.Tensor:
 
 
 # ---------------------------------------------------------------------------------------
+# The tiled MLP in W8A8-MX form (csrc/gemm_moe_tiled_mx.hip): the same slots, split, workspace and combine, but
+# the activations are quantized to MX e4m3 in SLOT order - one launch ahead of each GEMM - and the fp8 expert
+# weights go to the block-scaled MFMA as they are.  The shape gate is ``moe_tiled_ok``; the outputs differ from
+# the W8A16 form's by the activation quantization, so the executor takes these launches only under
+# MPAMD_MOE_TILED_MX on top of MPAMD_MOE_TILED.
+_MOE_MX_WS = {}
+
+
+def _moe_mx_workspace(S: int, K: int, device):
+    """(ax [S, 8, K/128, 2, 64, 16], as [S, 2, K/128, 64, 4]) views of the flat uint8 scratch of the slot-order
+    quantizer (per device, grown to the largest request, as ``_mx_rows_workspace``)."""
+    na, ns = S * 128 * K, S * 4 * K
+    ws = _MOE_MX_WS.get(device)
+    if ws is None or ws[0].numel() < na or ws[1].numel() < ns:
+        ws = (torch.empty(max(na, ws[0].numel() if ws else 0), dtype=torch.uint8, device=device),
+              torch.empty(max(ns, ws[1].numel() if ws else 0), dtype=torch.uint8, device=device))
+        _MOE_MX_WS[device] = ws
+    return ws[0][:na].view(S, 8, K // 128, 2, 64, 16), ws[1][:ns].view(S, 2, K // 128, 64, 4)
+
+
+def moe_quant_mx_tiled(x, off, tok=None, P=None):
+    """Slot-order MX quantizer of the tiled experts -> (ax uint8 [S, 8, K/128, 2, 64, 16], as_ uint8 [S, 2,
+    K/128, 64, 4]), S = P // 128 + E, views of a per-device workspace that the next call overwrites.  Row p of
+    the pair order is ``x[tok[p]]`` (``tok`` given: ``x`` [T, K], P = tok.numel()) or ``x[p]`` (``x`` [P, K]);
+    slot s holds the s-th 128-row block of the experts' ranges ``off[e] .. off[e + 1]`` in expert order, zero
+    rows with scale 127 past the expert's last pair, in ``quant_mx_rows``' byte order and by ``mx_block_quant``'s
+    rule.  Slots past the last block are left unwritten (CPU form: zero bytes, scale 127)."""
+    if x.dim() != 2 or x.shape[1] % 128 or x.shape[1] < 128:
+        raise ValueError("x must be row-major [rows, K] with K % 128 == 0")
+    E, K = off.numel() - 1, x.shape[1]
+    if off.dtype != torch.int32 or not 1 <= E <= 32:
+        raise ValueError("off must be int32 [E + 1] pair offsets (ops.moe_group), E <= 32")
+    if tok is not None and (tok.dim() != 1 or tok.dtype != torch.int32):
+        raise ValueError("tok must be int32 [P] tokens (ops.moe_group)")
+    n = int(tok.numel() if tok is not None else x.shape[0])
+    P = n if P is None else int(P)
+    if P != n or not 1 <= P <= 1 << 16:
+        raise ValueError(f"P must be the {n} pairs of tok / rows of x, at most 65536")
+    S = P // 128 + E
+    if not _native(x):
+        return _moe_quant_mx_tiled_torch(x, off, tok, S)
+    ax, as_ = _moe_mx_workspace(S, K, x.device)
+    torch.ops.mpamd.moe_quant_mx_tiled(x, off, tok, ax, as_)
+    return ax, as_
+
+
+def _moe_quant_mx_tiled_torch(x, off, tok, S: int):
+    """The torch form of ``moe_quant_mx_tiled``: the slot-order matrix [S * 128, K], ``mx_block_quant``'s scale
+    and codes per block, permuted into the fragment order (csrc/gemm_moe_tiled_mx.hip, Format)."""
+    K, o = x.shape[1], off.tolist()
+    rows = x if tok is None else x[tok.long().clamp(0, x.shape[0] - 1)]
+    m = torch.zeros(S * 128, K, dtype=torch.float32)
+    s = 0
+    for e in range(len(o) - 1):
+        for p0 in range(o[e], o[e + 1], 128):
+            n = min(128, o[e + 1] - p0)
+            m[s * 128:s * 128 + n] = rows[p0:p0 + n].to(torch.bfloat16).float()
+            s += 1
+    v = m.view(S, 8, 16, K // 128, 2, 2, 2, 2, 8)  # [S, mt, r, kb, sh, sl, qh, ql, j]
+    amax = v.abs().amax(dim=(5, 7, 8), keepdim=True)
+    mant, ex = torch.frexp(amax / 448.0)
+    e8 = torch.where(mant > 0.5, ex, ex - 1).clamp(-126, 126)
+    e8 = torch.where(amax > 0, e8, torch.zeros_like(e8))
+    q = (v * torch.exp2(-e8.float())).clamp(-448.0, 448.0).to(torch.float8_e4m3fn).view(torch.uint8)
+    ax = q.permute(0, 1, 3, 4, 6, 7, 2, 5, 8).reshape(S, 8, K // 128, 2, 64, 16)
+    sc = (e8 + 127).to(torch.uint8).view(S, 2, 4, 16, K // 128, 2, 2)  # [S, g, i, r, kb, sh, qh]
+    return ax, sc.permute(0, 1, 4, 5, 6, 3, 2).reshape(S, 2, K // 128, 64, 4)
+
+
+def moe_gate_up_mx_tiled(x, w8, w_scale, off, tok, out=None):
+    """``moe_gate_up_w8_tiled``'s arguments and result shape in W8A8-MX form: out [T k, F] bf16, row p =
+    SwiGLU(mx_block_quant(x[tok[p]]) @ gate_up[e]^T), fp32 SwiGLU, one rounding, the same bits on every run.
+    Runs the slot-order quantizer, then the GEMM; an expert without rows is never read.  CPU tensors: the
+    row-gathered torch form on the block-quantized gathered rows."""
+    if x.dim() != 2:
+        raise ValueError("x must be row-major [T, H]")
+    T = x.shape[0]
+    E, N, K, k = _moe_rows_dims(w8, w_scale, off, tok, T)
+    if x.shape[1] != K:
+        raise ValueError(f"x must be [T, {K}]")
+    if out is None:
+        out = torch.empty(T * k, N // 2, dtype=x.dtype, device=x.device)
+    elif tuple(out.shape) != (T * k, N // 2) or out.dtype != x.dtype:
+        raise ValueError(f"out must be [{T * k}, {N // 2}] {x.dtype}")
+    if not _native(x):
+        xq = mx_block_quant(x[tok.long().clamp(0, T - 1)]).to(x.dtype)
+        return moe_gate_up_w8_rows(xq, w8, w_scale, off, torch.arange(T * k, dtype=torch.int32), out=out)
+    ax, as_ = moe_quant_mx_tiled(x, off, tok)
+    torch.ops.mpamd.moe_gate_up_mx_tiled(ax, as_, w8, w_scale, off, tok, out, T)
+    return out
+
+
+def moe_down_mx_tiled(act, w8, w_scale, off, tok, wsel, idx, T: int, out=None):
+    """``moe_down_w8_tiled``'s arguments and result in W8A8-MX form: y [T, H] = bf16(sum over token t's valid
+    pairs, in ascending expert order, of wsel[p] * (mx_block_quant(act[p]) @ down[e]^T)).  Runs the slot-order
+    quantizer over ``act``, the down launch into the fp32 per-pair workspace, then ``moe_combine_tiled``."""
+    if not _native(act):
+        return moe_down_w8_tiled(mx_block_quant(act).to(act.dtype), w8, w_scale, off, tok, wsel, idx, T, out=out)
+    T = int(T)
+    E, N, K, k = _moe_rows_dims(w8, w_scale, off, tok, T)
+    if tuple(act.shape) != (T * k, K):
+        raise ValueError(f"act must be [{T * k}, {K}]")
+    if tuple(wsel.shape) != (T * k,) or wsel.dtype != torch.float32:
+        raise ValueError(f"wsel must be fp32 [{T * k}] routing weights (ops.moe_group)")
+    if tuple(idx.shape) != (T, k) or idx.dtype != torch.int64:
+        raise ValueError(f"idx must be the int64 [{T}, {k}] expert ids (moe.route)")
+    if out is None:
+        out = torch.empty(T, N, dtype=act.dtype, device=act.device)
+    elif tuple(out.shape) != (T, N) or out.dtype != act.dtype:
+        raise ValueError(f"out must be [{T}, {N}] {act.dtype}")
+    ws = _moe_tiled_workspace(T * k * N, act.device)
+    ax, as_ = moe_quant_mx_tiled(act, off)
+    torch.ops.mpamd.moe_down_mx_tiled(ax, as_, w8, w_scale, off, tok, wsel, idx.contiguous(), ws)
+    return moe_combine_tiled(ws, idx, E, out)
+
+
+# ---------------------------------------------------------------------------------------
 # W4A16 decode GEMM (csrc/gemm_w4.hip mp_gemm_w4): OCP MXFP4 weights - e2m1 codes, one e8m0 scale
 # per 32 weights along K, 4.25 bits per weight - dequantized in registers into the bf16 MFMA
 # (v_cvt_scalef32_pk_bf16_fp4), bf16 activations.  Weight layout, in the bf16 fragment order:

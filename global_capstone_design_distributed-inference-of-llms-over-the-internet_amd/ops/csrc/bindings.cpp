@@ -1008,6 +1008,70 @@ bool moe_tiled_ok(int64_t T, int64_t E, int64_t k, int64_t H, int64_t F) {
   return mp_moe_tiled_ok((int)T, (int)E, (int)k, (int)H, (int)F) != 0;
 }
 
+// Their W8A8-MX form (gemm_moe_tiled_mx.hip).  The slot-order MX activation of P pairs over E experts, depth K:
+// ax uint8 [S * 128 * K] and as uint8 [S * 4 * K] at least, S = P / 128 + E
+static void check_moe_mx_buffers(const at::Tensor& ax, const at::Tensor& as, int64_t P, int64_t E, int64_t K,
+                                 const at::Tensor& like) {
+  const int64_t S = P / 128 + E;
+  MP_CHECK(ax.is_cuda() && ax.scalar_type() == at::kByte && ax.is_contiguous() && ax.device() == like.device() &&
+               ax.numel() >= S * 128 * K && reinterpret_cast<uintptr_t>(ax.data_ptr()) % 16 == 0,
+           "moe_mx_tiled: ax must be contiguous uint8 [S, 8, K/128, 2, 64, 16], S = P / 128 + E, on the input's device");
+  MP_CHECK(as.is_cuda() && as.scalar_type() == at::kByte && as.is_contiguous() && as.device() == like.device() &&
+               as.numel() >= S * 4 * K && reinterpret_cast<uintptr_t>(as.data_ptr()) % 4 == 0,
+           "moe_mx_tiled: as must be contiguous uint8 [S, 2, K/128, 64, 4], S = P / 128 + E, on the input's device");
+}
+
+// x bf16 [T, K] with tok int32 [P] (row p of the pair order = x[tok[p]]) or [P, K] without (in place)
+void moe_quant_mx_tiled(const at::Tensor& x, const at::Tensor& off, const c10::optional<at::Tensor>& tok, at::Tensor& ax,
+                        at::Tensor& as) {
+  MP_CHECK(x.dim() == 2 && x.size(1) >= 128 && x.size(1) % 128 == 0, "moe_quant_mx_tiled: x must be 2-D with K % 128 == 0");
+  const int64_t T = x.size(0), K = x.size(1), E = off.numel() - 1;
+  MP_CHECK(E >= 1 && E <= 32, "moe_quant_mx_tiled: off int32 [E + 1], 1 <= E <= 32");
+  check_moe_rows(x, "x", T, K, x);
+  const int64_t P = tok.has_value() ? check_moe_pairs(off, *tok, T, (int)E, x) * T : T;
+  check_moe_vec(off, at::kInt, E + 1, x, "off: int32 [E + 1] pair offsets on the input's device");
+  MP_CHECK(P <= (1 << 16) && K < (1ll << 24), "moe_quant_mx_tiled: at most 65536 pairs");
+  check_moe_mx_buffers(ax, as, P, E, K, x);
+  const int rc = mp_moe_quant_mx_tiled(x.data_ptr(), off.data_ptr<int32_t>(),
+                                       tok.has_value() ? tok->data_ptr<int32_t>() : nullptr, ax.data_ptr(),
+                                       as.data_ptr(), (int)T, (int)P, (int)E, (int)K, cur_stream());
+  TORCH_CHECK(rc != 1, "mpamd: moe_quant_mx_tiled: no kernel covers P=", P, " E=", E, " K=", K);
+  check_launch(rc, "moe_quant_mx_tiled");
+}
+
+// out bf16 [T k, F] from ax / as = moe_quant_mx_tiled(x [T, H], off, tok)
+void moe_gate_up_mx_tiled(const at::Tensor& ax, const at::Tensor& as, const at::Tensor& w8, const at::Tensor& wsc,
+                          const at::Tensor& off, const at::Tensor& tok, at::Tensor& out, int64_t T) {
+  const auto [E, N, K] = check_moe_weight(w8, wsc);
+  MP_CHECK(N % 32 == 0, "moe_gate_up_mx_tiled: SwiGLU needs N % 32 == 0");
+  const int k = check_moe_pairs(off, tok, T, E, w8);
+  check_moe_mx_buffers(ax, as, T * k, E, K, w8);
+  check_moe_rows(out, "out", T * k, N / 2, w8);
+  const int rc = mp_moe_gate_up_mx_tiled(ax.data_ptr(), as.data_ptr(), w8.data_ptr(), wsc.data_ptr<float>(),
+                                         off.data_ptr<int32_t>(), out.data_ptr(), (int)T, (int)(T * k), E, K, N / 2,
+                                         cur_stream());
+  TORCH_CHECK(rc != 1, "mpamd: moe_gate_up_mx_tiled: no kernel covers T=", T, " k=", k, " E=", E, " H=", K, " F=", N / 2);
+  check_launch(rc, "moe_gate_up_mx_tiled");
+}
+
+// ws fp32 [T, k, H] from ax / as = moe_quant_mx_tiled(act [T k, F], off); moe_combine_tiled follows
+void moe_down_mx_tiled(const at::Tensor& ax, const at::Tensor& as, const at::Tensor& w8, const at::Tensor& wsc,
+                       const at::Tensor& off, const at::Tensor& tok, const at::Tensor& wsel, const at::Tensor& idx,
+                       at::Tensor& ws) {
+  const auto [E, N, K] = check_moe_weight(w8, wsc);
+  const auto [T, k] = check_moe_idx(idx, w8);
+  MP_CHECK(check_moe_pairs(off, tok, T, E, w8) == k, "tok: int32 [T k] tokens of idx's pairs");
+  check_moe_mx_buffers(ax, as, T * k, E, K, w8);
+  check_moe_vec(wsel, at::kFloat, T * k, w8, "wsel: fp32 [T k] routing weights on the weights' device");
+  check_moe_tiled_ws(ws, T * k * N, w8);
+  const int rc = mp_moe_down_mx_tiled(ax.data_ptr(), as.data_ptr(), w8.data_ptr(), wsc.data_ptr<float>(),
+                                      off.data_ptr<int32_t>(), tok.data_ptr<int32_t>(), wsel.data_ptr<float>(),
+                                      idx.data_ptr<int64_t>(), ws.data_ptr<float>(), (int)T, (int)(T * k), E, N, K,
+                                      cur_stream());
+  TORCH_CHECK(rc != 1, "mpamd: moe_down_mx_tiled: no kernel covers T=", T, " k=", k, " E=", E, " H=", N, " F=", K);
+  check_launch(rc, "moe_down_mx_tiled");
+}
+
 // W8A16 GEMM above 64 rows (gemm_w8_rows.hip mp_gemm_w8_rows): x bf16 row-major [T, K] with a row stride,
 // the fp8 weight in place, out bf16 [T, N'] (any row stride).  The messages name the op's arguments.
 void gemm_w8_rows(const at::Tensor& x, const at::Tensor& w8, const at::Tensor& w_scale, at::Tensor& out,
@@ -1580,6 +1644,13 @@ TORCH_LIBRARY(mpamd, m) {
       "Tensor(a!) ws) -> ()");
   m.def("moe_combine_tiled(Tensor ws, Tensor idx, Tensor(a!) y, int E) -> ()");
   m.def("moe_tiled_ok(int T, int E, int k, int H, int F) -> bool", &moe_tiled_ok);
+  m.def("moe_quant_mx_tiled(Tensor x, Tensor off, Tensor? tok, Tensor(a!) ax, Tensor(b!) as_) -> ()");
+  m.def(
+      "moe_gate_up_mx_tiled(Tensor ax, Tensor as_, Tensor w8, Tensor wsc, Tensor off, Tensor tok, Tensor(a!) out, "
+      "int T) -> ()");
+  m.def(
+      "moe_down_mx_tiled(Tensor ax, Tensor as_, Tensor w8, Tensor wsc, Tensor off, Tensor tok, Tensor wsel, "
+      "Tensor idx, Tensor(a!) ws) -> ()");
   m.def("gemm_w8_rows(Tensor x, Tensor w8, Tensor w_scale, Tensor(a!) out, int epilogue) -> ()");
   m.def("gemm_w8_rows_ok(int T, int N, int K, int epilogue) -> bool", &gemm_w8_rows_ok);
   m.def("gemm_w4_rows(Tensor x, Tensor w4, Tensor s4, Tensor(a!) out, int epilogue) -> ()");
@@ -1642,6 +1713,9 @@ TORCH_LIBRARY_IMPL(mpamd, CUDA, m) {
   m.impl("moe_gate_up_w8_tiled", &moe_gate_up_w8_tiled);
   m.impl("moe_down_w8_tiled", &moe_down_w8_tiled);
   m.impl("moe_combine_tiled", &moe_combine_tiled);
+  m.impl("moe_quant_mx_tiled", &moe_quant_mx_tiled);
+  m.impl("moe_gate_up_mx_tiled", &moe_gate_up_mx_tiled);
+  m.impl("moe_down_mx_tiled", &moe_down_mx_tiled);
   m.impl("gemm_w8_rows", &gemm_w8_rows);
   m.impl("gemm_w4_rows", &gemm_w4_rows);
   m.impl("quant_mx_rows", &quant_mx_rows);

@@ -42,34 +42,9 @@
 // independent multiplies and combine's adds, v_pk_mul_f32 / v_pk_add_f32 round each half as the scalar forms
 // do, nothing here can contract to an fma, and no other kernel has to match these outputs bit for bit (the
 // route is opt-in because its summation order is its own).  Registers / LDS / scratch: profiles/moe_tiled.
-#include <cstdlib>
-
-#include "gemm_rows_plan.h"
+#include "moe_tiled_common.h"
 
 namespace mp {
-
-constexpr int MT_MAX_E = 32;
-constexpr int MT_MAX_PAIRS = 1 << 16;
-constexpr int MT_BM = 128;  // rows of a slot
-
-// slot -> expert e, first pair p0 and rows n (1 .. 128) of its block.  False: past the last real block.
-// Every range is clamped to [0, P], so whatever off[] holds, p0 + n <= P.
-__device__ __forceinline__ bool mt_slot(const int32_t* __restrict__ off, int E, int P, int slot, int& e, int& p0,
-                                        int& n) {
-  int first = 0;
-  for (e = 0; e < E; ++e) {
-    const int lo = __builtin_amdgcn_readfirstlane(max(off[e], 0));
-    const int hi = __builtin_amdgcn_readfirstlane(min(off[e + 1], P));
-    const int nb = hi > lo ? (hi - lo + MT_BM - 1) / MT_BM : 0;
-    if (slot < first + nb) {
-      p0 = lo + (slot - first) * MT_BM;
-      n = min(MT_BM, hi - p0);
-      return true;
-    }
-    first += nb;
-  }
-  return false;
-}
 
 // DOWN = false: gate/up (x gathered through tok, SwiGLU, bf16 rows of out).  DOWN = true: act rows in place,
 // fp32 rows of the per-pair workspace.  Addresses first (kernarg preload, gemm_kernels.h KERNARG ORDER).
@@ -246,20 +221,6 @@ __global__ __launch_bounds__(MT_CB) void moe_combine_tiled_kernel(const float* _
 #pragma unroll
   for (int j = 0; j < 4; ++j) o[j] = f2bf(s[j]);
   *reinterpret_cast<u16x4*>(y + (int64_t)t * ys + col) = o;
-}
-
-static bool tiled_shape_ok(int T, int E, int k, int H, int F) {
-  return T >= 65 && E > 0 && E <= MT_MAX_E && k > 0 && k <= E && (int64_t)T * k <= MT_MAX_PAIRS && H > 0 && F > 0 &&
-         H % 128 == 0 && F % 128 == 0;
-}
-
-// blockIdx order of the two GEMM launches (file header, Placement): a lab knob, read once
-static int tiled_order() {
-  static const int order = [] {
-    const char* s = std::getenv("MPAMD_MOE_TILED_ORDER");
-    return s != nullptr && s[0] == '1' ? 1 : 0;
-  }();
-  return order;
 }
 
 // One GEMM launch: N output channels (gate/up: 2F, SwiGLU pairs), depth K, over S = P / 128 + E slots.

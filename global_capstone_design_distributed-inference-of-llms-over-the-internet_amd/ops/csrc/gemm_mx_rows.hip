@@ -51,8 +51,8 @@
 //
 // Deterministic: no atomics, no k split, every wave walks K upwards.  Nothing outside ax, as, the weight, the
 // scales and y[0:T, 0:N'] is touched.  Registers / LDS / scratch: profiles/mx_rows/README.md.
-#include "gemm_rows_plan.h"
 #include "mx_common.h"
+#include "mx_rows_stage.h"
 
 namespace mp {
 
@@ -100,19 +100,7 @@ __global__ __launch_bounds__(256) void quant_mx_rows_kernel(const bf16_t* __rest
   }
 }
 
-template <int MW, int NW, int WM, int WN>
-struct MxrGeom {
-  static constexpr int WAVES = WM * WN, THREADS = WAVES * 64;
-  static constexpr int BMT = WM * MW, BM = 16 * BMT;     // row tiles / rows per block
-  static constexpr int FA = 2 * BMT;                     // 1 KiB activation fragments per stage
-  static constexpr int J = FA / WAVES;                   // fragment loads per wave per stage
-  static constexpr int STAGE_BYTES = FA * 1024 + WM * 256;  // + one scale dword per lane and row wave
-  static constexpr int LDS_BYTES = 2 * STAGE_BYTES;
-  static_assert(MW == 4, "a row wave is one group of four row tiles: one scale dword per lane");
-  static_assert(FA % WAVES == 0 && WM <= WAVES, "every wave loads the same number of fragments");
-  static_assert(LDS_BYTES <= W8R_LDS_BYTES, "LDS budget of gemm_t2d.h");
-};
-
+// MxrGeom and the stage macros (MXR_*): mx_rows_stage.h, shared with gemm_moe_tiled_mx.hip.
 // Addresses first (kernarg preload, gemm_kernels.h KERNARG ORDER).
 template <int MW, int NW, int WM, int WN, int EPI>
 __global__ __launch_bounds__(WM* WN * 64) void gemm_mx_rows_kernel(const uint8_t* __restrict__ ax,
@@ -168,69 +156,7 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_mx_rows_kernel(const uint8_t
   u32x4 stg[J];
   unsigned stgs = 0;
   u32x8 rb[2][NW];
-#define MXR_LOAD_A(st)                                                                                   \
-  {                                                                                                      \
-    const int s_ = min(st, nst - 1);                                                                     \
-    _Pragma("unroll") for (int j = 0; j < J; ++j) stg[j] =                                               \
-        *reinterpret_cast<const u32x4*>(xp[j] + ((int64_t)s_ << 11));                                    \
-    if (wid < WM) stgs = *reinterpret_cast<const unsigned*>(sp + ((int64_t)s_ << 8));                    \
-  }
-#define MXR_STORE_A(buf)                                                                                 \
-  {                                                                                                      \
-    _Pragma("unroll") for (int j = 0; j < J; ++j) *reinterpret_cast<u32x4*>(                             \
-        smem + (buf) * SB + (wid + WAVES * j) * 1024 + lane * 16) = stg[j];                              \
-    if (wid < WM) *reinterpret_cast<unsigned*>(smem + (buf) * SB + SOFF + wid * 256 + lane * 4) = stgs;  \
-  }
-#define MXR_LOAD_B(d, st)                                                                                \
-  {                                                                                                      \
-    const int s_ = min(st, nst - 1);                                                                     \
-    _Pragma("unroll") for (int t = 0; t < NW; ++t) {                                                     \
-      const u32x2* p_ = reinterpret_cast<const u32x2*>(wb + (((int64_t)tc[t] * nks + 4 * s_) << 9));     \
-      const u32x2 w0 = p_[0], w1 = p_[64], w2 = p_[128], w3 = p_[192];                                   \
-      rb[d][t] = (u32x8){w0[0], w0[1], w1[0], w1[1], w2[0], w2[1], w3[0], w3[1]};                        \
-    }                                                                                                    \
-  }
-#define MXR_MMA(d)                                                                                       \
-  {                                                                                                      \
-    const unsigned char* sb_ = smem + (d) * SB;                                                          \
-    const unsigned sa_ = *reinterpret_cast<const unsigned*>(sb_ + SOFF + wm * 256 + lane * 4);           \
-    u32x8 a_[MW];                                                                                        \
-    _Pragma("unroll") for (int mt = 0; mt < MW; ++mt) {                                                  \
-      const unsigned char* f_ = sb_ + (wm * MW + mt) * 2048 + lane * 16;                                 \
-      const u32x4 a0 = *reinterpret_cast<const u32x4*>(f_), a1 = *reinterpret_cast<const u32x4*>(f_ + 1024); \
-      a_[mt] = (u32x8){a0[0], a0[1], a0[2], a0[3], a1[0], a1[1], a1[2], a1[3]};                          \
-    }                                                                                                    \
-    _Pragma("unroll") for (int t = 0; t < NW; ++t) {                                                     \
-      if (t < ntw) {                                                                                     \
-        _Pragma("unroll") for (int mt = 0; mt < MW; ++mt) acc[mt][t] =                                   \
-            mfma_mx(a_[mt], rb[d][t], sa_ >> (8 * mt), acc[mt][t]);                                      \
-      }                                                                                                  \
-    }                                                                                                    \
-  }
-
-  MXR_LOAD_A(0)
-  MXR_LOAD_B(0, 0)
-  MXR_STORE_A(0)
-  MXR_LOAD_A(1)
-  lds_barrier();
-  // at the top of step s: LDS buffer s & 1 holds stage s of A, stg stage s + 1 (in flight), ring slot
-  // s & 1 stage s of B
-  for (int s0 = 0; s0 < nst; s0 += 2) {
-#pragma unroll
-    for (int d = 0; d < 2; ++d) {
-      const int s = s0 + d;
-      if (s >= nst) break;
-      MXR_LOAD_B(d ^ 1, s + 1)
-      MXR_MMA(d)
-      MXR_STORE_A(d ^ 1)  // (at s = nst - 1 a clamped copy nobody reads: no branch around the pipeline)
-      MXR_LOAD_A(s + 2)
-      lds_barrier();
-    }
-  }
-#undef MXR_MMA
-#undef MXR_LOAD_B
-#undef MXR_STORE_A
-#undef MXR_LOAD_A
+  MXR_PIPELINE()
 
   // epilogue: scales in fp32, one rounding; rows past T and tiles past ntw store nothing
 #pragma unroll

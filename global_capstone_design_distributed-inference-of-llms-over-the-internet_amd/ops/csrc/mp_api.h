@@ -243,6 +243,17 @@ int mp_moe_down_w8_tiled(const void* act, const void* w8, const float* wsc, cons
 int mp_moe_combine_tiled(const float* ws, const int64_t* idx, void* y, int64_t y_stride, int T, int k, int E, int H,
                          hipStream_t stream);
 int mp_moe_tiled_ok(int T, int E, int k, int H, int F);
+// gemm_moe_tiled_mx.hip: the W8A8-MX form of the two GEMMs (the same shapes, weights and return codes; the
+// combine above follows).  mp_moe_quant_mx_tiled writes the slot-order MX activation - x bf16 contiguous [T][K]
+// gathered through tok, or [P][K] in place when tok is null - into ax uint8 [S][8][K/128][2][64][16] and as
+// uint8 [S][2][K/128][64][4], S = P / 128 + E (live slots only); the GEMMs take ax / as of K = H and K = F
+int mp_moe_quant_mx_tiled(const void* x, const int32_t* off, const int32_t* tok, void* ax, void* as, int T, int P,
+                          int E, int K, hipStream_t stream);
+int mp_moe_gate_up_mx_tiled(const void* ax, const void* as, const void* w8, const float* wsc, const int32_t* off,
+                            void* out, int T, int P, int E, int H, int F, hipStream_t stream);
+int mp_moe_down_mx_tiled(const void* ax, const void* as, const void* w8, const float* wsc, const int32_t* off,
+                         const int32_t* tok, const float* wsel, const int64_t* idx, float* ws, int T, int P, int E,
+                         int H, int F, hipStream_t stream);
 // gemm_w8_rows.hip: the W8A16 GEMM above 64 rows on ROW-MAJOR bf16 x (x_stride % 8 == 0): M = T >= 65 rows,
 // N % 16 == 0 (SwiGLU: % 32), K % 128 == 0, epilogue 0 / 1 with row-major output; reads x, x_stride, w, wsc,
 // y, y_stride, M, N, K, epilogue.  0, 1 when the shape is not covered (nothing launched), < 0 for a bad call

@@ -29,7 +29,11 @@ MI355X execution strategy (runtime/executor.py ``_moe_mlp``):
   grouping, on ``ops.moe_gate_up_w8_tiled`` / ``moe_down_w8_tiled`` (ops/csrc/gemm_moe_tiled.hip): 128-row
   blocks of an expert x up to 256 columns per workgroup, so a weight byte is read once per block instead of
   once per 64 rows; down writes fp32 per-pair rows and a streaming combine adds them in ascending expert
-  order.  Opt-in: the summation order, and so the outputs of the steps it takes, differ from both others.
+  order.  Opt-in: the summation order, and so the outputs of the steps it takes, differ from both others;
+* MPAMD_MOE_TILED_MX=1 on top of it: those steps run the W8A8-MX form (``ops.moe_gate_up_mx_tiled`` /
+  ``moe_down_mx_tiled``, ops/csrc/gemm_moe_tiled_mx.hip): a slot-order quantizer writes each GEMM's input as MX
+  e4m3 blocks and the fp8 expert weights go to the block-scaled MFMA unconverted.  Opt-in: the activation
+  quantization changes outputs.
 """
 from __future__ import annotations
 

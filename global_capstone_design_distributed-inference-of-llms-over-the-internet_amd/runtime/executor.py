@@ -418,6 +418,11 @@ class StageExecutor:
         # steps it takes change their outputs (a summation order of its own), so it is opt-in;
         # profiles/moe_tiled/README.md has the measurements a default would be decided on
         self._moe_tiled_min = int(os.environ.get("MPAMD_MOE_TILED", "0"))
+        # MPAMD_MOE_TILED_MX=1: the steps that take the tiled launches run them in W8A8-MX form
+        # (ops.moe_gate_up_mx_tiled / moe_down_mx_tiled: activations quantized to MX e4m3 in slot order, the
+        # fp8 weights on the block-scaled MFMA).  No effect on any other step, or without MPAMD_MOE_TILED;
+        # opt-in: the activation quantization changes outputs (profiles/moe_tiled_mx/README.md)
+        self._moe_tiled_mx = os.environ.get("MPAMD_MOE_TILED_MX", "0") == "1"
         # W8A16 projections of the row-major path at 65 .. MPAMD_W8_ROWS rows read the fp8 weight in place
         # (_proj_dense); pure decode steps of 65+ sessions keep their recorded launches unless
         # MPAMD_W8_ROWS_DECODE=1, the rule of MPAMD_MOE_ROWS_DECODE
@@ -1444,10 +1449,13 @@ class StageExecutor:
         if (self._moe_w8 and not packed and 0 < self._moe_tiled_min <= T and
                 (not st.decode or self._moe_rows_decode) and getattr(L, "gate_up_w8", None) is not None and
                 ops.moe_tiled_ok(T, E, k, H, F)):
-            # MPAMD_MOE_TILED: the same grouping, then the tiled launches (ops/csrc/gemm_moe_tiled.hip)
+            # MPAMD_MOE_TILED: the same grouping, then the tiled launches (ops/csrc/gemm_moe_tiled.hip), or with
+            # MPAMD_MOE_TILED_MX their W8A8-MX form (ops/csrc/gemm_moe_tiled_mx.hip)
             off, tok, wsel = ops.moe_group(idx, w, E)
-            rows = ops.moe_gate_up_w8_tiled(xn, L.gate_up_w8, L.gate_up_ws, off, tok, out=e("moe_rows", (T * k, F)))
-            ops.moe_down_w8_tiled(rows, L.down_w8, L.down_ws, off, tok, wsel, idx, T, out=mlp)
+            gate_up, down = ((ops.moe_gate_up_mx_tiled, ops.moe_down_mx_tiled) if self._moe_tiled_mx else
+                             (ops.moe_gate_up_w8_tiled, ops.moe_down_w8_tiled))
+            rows = gate_up(xn, L.gate_up_w8, L.gate_up_ws, off, tok, out=e("moe_rows", (T * k, F)))
+            down(rows, L.down_w8, L.down_ws, off, tok, wsel, idx, T, out=mlp)
             return
         if (self._moe_w8 and not packed and 64 < T <= self._moe_rows_cap and
                 (not st.decode or self._moe_rows_decode) and getattr(L, "gate_up_w8", None) is not None and

@@ -1,11 +1,13 @@
 """A/B of one Mixtral MoE layer's expert MLP over fp8 weights ABOVE 64 rows: the three row-gathered
 launches (ops.moe_group + moe_gate_up_w8_rows + moe_down_w8_rows), the tiled launches for large steps
-(ops.moe_group + moe_gate_up_w8_tiled + moe_down_w8_tiled: gemm_moe_tiled.hip) and the dequantizing schedule
-they replace (StageExecutor._moe_mlp: argsort + bincount().tolist(), then per routed expert two
+(ops.moe_group + moe_gate_up_w8_tiled + moe_down_w8_tiled: gemm_moe_tiled.hip), their W8A8-MX form
+(moe_gate_up_mx_tiled + moe_down_mx_tiled: gemm_moe_tiled_mx.hip) and the dequantizing schedule they replace (StageExecutor._moe_mlp: argsort + bincount().tolist(), then per routed expert two
 ``ops.unpack_weight_w8``, ``index_select``, two ``ops.linear`` and an ``index_add_``, the bf16 copy).
 Mixtral-8x7B shapes by default (H 4096, F 14336, E 8, top-2), T = 65 .. 2048 (the tiled launches take T >=
 65); the weights rotate over ``--copies`` layer copies (1.41 GB each: far more than the 256 MB Infinity
-Cache), the three forms alternate round by round, min..max over the rounds is printed.  ``rows_bytes``: the
+Cache), the forms (``--forms``) alternate round by round, min..max over the rounds is printed.  ``mx_quant_us``: the MX
+form's two quantizer launches alone (their share of ``tiled_mx_us``); ``mx_wins``: the MX form's slowest round
+beats the W8A16 tiled form's fastest.  ``rows_bytes``: the
 fp8 bytes the row-gathered launches stream - an expert with c rows streams its 3 H F bytes ceil(c / 64)
 times.  ``tiled_PFLOPs``: 6 T k H F / time.  ``tiled_wins``: its slowest round beats both others' fastest.
 
@@ -33,6 +35,7 @@ def main():
     ap.add_argument("--copies", type=int, default=3)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--iters", type=int, default=10)
+    ap.add_argument("--forms", default="rows,tiled,tiled_mx,dequant")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     dev = torch.device("cuda")
@@ -47,7 +50,8 @@ def main():
                        torch.full((E, H), 1e-3, device=dev)))
     rows_out = []
     for T in [int(m) for m in a.rows.split(",")]:
-        assert ops.moe_rows_ok(T, E, k, H, F) and ops.moe_tiled_ok(T, E, k, H, F)
+        forms = a.forms.split(",")
+        assert ("rows" not in forms or ops.moe_rows_ok(T, E, k, H, F)) and ops.moe_tiled_ok(T, E, k, H, F)
         x = torch.randn(T, H, device=dev, generator=g).to(torch.bfloat16)
         w, idx = moe.route(torch.randn(T, E, device=dev, generator=g), k)
         counts = torch.bincount(idx.reshape(-1), minlength=E).tolist()
@@ -66,6 +70,18 @@ def main():
             off, tok, wsel = ops.moe_group(idx, w, E)
             ops.moe_gate_up_w8_tiled(x, gu8, gus, off, tok, out=act)
             ops.moe_down_w8_tiled(act, dn8, dns, off, tok, wsel, idx, T, out=y)
+
+        def tiled_mx(i):
+            gu8, gus, dn8, dns = layers[i % a.copies]
+            off, tok, wsel = ops.moe_group(idx, w, E)
+            ops.moe_gate_up_mx_tiled(x, gu8, gus, off, tok, out=act)
+            ops.moe_down_mx_tiled(act, dn8, dns, off, tok, wsel, idx, T, out=y)
+
+        off0, tok0, _ = ops.moe_group(idx, w, E)
+
+        def mx_quant(i):  # the MX form's two quantizer launches alone
+            ops.moe_quant_mx_tiled(x, off0, tok0)
+            ops.moe_quant_mx_tiled(act, off0)
 
         def dequant(i):
             gu8, gus, dn8, dns = layers[i % a.copies]
@@ -96,19 +112,29 @@ def main():
             torch.cuda.synchronize()
             return t0.elapsed_time(t1) * 1e3 / a.iters  # us per layer
 
-        t = {"rows": [], "tiled": [], "dequant": []}
-        for _ in range(a.rounds):  # alternate the three forms
-            t["rows"].append(timed(rows))
-            t["tiled"].append(timed(tiled))
-            t["dequant"].append(timed(dequant))
+        fns = {"rows": rows, "tiled": tiled, "tiled_mx": tiled_mx, "dequant": dequant}
+        if "tiled_mx" in forms:
+            forms.append("mx_quant")
+            fns["mx_quant"] = mx_quant
+        t = {f: [] for f in forms}
+        for _ in range(a.rounds):  # alternate the forms
+            for f in forms:
+                t[f].append(timed(fns[f]))
         nbytes = sum(-(-c // 64) for c in counts) * 3 * H * F
-        row = {"T": T, "counts": counts, "rows_us": [min(t["rows"]), max(t["rows"])],
-               "tiled_us": [min(t["tiled"]), max(t["tiled"])],
-               "dequant_us": [min(t["dequant"]), max(t["dequant"])], "rows_bytes": nbytes,
-               "tiled_PFLOPs": [6.0 * T * k * H * F / max(t["tiled"]) / 1e9, 6.0 * T * k * H * F / min(t["tiled"]) / 1e9],
-               "tiled_wins": max(t["tiled"]) < min(t["rows"] + t["dequant"]),
-               "rows_TBps": [nbytes / max(t["rows"]) / 1e6, nbytes / min(t["rows"]) / 1e6],
-               "wins": max(t["rows"]) < min(t["dequant"])}
+        pflops = lambda us: [6.0 * T * k * H * F / max(us) / 1e9, 6.0 * T * k * H * F / min(us) / 1e9]  # noqa: E731
+        row = {"T": T, "counts": counts, "rows_bytes": nbytes}
+        row.update({f + "_us": [min(v), max(v)] for f, v in t.items()})
+        row["tiled_PFLOPs"] = pflops(t["tiled"])
+        if "tiled_mx" in forms:
+            row["tiled_mx_PFLOPs"] = pflops(t["tiled_mx"])
+            row["mx_wins"] = max(t["tiled_mx"]) < min(t["tiled"])
+        others = [u for f in ("rows", "dequant") if f in forms for u in t[f]]
+        if others:
+            row["tiled_wins"] = max(t["tiled"]) < min(others)
+        if "rows" in forms:
+            row["rows_TBps"] = [nbytes / max(t["rows"]) / 1e6, nbytes / min(t["rows"]) / 1e6]
+            if "dequant" in forms:
+                row["wins"] = max(t["rows"]) < min(t["dequant"])
         rows_out.append(row)
         print(json.dumps(row), flush=True)
     if a.out:
